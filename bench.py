@@ -24,6 +24,12 @@ packages in stream order and integrates into its hash-bucket shard of the one vo
 bit-deterministic, so the pose update needs no exchange beyond one RCCL MIN/MAX all-reduce that verifies it after the run.
 `value` = frames of the one stream / slowest rank.  Other modes: "segments" (independent stream segments per rank, weak scaling) and
 "volume-shard" (every rank bundles everything, the volume is sharded).
+
+A plain run measures the headline only: set-up, pre-roll, warm-up, the K timed steps, the line (with the roofline of the voxel update in
+those steps).  `--full` adds the secondary measurements, each a run of its own: the other arithmetic contract (`other_contract`), the serial
+order (`serial_order`), the class surface (`class_surface`), the CPU baseline (`cpu_baseline`), the 1280x960 @2 mm sweep (`sweep`) and the
+whole stream (`long_stream`).  `--dump-outputs DIR` writes what the timed path computed after its last step as DIR/<name>.npy (trajectories,
+the allocated block set and a seeded sample of the voxel blocks), so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -81,6 +87,10 @@ def main():
     ap.add_argument("--cpu-frames", type=int, default=31, help="frames of the stream the CPU baseline processes (three local chunks: the last ten frames "
                     "run with the re-integration queue saturated, like the timed window of the GPU leg)")
     ap.add_argument("--launch-check", action="store_true", help="(CPU test of the launch path) rendezvous over gloo, print the world size, exit")
+    ap.add_argument("--full", action="store_true", help="also run the secondary measurements (other contract, serial order, class surface, CPU baseline, "
+                    "sweep, long stream; each can still be left out with its own option); off: the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed path computed (trajectories, "
+                    "allocated blocks, a seeded sample of the voxel blocks) as DIR/<name>.npy, float32 / float64, rank 0")
     args = ap.parse_args()
 
     plan = launch_plan(args.gpus, os.environ, sys.argv[1:])
@@ -123,7 +133,7 @@ def main():
     # synthetic stream, rendered by plain-python subprocesses before HIP is initialised
     from bundlefusion_amd import synth                      # (imports torch; no device context yet)
     import numpy as np
-    ncpu = os.cpu_count() or 1
+    ncpu = usable_cpus()
     from bundlefusion_amd.shard import segment, max_over_ranks, same_over_ranks, ChunkedRunner
     mode = args.mode if args.mode != "auto" else ("chunks" if world > 1 else "serial")
     chunked = mode == "chunks"
@@ -206,8 +216,8 @@ def main():
     T0inv = np.linalg.inv(frames[0][2].astype(np.float64))
     gt = np.stack([T0inv @ f[2].astype(np.float64) for f in frames])
 
-    def run_leg(arith, solve_lag=None):
-        """The whole measurement (pre-roll, warm-up, K timed steps) with the voxel update under one arithmetic contract."""
+    def run_leg(arith, solve_lag=None, dump_dir=None):
+        """The whole measurement (pre-roll, warm-up, K timed steps) with the voxel update under one arithmetic contract; `dump_dir`: write its outputs there."""
         gas, gbs = params()
         pipe = bf.capi.Pipeline(gas, gbs, sensor_desc(W, H, K))
         pipe.scene().set_arith(arith)
@@ -279,6 +289,8 @@ def main():
         valid = np.isfinite(traj[:, 0, 0])
         L["frames_valid"], L["frames_total"] = int(valid.sum()), int(len(traj))
         L["ate"] = float(np.sqrt(np.mean(np.sum((traj[valid][:, :3, 3] - gt[:len(traj)][valid][:, :3, 3]) ** 2, axis=1)))) if valid.any() else None
+        if dump_dir and rank == 0:
+            dump_outputs(dump_dir, pipe)
         if runner is not None:
             runner.close()
         del sc, pipe, runner
@@ -353,12 +365,12 @@ def main():
             "share_of_step_time": (L["kernel_ms"] / 1e3) / L["elapsed"] if L["elapsed"] > 0 else None,
         }
 
-    main_leg = run_leg(args.arith)
+    main_leg = run_leg(args.arith, dump_dir=args.dump_outputs)
     other = None
-    if args.both_contracts and world == 1 and not args.pmc_out:
+    if args.full and args.both_contracts and world == 1 and not args.pmc_out:
         other = run_leg("exact" if args.arith == "fast" else "fast")
     serial = None
-    if args.both_contracts and world == 1 and not args.pmc_out and main_leg["solve_lag"] != 0 and not chunked:
+    if args.full and args.both_contracts and world == 1 and not args.pmc_out and main_leg["solve_lag"] != 0 and not chunked:
         # the same window in the serial order of the reference's single-threaded branch (the schedule of rounds 1-5's `value`), beside the default
         serial = run_leg(args.arith, solve_lag=0)
     if args.pmc_out and rank == 0:
@@ -429,12 +441,12 @@ def main():
                                    "timed_ops": {k: serial["c1"][k] - serial["c0"][k] for k in serial["c1"]}, "roofline": roofline_of(serial),
                                    "note": "the same window with the chunk solves inside the frame that closes the chunk (BF_PIPELINE_SOLVE_LAG=0): the reference's single-threaded "
                                            "branch, the schedule of every earlier round's `value`, and the one the oracle loop / the compiled reference loop are compared in"}
-        if not args.no_class_surface and world == 1 and not args.pmc_out and not args.host:
+        if args.full and not args.no_class_surface and world == 1 and not args.pmc_out and not args.host:
             try:
                 out["class_surface"] = class_surface_block(frames, pre, total, args, Kd, W, H, out["value"])
             except Exception as e:      # noqa: BLE001 - reported in the line
                 out["class_surface"] = {"error": "%s: %s" % (type(e).__name__, e)}
-        if not args.no_cpu_baseline and world == 1:          # reported at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:          # reported at N=1 only
             out["cpu_baseline"] = cpu_baseline(frames[:args.cpu_frames], feed[:args.cpu_frames], params, K, W, H, args.arith)
     del frames, feed
     # The secondary blocks must not cost the line its headline: an exception becomes {"error": ...}; a collective that never returns (the sweep's RCCL
@@ -471,7 +483,7 @@ def main():
         with line_lock:
             state["done"] = True
         return r
-    if not args.no_sweep:
+    if args.full and not args.no_sweep:
         sw = secondary("sweep", lambda: sweep_block(args, rank, world), 300)
         if rank == 0:
             with line_lock:
@@ -479,13 +491,55 @@ def main():
                 # the same update kernels on a volume far beyond the 256 MB Infinity Cache (1280x960 @2 mm, ~6 GB of blocks walked per sweep): what HBM itself delivers
                 g = (sw or {}).get("algorithmic_GBps_of_update_kernel_rank0") if isinstance(sw, dict) else None
                 out["roofline"]["frac_beyond_l3"] = (g / HBM_PEAK_GBS) if g else None
-    if args.long_stream and world == 1:
+    if args.full and args.long_stream and world == 1:
         ls = secondary("long_stream", lambda: long_stream_block(args, K, W, H), 1500)
         with line_lock:
             out["long_stream"] = ls
     print_line()
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_SAMPLE_BLOCKS = 2048      # voxel blocks in the dump's sample: 2048 x 512 voxels x (sdf + weight + 4 colour channels) x 4 bytes = 25 MB
+
+
+def dump_outputs(out_dir, pipe):
+    """What a caller of the timed path receives after its last step, as out_dir/<name>.npy: the integrated and the optimised trajectory
+    (float32 [frames, 4, 4], -inf rows for untracked frames), the allocated voxel blocks (float64 [n, 3] block coordinates in lexicographic
+    order, so that the file does not depend on where the heap placed them) and a sample of them: DUMP_SAMPLE_BLOCKS blocks drawn from that
+    order by a fixed seed, with their coordinates and their voxels' sdf, weight (float32 [s, 512]) and colour (float32 [s, 512, 4])."""
+    import numpy as np
+    from bundlefusion_amd.capi import FREE_ENTRY, HASH_BUCKET_SIZE, VOX_PER_BLOCK, VOXEL_DTYPE, HASH_ENTRY_DTYPE, _d2h
+    os.makedirs(out_dir, exist_ok=True)
+    pipe.synchronize()
+    np.save(os.path.join(out_dir, "integrated_trajectory.npy"), np.asarray(pipe.integrated_trajectory(), np.float32))
+    np.save(os.path.join(out_dir, "optimized_trajectory.npy"), np.asarray(pipe.optimized_trajectory(), np.float32))
+    sc = pipe.scene()
+    hd = sc.hash_data()
+    entries = _d2h(hd.d_hash, sc.params.m_hashNumBuckets * HASH_BUCKET_SIZE * HASH_ENTRY_DTYPE.itemsize).view(HASH_ENTRY_DTYPE)
+    occ = entries[entries["ptr"] != FREE_ENTRY]
+    pos = occ["pos"].astype(np.int64)
+    order = np.lexsort((pos[:, 2], pos[:, 1], pos[:, 0]))
+    pos, ptr = pos[order], occ["ptr"][order].astype(np.int64)
+    np.save(os.path.join(out_dir, "allocated_blocks.npy"), pos.astype(np.float64))
+    pick = np.sort(np.random.RandomState(12345).choice(len(pos), size=min(DUMP_SAMPLE_BLOCKS, len(pos)), replace=False)) if len(pos) else np.zeros(0, np.int64)
+    block_bytes = VOX_PER_BLOCK * VOXEL_DTYPE.itemsize
+    vox = np.stack([_d2h(hd.d_SDFBlocks + int(ptr[i]) * VOXEL_DTYPE.itemsize, block_bytes).view(VOXEL_DTYPE) for i in pick]) if len(pick) \
+        else np.zeros((0, VOX_PER_BLOCK), VOXEL_DTYPE)
+    np.save(os.path.join(out_dir, "sample_blocks.npy"), pos[pick].astype(np.float64))
+    np.save(os.path.join(out_dir, "sample_sdf.npy"), vox["sdf"].astype(np.float32))
+    np.save(os.path.join(out_dir, "sample_weight.npy"), vox["weight"].astype(np.float32))
+    np.save(os.path.join(out_dir, "sample_color.npy"), vox["color"].astype(np.float32))
+
+
+def usable_cpus():
+    """CPUs this process may run on: its affinity mask, capped by OMP_NUM_THREADS where the environment sets it.  os.cpu_count() counts the
+    whole machine, and a render pool sized by it on a machine shared under a CPU quota only competes with itself."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    if omp.isdigit() and int(omp) > 0:
+        n = min(n, int(omp))
+    return max(1, n)
 
 
 def visible_devices():
@@ -551,7 +605,7 @@ def long_stream_block(args, K, W, H):
         pipe.set_solve_lag(args.solve_lag)
     poses, marks, dev = [], [], []
     for c0 in range(0, n, 500):                                       # render and upload in batches (host memory); the whole stream is resident in HBM before the clock starts (5000 frames = 12 GB)
-        part = synth.render_frames(range(c0, min(c0 + 500, n)), W, H, bob=bob)
+        part = synth.render_frames(range(c0, min(c0 + 500, n)), W, H, workers=min(64, usable_cpus()), bob=bob)
         dev += [(torch.from_numpy(f[0]).cuda(), torch.from_numpy(f[1]).cuda()) for f in part]
         poses += [f[2] for f in part]
         del part

@@ -467,6 +467,53 @@ def test_bench_launches_its_own_ranks_and_refuses_a_mismatched_world():
     assert r.returncode != 0 and "{" not in r.stdout and "GPU(s) are visible" in r.stderr
 
 
+def test_bench_dump_outputs_layout(built, tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the files, their dtypes, the block order independent of heap placement, the seeded sample and the 64 MB bound,
+    on host-memory stand-ins for the pipeline's device arrays (the copies go through capi._d2h, replaced here by a host read)."""
+    sys.path.insert(0, ROOT)
+    import bench
+    from bundlefusion_amd import capi
+    monkeypatch.setattr(capi, "_d2h", lambda ptr, nbytes: np.frombuffer((C.c_uint8 * nbytes).from_address(ptr), np.uint8).copy())
+    rng = np.random.RandomState(3)
+    n_buckets, n_alloc = 4000, 3000
+    pos = np.unique(rng.randint(-60, 60, size=(2 * n_alloc, 3)), axis=0)[:n_alloc]
+    vox = np.zeros(n_alloc * capi.VOX_PER_BLOCK, capi.VOXEL_DTYPE)
+    vox["sdf"] = rng.standard_normal(len(vox)); vox["weight"] = rng.randint(0, 99, len(vox)); vox["color"] = rng.randint(0, 255, (len(vox), 4))
+
+    def pipe_with(heap_order):          # the same volume with its blocks at other heap slots and hash entries
+        ent = np.zeros(n_buckets * capi.HASH_BUCKET_SIZE, capi.HASH_ENTRY_DTYPE); ent["ptr"] = capi.FREE_ENTRY
+        slots = rng.choice(len(ent), n_alloc, replace=False)
+        ent["pos"][slots] = pos; ent["ptr"][slots] = heap_order * capi.VOX_PER_BLOCK
+        heap = np.empty_like(vox).reshape(n_alloc, -1)
+        heap[heap_order] = vox.reshape(n_alloc, -1)
+        hd = capi.HashData(); hd.d_hash = ent.ctypes.data; hd.d_SDFBlocks = heap.ctypes.data
+        traj = np.tile(np.eye(4, dtype=np.float32), (9, 1, 1)); traj[3] = -np.inf
+        scene = type("Scene", (), {"params": type("P", (), {"m_hashNumBuckets": n_buckets})(), "hash_data": lambda self: hd})()
+        pipe = type("Pipe", (), {"synchronize": lambda self: None, "integrated_trajectory": lambda self: traj, "optimized_trajectory": lambda self: traj + 1,
+                                 "scene": lambda self: scene})()
+        return pipe, (ent, heap)
+
+    outs = []
+    for k, order in enumerate((np.arange(n_alloc), rng.permutation(n_alloc))):
+        pipe, _alive = pipe_with(order)          # (_alive: the host arrays behind the stand-in pointers)
+        bench.dump_outputs(str(tmp_path / str(k)), pipe)
+        outs.append({f[:-4]: np.load(str(tmp_path / str(k) / f)) for f in os.listdir(str(tmp_path / str(k)))})
+    a, b = outs
+    assert sorted(a) == ["allocated_blocks", "integrated_trajectory", "optimized_trajectory", "sample_blocks", "sample_color", "sample_sdf", "sample_weight"]
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64 << 20
+    for name in a:
+        assert np.array_equal(a[name], b[name]), name               # heap placement does not show
+    blocks = a["allocated_blocks"]
+    assert blocks.shape == (n_alloc, 3) and np.array_equal(blocks, pos[np.lexsort((pos[:, 2], pos[:, 1], pos[:, 0]))].astype(np.float64))
+    s = a["sample_blocks"]
+    assert s.shape == (bench.DUMP_SAMPLE_BLOCKS, 3) and a["sample_sdf"].shape == (bench.DUMP_SAMPLE_BLOCKS, capi.VOX_PER_BLOCK)
+    row = {tuple(p): i for i, p in enumerate(pos.tolist())}
+    for k in range(0, len(s), 101):
+        v = vox.reshape(n_alloc, -1)[row[tuple(int(c) for c in s[k])]]
+        assert np.array_equal(a["sample_sdf"][k], v["sdf"]) and np.array_equal(a["sample_weight"][k], v["weight"]) and np.array_equal(a["sample_color"][k], v["color"])
+    assert np.isneginf(a["integrated_trajectory"][3]).all() and a["integrated_trajectory"].shape == (9, 4, 4)
+
+
 _POSEHELPER_CPP = r'''
 #include "bundlefusion/bundlefusion.hpp"
 using namespace bundlefusion;

@@ -26,7 +26,7 @@ for step in $STEPS; do
       (cd "$ROOT" && timeout 300 python __graft_entry__.py --smoke 2>&1 | tail -3 | tee "$OUT/smoke.txt") ;;
     long)       # BASELINE configs[2] (2000-frame loop closure) and configs[3] (5000 frames) at full length through bench.py's long_stream block
       for N in ${LONG_FRAMES:-2000 5000}; do
-        (cd "$ROOT" && timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --one-contract --no-sweep --long-stream $N > "$OUT/bench_long_$N.json" 2> "$OUT/bench_long_$N.err"; python -c "
+        (cd "$ROOT" && timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline --one-contract --no-sweep --long-stream $N > "$OUT/bench_long_$N.json" 2> "$OUT/bench_long_$N.err"; python -c "
 import json; j=json.load(open('$OUT/bench_long_$N.json'))['long_stream']; print({k: j[k] for k in ('frames','value','last_over_first','frames_tracked','ate_integrated_m','ate_optimized_m','counters')})"; tail -2 "$OUT/bench_long_$N.err")
       done ;;
     probe)
@@ -34,9 +34,9 @@ import json; j=json.load(open('$OUT/bench_long_$N.json'))['long_stream']; print(
     tests_new)
       (cd "$ROOT" && timeout 900 python -m pytest tests/test_pipeline_baseline_gpu.py -x -q --durations=8 2>&1 | tail -25 | tee "$OUT/pytest_new.txt") ;;
     bench)
-      (cd "$ROOT" && timeout 400 python bench.py $BENCH_ARGS > "$OUT/bench.json" 2> "$OUT/bench.err"; cut -c1-260 "$OUT/bench.json"; tail -3 "$OUT/bench.err") ;;
-    bench_driver)   # the driver's invocation
-      (cd "$ROOT" && timeout 400 python bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_driver.json" 2> "$OUT/bench_driver.err"; cut -c1-260 "$OUT/bench_driver.json"; tail -3 "$OUT/bench_driver.err") ;;
+      (cd "$ROOT" && timeout 600 python bench.py --full $BENCH_ARGS > "$OUT/bench.json" 2> "$OUT/bench.err"; cut -c1-260 "$OUT/bench.json"; tail -3 "$OUT/bench.err") ;;
+    bench_driver)   # the driver's invocation, with --full: the recorded lines hold the secondary blocks too
+      (cd "$ROOT" && timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT/bench_driver.json" 2> "$OUT/bench_driver.err"; cut -c1-260 "$OUT/bench_driver.json"; tail -3 "$OUT/bench_driver.err") ;;
     bench_env)      # the driver's window under environment variants: ENVS="A=1;B=2 C=3" runs once per ';'-separated assignment list
       IFS=';' read -ra VARIANTS <<< "${ENVS:-}"
       for V in "${VARIANTS[@]}"; do
