@@ -873,6 +873,140 @@ def sensor_desc(width, height, K):
     return s
 
 
+# --------------------------------------------------------------------------- frame-ingest image operators (csrc/imageops.hip)
+# torch device tensors in; an image's size is its tensor's (h, w) shape (uint8 colour: (h, w, 4)).  `stream`: a hipStream_t (0: the null stream).
+def _p(t):
+    return C.c_void_p(t.data_ptr() if t is not None else None)
+
+
+def image_erode_depth_map(out, inp, structure_size=3, d_thresh=0.05, frac_req=0.3, stream=0):
+    h, w = inp.shape[:2]
+    check(lib.bf_image_erode_depth_map(_p(out), _p(inp), int(structure_size), w, h, C.c_float(d_thresh), C.c_float(frac_req), C.c_void_p(stream)))
+
+
+def image_erode_depth_map_and_copy(out, inp, copy_src, copy_dst1, copy_dst2=None, structure_size=3, d_thresh=0.05, frac_req=0.3, stream=0):
+    """the erosion with a pixel-wise copy of a 4-byte-per-pixel image of the same size riding along (copy_src -> copy_dst1 and, if given, copy_dst2)"""
+    h, w = inp.shape[:2]
+    check(lib.bf_image_erode_depth_map_and_copy(_p(out), _p(inp), int(structure_size), w, h, C.c_float(d_thresh), C.c_float(frac_req),
+                                                _p(copy_src), _p(copy_dst1), _p(copy_dst2), C.c_void_p(stream)))
+
+
+def image_gauss_filter_depth_map(out, inp, sigma_d, sigma_r, stream=0):
+    h, w = inp.shape[:2]
+    check(lib.bf_image_gauss_filter_depth_map(_p(out), _p(inp), C.c_float(sigma_d), C.c_float(sigma_r), w, h, C.c_void_p(stream)))
+
+
+def image_gauss_filter_depth_map2(out, out2, inp, sigma_d, sigma_r, stream=0):
+    h, w = inp.shape[:2]
+    check(lib.bf_image_gauss_filter_depth_map2(_p(out), _p(out2), _p(inp), C.c_float(sigma_d), C.c_float(sigma_r), w, h, C.c_void_p(stream)))
+
+
+def image_gauss_filter_intensity(out, inp, sigma_d, stream=0):
+    h, w = inp.shape[:2]
+    check(lib.bf_image_gauss_filter_intensity(_p(out), _p(inp), C.c_float(sigma_d), w, h, C.c_void_p(stream)))
+
+
+def image_resample_float(out, inp, stream=0):
+    (oh, ow), (ih, iw) = out.shape[:2], inp.shape[:2]
+    check(lib.bf_image_resample_float(_p(out), ow, oh, _p(inp), iw, ih, C.c_void_p(stream)))
+
+
+def image_resample_uchar4(out, inp, stream=0):
+    (oh, ow), (ih, iw) = out.shape[:2], inp.shape[:2]
+    check(lib.bf_image_resample_uchar4(_p(out), ow, oh, _p(inp), iw, ih, C.c_void_p(stream)))
+
+
+def image_resample_to_intensity(out, inp, stream=0):
+    (oh, ow), (ih, iw) = out.shape[:2], inp.shape[:2]
+    check(lib.bf_image_resample_to_intensity(_p(out), ow, oh, _p(inp), iw, ih, C.c_void_p(stream)))
+
+
+def image_interleave_texels(texels, depth, color, stream=0):
+    """{depth f32 bits, colour RGBX8} per pixel: `texels` holds depth.numel() x 8 bytes"""
+    check(lib.bf_image_interleave_texels(_p(texels), _p(depth), _p(color), depth.numel(), C.c_void_p(stream)))
+
+
+class ImageManager:
+    """Python view of `bf_image_manager` (== the reference's CUDAImageManager): the frame ingest (erosion, depth filter, resampling) and the
+    frames stored at integration resolution.  store_frames_on_gpu: 1 slabs of frames in device memory, 0 host copies (the reference's default),
+    2 one device slot that every frame overwrites."""
+
+    def __init__(self, gas, gbs, sensor, store_frames_on_gpu=1):
+        self._h = C.c_void_p()
+        self.sensor = sensor
+        self.w, self.h = gas.s_integrationWidth, gas.s_integrationHeight
+        check(lib.bf_image_manager_create(self.w, self.h, gbs.s_widthSIFT, gbs.s_heightSIFT, C.byref(sensor), C.byref(gbs), int(store_frames_on_gpu),
+                                          C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib.bf_image_manager_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_store_texels(self, enable=True):
+        check(lib.bf_image_manager_set_store_texels(self._h, int(enable)))
+
+    def reset(self):
+        check(lib.bf_image_manager_reset(self._h))
+
+    def process(self, depth, color):
+        """host numpy frame (sensor resolution: depth float32 (h, w), colour uint8 (h, w, 4)) -> whether a frame was stored"""
+        depth = np.ascontiguousarray(depth, np.float32); color = np.ascontiguousarray(color, np.uint8)
+        got = C.c_int()
+        check(lib.bf_image_manager_process(self._h, depth.ctypes.data_as(C.c_void_p), color.ctypes.data_as(C.c_void_p), C.byref(got)))
+        return bool(got.value)
+
+    def process_device(self, depth, color):
+        """the same from torch device tensors"""
+        got = C.c_int()
+        check(lib.bf_image_manager_process_device(self._h, _p(depth), _p(color), C.byref(got)))
+        return bool(got.value)
+
+    def get_input_gpu(self):
+        """host copies of the last frame's sensor-resolution buffers: (raw depth, filtered depth, colour)"""
+        import torch
+        torch.cuda.synchronize()
+        raw, filt, col = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        check(lib.bf_image_manager_get_input_gpu(self._h, C.byref(raw), C.byref(filt), C.byref(col)))
+        s = self.sensor
+        nd, nc = s.depthWidth * s.depthHeight, s.colorWidth * s.colorHeight
+        return (_d2h(raw.value, nd * 4).view("<f4").reshape(s.depthHeight, s.depthWidth),
+                _d2h(filt.value, nd * 4).view("<f4").reshape(s.depthHeight, s.depthWidth),
+                _d2h(col.value, nc * 4).reshape(s.colorHeight, s.colorWidth, 4))
+
+    def get_integrate_frame_cpu(self, frame):
+        """host copies (depth float32 (h, w), colour uint8 (h, w, 4)) of a stored frame at integration resolution"""
+        import torch
+        torch.cuda.synchronize()
+        d = np.zeros((self.h, self.w), np.float32); c = np.zeros((self.h, self.w, 4), np.uint8)
+        check(lib.bf_image_manager_get_integrate_frame_cpu(self._h, frame, d.ctypes.data_as(C.c_void_p), c.ctypes.data_as(C.c_void_p)))
+        return d, c
+
+    def get_integrate_frame_texels(self, frame):
+        """host copy (uint8 (h, w, 8)) of a stored frame's interleaved texels, or None where the manager keeps none"""
+        import torch
+        torch.cuda.synchronize()
+        p = C.c_void_p()
+        check(lib.bf_image_manager_get_integrate_frame_texels(self._h, frame, C.byref(p)))
+        return None if not p.value else _d2h(p.value, self.w * self.h * 8).reshape(self.h, self.w, 8)
+
+    def num_frames(self):
+        n = C.c_uint32()
+        check(lib.bf_image_manager_get_num_frames(self._h, C.byref(n)))
+        return n.value
+
+    def curr_frame_number(self):
+        n = C.c_uint32()
+        check(lib.bf_image_manager_get_curr_frame_number(self._h, C.byref(n)))
+        return n.value
+
+
 _ALL_GATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p)
 
 

@@ -154,47 +154,56 @@ def cache_store_frame(depth, color, W, H, input_intrinsics, sigma_intensity=2.5,
     return out
 
 
-def erode_depth(depth, structure_size=3, d_thresh=0.05, frac_req=0.3):
+def _out(init, shape, dtype, fill):
+    """the output buffer an operator writes into: a copy of `init` (the pixels the operator leaves unwritten keep its values), else `fill`"""
+    if init is None:
+        return np.full(shape, fill, dtype)
+    init = np.array(init, dtype=dtype, copy=True, order="C")
+    assert init.shape == tuple(shape)
+    return init
+
+
+def erode_depth(depth, structure_size=3, d_thresh=0.05, frac_req=0.3, out=None):
     depth = np.ascontiguousarray(depth, dtype=np.float32)
-    out = np.empty_like(depth)
+    out = _out(out, depth.shape, np.float32, np.nan)
     h, w = depth.shape
     olib.or_erode_depth(_fp(out), _fp(depth), structure_size, w, h, C.c_float(d_thresh), C.c_float(frac_req))
     return out
 
 
-def gauss_filter_depth(depth, sigma_d, sigma_r):
+def gauss_filter_depth(depth, sigma_d, sigma_r, out=None):
     depth = np.ascontiguousarray(depth, dtype=np.float32)
-    out = np.empty_like(depth)
+    out = _out(out, depth.shape, np.float32, np.nan)
     h, w = depth.shape
     olib.or_gauss_filter_depth(_fp(out), _fp(depth), C.c_float(sigma_d), C.c_float(sigma_r), w, h)
     return out
 
 
-def gauss_filter_intensity(img, sigma_d):
+def gauss_filter_intensity(img, sigma_d, out=None):
     img = np.ascontiguousarray(img, dtype=np.float32)
-    out = np.full_like(img, np.nan)
+    out = _out(out, img.shape, np.float32, np.nan)
     h, w = img.shape
     olib.or_gauss_filter_intensity(_fp(out), _fp(img), C.c_float(sigma_d), w, h)
     return out
 
 
-def resample_float(img, ow, oh):
+def resample_float(img, ow, oh, out=None):
     img = np.ascontiguousarray(img, dtype=np.float32)
-    out = np.full((oh, ow), np.nan, np.float32)
+    out = _out(out, (oh, ow), np.float32, np.nan)
     olib.or_resample_float(_fp(out), ow, oh, _fp(img), img.shape[1], img.shape[0])
     return out
 
 
-def resample_uchar4(img, ow, oh):
+def resample_uchar4(img, ow, oh, out=None):
     img = np.ascontiguousarray(img, dtype=np.uint8)
-    out = np.zeros((oh, ow, 4), np.uint8)
+    out = _out(out, (oh, ow, 4), np.uint8, 0)
     olib.or_resample_uchar4(_fp(out), ow, oh, _fp(img), img.shape[1], img.shape[0])
     return out
 
 
-def resample_to_intensity(img, ow, oh):
+def resample_to_intensity(img, ow, oh, out=None):
     img = np.ascontiguousarray(img, dtype=np.uint8)
-    out = np.full((oh, ow), np.nan, np.float32)
+    out = _out(out, (oh, ow), np.float32, np.nan)
     olib.or_resample_to_intensity(_fp(out), ow, oh, _fp(img), img.shape[1], img.shape[0])
     return out
 

@@ -246,6 +246,74 @@ def test_ingest_and_resample_kernels(oracle):
     assert _same(integ_r, ref_api.resample_float(filt_r, 80, 60))
 
 
+def _edge_depth(w, h, seed):
+    """depth blocks whose neighbours differ by just under / just over 0.05 (dThresh == sigmaR), with -inf, 0.0 and a few NaNs"""
+    rng = np.random.default_rng(seed)
+    levels = np.float32([1.0, 1.0499, 1.0501, 1.0998, 1.1002])
+    d = np.repeat(np.repeat(levels[rng.integers(0, 5, ((h + 1) // 2, (w + 2) // 3))], 2, axis=0), 3, axis=1)[:h, :w].copy()
+    u = rng.random((h, w))
+    d[u < 0.04] = -np.inf
+    d[(u >= 0.04) & (u < 0.06)] = 0.0
+    d[(u >= 0.06) & (u < 0.063)] = np.nan
+    return d
+
+
+def test_ingest_kernels_at_edge_shapes_and_every_radius(oracle):
+    """The operators tests/test_ingest_gpu.py holds the HIP kernels to, at its edge shapes: erosion with structure sizes 0 / 1 / 3 / 5 and
+    fracReq values that land exactly on a count ratio (exact); both Gaussians at sigma 0.25 / 1 / 2 / 4, radius 1 to 8 (3e-6, the set of valid
+    pixels exactly); resampling up, down, at non-integer ratios, to width 2 and from width or height 1 (exact).  A Gaussian with sigma 0 is
+    left out: its taps are exp(-0 / 0), NaN, in the reference too."""
+    for w, h in ((1, 1), (2, 3), (63, 5), (65, 4), (130, 1), (97, 61)):
+        d = _edge_depth(w, h, w + h)
+        for s, a, b in ((0, 1, 1), (1, 3, 9), (3, 3, 10), (3, 15, 49), (5, 40, 121)):
+            frac = float(np.float32(a) / np.float32(b))
+            assert _same(oracle.erode_depth(d, s, 0.05, frac), ref_api.erode_depth(d, s, 0.05, frac)), (w, h, s, a, b)
+        img = np.random.default_rng(w * h).random((h, w)).astype(np.float32)
+        for sigma in (0.25, 1.0, 2.0, 4.0):
+            g_o, g_r = oracle.gauss_filter_depth(d, sigma, 0.05), ref_api.gauss_filter_depth(d, sigma, 0.05)
+            v = np.isfinite(g_o)
+            assert np.array_equal(v, np.isfinite(g_r)) and _same(g_o[~v], g_r[~v]), (w, h, sigma)
+            assert not v.any() or np.abs(g_o[v] - g_r[v]).max() <= 3e-6 * np.abs(g_r[v]).max(), (w, h, sigma)
+            i_o, i_r = oracle.gauss_filter_intensity(img, sigma), ref_api.gauss_filter_intensity(img, sigma)
+            assert np.abs(i_o - i_r).max() <= 3e-6, (w, h, sigma)
+    for (iw, ih), (ow, oh) in (((64, 4), (130, 5)), ((130, 5), (63, 3)), ((65, 3), (2, 2)), ((1, 97), (64, 5)), ((97, 1), (65, 4)), ((1, 1), (2, 2)),
+                               ((63, 5), (161, 121))):
+        d = _edge_depth(iw, ih, iw * ih)
+        c = np.random.default_rng(iw + ih).integers(0, 256, (ih, iw, 4), dtype=np.uint8)
+        assert _same(oracle.resample_float(d, ow, oh), ref_api.resample_float(d, ow, oh)), (iw, ih, ow, oh)
+        assert _same(oracle.resample_uchar4(c, ow, oh), ref_api.resample_uchar4(c, ow, oh)), (iw, ih, ow, oh)
+        assert _same(oracle.resample_to_intensity(c, ow, oh), ref_api.resample_to_intensity(c, ow, oh)), (iw, ih, ow, oh)
+
+
+def test_cache_store_frame_at_edge_shapes_vs_reference_kernels(oracle):
+    """CUDACache::storeFrame at the cache sizes tests/test_ingest_gpu.py runs (partial tiles, a partial workgroup, 2 x 2), colour at another size
+    than depth, and the sigma pairs it runs: 0 (the reference skips the filter: defined), 3 (radius 6) and the defaults."""
+    rng = np.random.default_rng(5)
+    dw, dh, cw, ch = 161, 121, 200, 150
+    d, _, _, Kd = synth.scene_room(40, dw, dh)
+    c = synth.scene_room(40, cw, ch)[1]
+    d = (d + rng.normal(0, 0.004, d.shape)).astype(np.float32)
+    d[dh // 3: dh // 3 + 7, dw // 2: dw // 2 + 20] = -np.inf
+    d[rng.random(d.shape) < 0.01] = -np.inf
+    K = intrinsics_matrix(Kd["fx"], Kd["fy"], Kd["mx"], Kd["my"])
+    for W, H in ((81, 61), (100, 75), (17, 13), (16, 12), (2, 2)):
+        for cs, ds in ((2.5, 1.0), (0.0, 0.0), (3.0, 3.0), (0.0, 3.0), (3.0, 0.0)):
+            fo = oracle.cache_store_frame(d, c, W, H, K, cs, ds, 0.05)
+            fr = ref_api.cache_store_frame(d, c, W, H, oracle.mat4_inverse(K), cs, ds, 0.05)
+            for name in ("depth", "campos", "normals", "intensity", "derivs"):
+                fin_o, fin_r = np.isfinite(fo[name]), np.isfinite(fr[name])
+                assert np.array_equal(fin_o, fin_r) and _same(fo[name][~fin_o], fr[name][~fin_r]), (W, H, cs, ds, name)
+                if not fin_o.any():
+                    continue                        # 2 x 2: no interior pixel, every normal and derivative is -inf
+                tol = 3e-6 if name != "normals" else 2e-5
+                assert np.abs(fo[name][fin_o] - fr[name][fin_r]).max() <= tol * max(1.0, np.abs(fr[name][fin_r]).max()), (W, H, cs, ds, name)
+            assert np.abs(fo["normals_u"].astype(int) - fr["normals_u"].astype(int)).max() <= 1, (W, H, cs, ds)
+            if cs == 0.0:                           # unfiltered intensity: point samples, exact
+                assert _same(fo["intensity"], fr["intensity"]), (W, H)
+            if ds == 0.0:                           # unfiltered depth: point samples and +, -, * only, exact
+                assert _same(fo["depth"], fr["depth"]) and _same(fo["campos"], fr["campos"]), (W, H)
+
+
 def test_cache_store_frame_vs_reference_kernels(oracle):
     """CUDACache::storeFrame: the six arrays of one 80x60 cache frame from a 320x240 input and from a 640x480 one, clean and with depth noise + holes."""
     rng = np.random.default_rng(4)
