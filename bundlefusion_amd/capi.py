@@ -533,6 +533,20 @@ class Solver:
         check(lib.bf_solver_debug_dense_system(self._h, JtJ.ctypes.data_as(C.c_void_p), Jtr.ctypes.data_as(C.c_void_p), n, C.byref(npairs)))
         return JtJ, Jtr, npairs.value
 
+    def debug_system(self, n):
+        """the last Gauss-Newton iteration's A (6N x 6N), b = -J^T F and M^-1 in the reference's layout"""
+        dim = 6 * n
+        A = np.zeros((dim, dim), dtype=np.float32)
+        b = np.zeros(dim, dtype=np.float32)
+        prec = np.zeros(dim, dtype=np.float32)
+        check(lib.bf_solver_debug_system(self._h, A.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), prec.ctypes.data_as(C.c_void_p), n))
+        return A, b, prec
+
+    def slot_overflow(self):
+        v = C.c_uint32()
+        check(lib.bf_solver_get_slot_overflow(self._h, C.byref(v)))
+        return v.value
+
 
 def convert_matrices_to_poses(T, rot, trans, valid, stream=0):
     check(lib.bf_convert_matrices_to_poses(C.c_void_p(T.data_ptr()), T.shape[0], C.c_void_p(rot.data_ptr()), C.c_void_p(trans.data_ptr()),

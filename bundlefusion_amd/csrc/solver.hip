@@ -35,7 +35,7 @@ constexpr int DENSE_BLK = 120;                   // ii(36) jj(36) ij(36) gi(6) g
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-enum Flag { FL_DONE = 0, FL_NUM_SLOTS = 1, FL_NUM_PAIRS = 2, FL_LIST_LEN = 3, FL_GN_ITERS = 4, FL_BARRIER_FAIL = 5, FL_PCG_ITERS = 8, FL_COUNT = 40 };
+enum Flag { FL_DONE = 0, FL_NUM_SLOTS = 1, FL_NUM_PAIRS = 2, FL_LIST_LEN = 3, FL_GN_ITERS = 4, FL_BARRIER_FAIL = 5, FL_SLOT_OVERFLOW = 6, FL_PCG_ITERS = 8, FL_COUNT = 40 };
 
 struct Cfg {
     float denseDistThresh, denseNormalThresh, denseColorThresh, denseColorGradientMin, denseDepthMin, denseDepthMax;
@@ -160,7 +160,7 @@ __global__ __launch_bounds__(1024) void k_scan_base(Dev d) {
     for (uint32_t r = r0; r < r1; ++r) {
         const uint32_t ta = d.scanRow[r * 3], tb = d.scanRow[r * 3 + 1], tc = d.scanRow[r * 3 + 2];
         d.scanRow[r * 3] = ra; d.scanRow[r * 3 + 1] = rb; d.scanRow[r * 3 + 2] = rc;      // exclusive bases of row r
-        d.rowStart[r] = rb;
+        d.rowStart[r] = min(rb, d.maxSlots);      // every row range stays inside the slot arrays (k_scan_fill writes only slots < maxSlots)
         ra += ta; rb += tb; rc += tc;
     }
     if (threadIdx.x == blockDim.x - 1) {
@@ -168,6 +168,7 @@ __global__ __launch_bounds__(1024) void k_scan_base(Dev d) {
         d.flags[FL_LIST_LEN] = (int)ra;
         d.flags[FL_NUM_SLOTS] = (int)min(rb, d.maxSlots);
         d.flags[FL_NUM_PAIRS] = (int)min(rc, d.maxPairs);
+        if (rb > d.maxSlots) d.flags[FL_SLOT_OVERFLOW] = max(d.flags[FL_SLOT_OVERFLOW], (int)(rb - d.maxSlots));   // directed slots that did not fit
     }
 }
 
@@ -1320,6 +1321,45 @@ int bf_solver_debug_dense_system(bf_solver* s, float* hJtJ, float* hJtr, uint32_
     BF_HIP_TRY(hipStreamSynchronize(s->stream));
     *numPairs = s->lastUsedDense ? flags[FL_NUM_PAIRS] : 0;
     (void)hipFree(dJ); (void)hipFree(dr);
+    return BF_OK;
+}
+
+// the last Gauss-Newton iteration's system in the reference's 6N layout, expanded on the host from the CSR blocks the PCG reads
+int bf_solver_debug_system(bf_solver* s, float* hA, float* hb, float* hPrec, uint32_t N) {
+    BF_REQUIRE(s && hA && hb && hPrec && N == s->lastN, "bad argument");
+    const size_t dim = 6 * (size_t)N;
+    hipStream_t st = s->stream;
+    std::vector<uint32_t> rowStart(N + 1);
+    BF_HIP_TRY(hipMemcpyAsync(rowStart.data(), s->d.rowStart, (N + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    BF_HIP_TRY(hipStreamSynchronize(st));
+    const uint32_t nSlots = rowStart[N];
+    std::vector<uint32_t> col(std::max<uint32_t>(nSlots, 1));
+    std::vector<float> O((size_t)std::max<uint32_t>(nSlots, 1) * 36), D((size_t)N * 36);
+    if (nSlots) {
+        BF_HIP_TRY(hipMemcpyAsync(col.data(), s->d.slotCol, nSlots * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        BF_HIP_TRY(hipMemcpyAsync(O.data(), s->d.slotO, (size_t)nSlots * 36 * sizeof(float), hipMemcpyDeviceToHost, st));
+    }
+    BF_HIP_TRY(hipMemcpyAsync(D.data(), s->d.diagA, D.size() * sizeof(float), hipMemcpyDeviceToHost, st));
+    BF_HIP_TRY(hipMemcpyAsync(hb, s->d.rhs, dim * sizeof(float), hipMemcpyDeviceToHost, st));
+    BF_HIP_TRY(hipMemcpyAsync(hPrec, s->d.prec, dim * sizeof(float), hipMemcpyDeviceToHost, st));
+    BF_HIP_TRY(hipStreamSynchronize(st));
+    std::fill(hA, hA + dim * dim, 0.0f);
+    for (uint32_t i = 0; i < N; ++i) {
+        for (uint32_t a = 0; a < 6; ++a)
+            for (uint32_t b = 0; b < 6; ++b) hA[(6 * i + a) * dim + 6 * i + b] += D[(size_t)i * 36 + a * 6 + b];
+        for (uint32_t sl = rowStart[i]; sl < rowStart[i + 1]; ++sl)
+            for (uint32_t a = 0; a < 6; ++a)
+                for (uint32_t b = 0; b < 6; ++b) hA[(6 * i + a) * dim + 6 * (size_t)col[sl] + b] += O[(size_t)sl * 36 + a * 6 + b];
+    }
+    return BF_OK;
+}
+
+int bf_solver_get_slot_overflow(bf_solver* s, uint32_t* numSlotsDropped) {
+    BF_REQUIRE(s && numSlotsDropped, "null argument");
+    int v = 0;
+    BF_HIP_TRY(hipMemcpyAsync(&v, s->d.flags + FL_SLOT_OVERFLOW, sizeof v, hipMemcpyDeviceToHost, s->stream));
+    BF_HIP_TRY(hipStreamSynchronize(s->stream));
+    *numSlotsDropped = (uint32_t)std::max(v, 0);
     return BF_OK;
 }
 

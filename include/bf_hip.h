@@ -364,6 +364,12 @@ BF_API int bf_solver_get_iteration_counts(bf_solver* s, int32_t* out, uint32_t c
 /* dump of the last dense system in the reference's layout (6N x 6N row-major JtJ, 6N Jtr);
  * test hook, syncs.  numPairs = #overlapping image pairs found.                              */
 BF_API int bf_solver_debug_dense_system(bf_solver* s, float* h_JtJ, float* h_Jtr, uint32_t numImages, int32_t* numPairs);
+/* dump of the last Gauss-Newton iteration's whole system in the reference's layout: A (6N x 6N row-major, sparse + dense),
+ * b = -J^T F (6N) and the Jacobi preconditioner M^-1 (6N); test hook, syncs.  Image 0 is not a variable. */
+BF_API int bf_solver_debug_system(bf_solver* s, float* h_A, float* h_b, float* h_prec, uint32_t numImages);
+/* directed image pairs of the last solve that did not fit the solver's block capacity (min(N^2, 2C + 4N) for N > 64 images):
+ * their blocks are left out of the system.  0 when everything fit.  Syncs. */
+BF_API int bf_solver_get_slot_overflow(bf_solver* s, uint32_t* numSlotsDropped);
 
 /* convertMatricesToPosesCU / convertPosesToMatricesCU          SBA.cu:75-108 (Lie space) */
 BF_API int bf_convert_matrices_to_poses(const float* d_transforms, uint32_t numTransforms, float* d_rot, float* d_trans,
