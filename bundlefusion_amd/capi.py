@@ -940,6 +940,50 @@ def image_interleave_texels(texels, depth, color, stream=0):
     check(lib.bf_image_interleave_texels(_p(texels), _p(depth), _p(color), depth.numel(), C.c_void_p(stream)))
 
 
+# --------------------------------------------------------------------------- sensor-format ingest (csrc/sensoringest.hip)
+BF_ERR_NOT_ON_DEVICE = -6
+
+
+class JpegComponent(C.Structure):
+    _fields_ = [("h", C.c_uint32), ("v", C.c_uint32), ("tq", C.c_uint32), ("blocksX", C.c_uint32), ("blocksY", C.c_uint32), ("blockOffset", C.c_uint32),
+                ("planeOffset", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class JpegInfo(C.Structure):
+    """bf_jpeg_info: a baseline JPEG frame between its entropy decode and its reconstruction (layout of the coefficient buffer: include/bf_hip.h)"""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("numComponents", C.c_uint32), ("hmax", C.c_uint32), ("vmax", C.c_uint32), ("mcusX", C.c_uint32),
+                ("mcusY", C.c_uint32), ("restartInterval", C.c_uint32), ("numBlocks", C.c_uint32), ("planeBytes", C.c_uint32), ("comp", JpegComponent * 3),
+                ("qt", (C.c_uint16 * 64) * 4), ("qtPresent", C.c_uint8 * 4)]
+
+
+def image_convert_depth_u16(out, inp, depth_shift, stream=0):
+    """u16 depth -> float32 metres (0 -> -inf); torch device tensors, out.numel() == inp.numel()"""
+    check(lib.bf_image_convert_depth_u16(_p(out), _p(inp), C.c_float(depth_shift), inp.numel(), C.c_void_p(stream)))
+
+
+def image_convert_rgb8_to_rgbx(out, inp, stream=0):
+    """RGB8 (n x 3 bytes) -> RGBX8 with X = 255"""
+    check(lib.bf_image_convert_rgb8_to_rgbx(_p(out), _p(inp), inp.numel() // 3, C.c_void_p(stream)))
+
+
+def jpeg_reconstruct_device(info, coefficients, planes, rgbx, stream=0):
+    """quantised coefficients (int16 device tensor) -> RGBX8 (h, w, 4); planes: info.planeBytes bytes of device scratch.  Returns False where the device
+    declines the layout (BF_ERR_NOT_ON_DEVICE: decode on the host), raises on every other failure."""
+    rc = lib.bf_jpeg_reconstruct_device(C.byref(info), _p(coefficients), _p(planes), _p(rgbx), C.c_void_p(stream))
+    if rc == BF_ERR_NOT_ON_DEVICE:
+        return False
+    check(rc)
+    return True
+
+
+def _raw_colour(colour, jpeg):
+    """the colour argument of the *_raw_decoded / *_raw_device calls as (pointer, keep-alive)"""
+    if isinstance(colour, np.ndarray):
+        colour = np.ascontiguousarray(colour, np.int16 if jpeg is not None else np.uint8)
+        return colour.ctypes.data_as(C.c_void_p), colour
+    return C.c_void_p(colour.data_ptr()), colour
+
+
 class ImageManager:
     """Python view of `bf_image_manager` (== the reference's CUDAImageManager): the frame ingest (erosion, depth filter, resampling) and the
     frames stored at integration resolution.  store_frames_on_gpu: 1 slabs of frames in device memory, 0 host copies (the reference's default),
@@ -980,6 +1024,26 @@ class ImageManager:
         """the same from torch device tensors"""
         got = C.c_int()
         check(lib.bf_image_manager_process_device(self._h, _p(depth), _p(color), C.byref(got)))
+        return bool(got.value)
+
+    def process_raw(self, depth_u16, depth_shift, colour, compression=0, jpeg=None):
+        """A frame in sensor format, converted / reconstructed on the device (bf_image_manager_process_raw*).  depth_u16: uint16 (h, w).  colour: the stored
+        bytes (`bytes` / uint8 array; compression 0 raw RGB8, 1 PNG, 2 JPEG), or - with `jpeg` a JpegInfo or colour an array that is not bytes-like input of a
+        recording - already decoded buffers: host numpy (RGB8 uint8, or int16 coefficients with `jpeg`) or torch device tensors (depth_u16 then as a device tensor too)."""
+        got = C.c_int()
+        if isinstance(depth_u16, np.ndarray):
+            d = np.ascontiguousarray(depth_u16, np.uint16)
+            if isinstance(colour, (bytes, bytearray, memoryview)):
+                buf = np.frombuffer(colour, np.uint8)
+                check(lib.bf_image_manager_process_raw(self._h, d.ctypes.data_as(C.c_void_p), C.c_float(depth_shift), buf.ctypes.data_as(C.c_void_p), C.c_uint64(buf.size),
+                                                       int(compression), C.byref(got)))
+            else:
+                ptr, _keep = _raw_colour(colour, jpeg)
+                check(lib.bf_image_manager_process_raw_decoded(self._h, d.ctypes.data_as(C.c_void_p), C.c_float(depth_shift), ptr, C.byref(jpeg) if jpeg is not None else None,
+                                                               C.byref(got)))
+        else:
+            ptr, _keep = _raw_colour(colour, jpeg)
+            check(lib.bf_image_manager_process_raw_device(self._h, _p(depth_u16), C.c_float(depth_shift), ptr, C.byref(jpeg) if jpeg is not None else None, C.byref(got)))
         return bool(got.value)
 
     def get_input_gpu(self):
@@ -1162,6 +1226,25 @@ class Pipeline:
             check(lib.bf_pipeline_process_frame(self._h, depth.ctypes.data_as(C.c_void_p), color.ctypes.data_as(C.c_void_p), C.byref(got)))
         else:
             check(lib.bf_pipeline_process_frame_device(self._h, C.c_void_p(depth.data_ptr()), C.c_void_p(color.data_ptr()), C.byref(got)))
+        return bool(got.value)
+
+    def process_frame_raw(self, depth_u16, depth_shift, colour, compression=0, jpeg=None):
+        """One iteration of the frame loop with a frame in sensor format (bf_pipeline_process_frame_raw*): arguments as ImageManager.process_raw."""
+        got = C.c_int()
+        if isinstance(depth_u16, np.ndarray):
+            d = np.ascontiguousarray(depth_u16, np.uint16)
+            if isinstance(colour, (bytes, bytearray, memoryview)):
+                buf = np.frombuffer(colour, np.uint8)
+                check(lib.bf_pipeline_process_frame_raw(self._h, d.ctypes.data_as(C.c_void_p), C.c_float(depth_shift), buf.ctypes.data_as(C.c_void_p), C.c_uint64(buf.size),
+                                                        int(compression), C.byref(got)))
+            else:
+                ptr, _keep = _raw_colour(colour, jpeg)
+                check(lib.bf_pipeline_process_frame_raw_decoded(self._h, d.ctypes.data_as(C.c_void_p), C.c_float(depth_shift), ptr, C.byref(jpeg) if jpeg is not None else None,
+                                                                C.byref(got)))
+        else:
+            ptr, _keep = _raw_colour(colour, jpeg)
+            check(lib.bf_pipeline_process_frame_raw_device(self._h, C.c_void_p(depth_u16.data_ptr()), C.c_float(depth_shift), ptr, C.byref(jpeg) if jpeg is not None else None,
+                                                           C.byref(got)))
         return bool(got.value)
 
     def process_end_of_sequence(self):

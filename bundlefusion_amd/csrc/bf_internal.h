@@ -55,4 +55,6 @@ void set_error(const char* fmt, ...);
 
 inline unsigned div_up(unsigned a, unsigned b) { return (a + b - 1) / b; }
 
+bool jpeg_on_device(const bf_jpeg_info& info);      // the sampling layouts bf_jpeg_reconstruct_device takes (sensoringest.hip)
+
 }  // namespace bf

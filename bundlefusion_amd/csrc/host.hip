@@ -24,6 +24,7 @@
 
 #include "../../include/bf_pipeline.h"
 #include "../../include/bf_comm.h"
+#include "../../include/bf_sensordata.h"
 #include "bf_device.h"
 #include "bf_internal.h"
 #include "bf_se3.h"
@@ -190,6 +191,17 @@ struct bf_image_manager {
     int activeDepth = -1, activeColor = -1;
     uint32_t currFrame = 0;
     size_t nInt() const { return (size_t)wInt * hInt; }
+    // sensor-format ingest (bf_image_manager_process_raw*), allocated at its first use.  Device side: the uploaded u16 / RGB8 / coefficient bytes, the decoder's sample
+    // planes and the converted frame - one set: every user is on `stream`, in order.  Host side: NSETS pinned staging slots (frame n copies into slot n % NSETS; the
+    // slot's event is recorded behind its uploads and waited for before the slot is written again).
+    struct RawIngest {
+        uint16_t* d_depthU16 = nullptr; uint8_t* d_colourIn = nullptr; uint8_t* d_planes = nullptr; float* d_depth = nullptr; uint8_t* d_rgbx = nullptr;
+        size_t colourInBytes = 0, planeBytes = 0;
+        uint16_t* h_depth[NSETS] = {}; uint8_t* h_colour[NSETS] = {}; size_t h_colourBytes[NSETS] = {}; hipEvent_t uploaded[NSETS] = {};
+        hipEvent_t evDecoded = nullptr;
+        uint32_t next = 0;
+        bool ready = false;
+    } rawIn;
 };
 
 extern "C" {
@@ -242,6 +254,12 @@ int bf_image_manager_destroy(bf_image_manager* im) {
     bf_image_manager_reset(im);
     for (uint32_t k = 0; k < (im->scratch ? 1u : bf_image_manager::NSETS); ++k) { (void)hipFree(im->rawSet[k]); (void)hipFree(im->filtSet[k]); (void)hipFree(im->colSet[k]); }
     (void)hipFree(im->d_stageDepth); (void)hipFree(im->d_stageColor);
+    {
+        bf_image_manager::RawIngest& r = im->rawIn;
+        (void)hipFree(r.d_depthU16); (void)hipFree(r.d_colourIn); (void)hipFree(r.d_planes); (void)hipFree(r.d_depth); (void)hipFree(r.d_rgbx);
+        for (uint32_t k = 0; k < bf_image_manager::NSETS; ++k) { (void)hipHostFree(r.h_depth[k]); (void)hipHostFree(r.h_colour[k]); if (r.uploaded[k]) (void)hipEventDestroy(r.uploaded[k]); }
+        if (r.evDecoded) (void)hipEventDestroy(r.evDecoded);
+    }
     delete im;
     return BF_OK;
 }
@@ -347,6 +365,122 @@ int bf_image_manager_process(bf_image_manager* im, const float* h_depth, const u
 }
 int bf_image_manager_process_device(bf_image_manager* im, const float* d_depth, const uint8_t* d_color, int* gotFrame) {
     return im_process(im, d_depth, d_color, hipMemcpyDeviceToDevice, gotFrame);
+}
+
+// ------------------------------------------------------------------------------------------------ sensor-format ingest
+namespace {
+enum RawWhere { RAW_HOST_STORED, RAW_HOST_DECODED, RAW_DEVICE };
+
+int rawEnsure(bf_image_manager* im, size_t colourInBytes, size_t planeBytes) {
+    bf_image_manager::RawIngest& r = im->rawIn;
+    const size_t nd = (size_t)im->sensor.depthWidth * im->sensor.depthHeight, nc = (size_t)im->sensor.colorWidth * im->sensor.colorHeight;
+    if (!r.ready) {
+        BF_HIP_TRY(BF_MALLOC((void**)&r.d_depthU16, nd * 2));
+        BF_HIP_TRY(BF_MALLOC((void**)&r.d_depth, nd * 4));
+        BF_HIP_TRY(BF_MALLOC((void**)&r.d_rgbx, nc * 4));
+        for (uint32_t k = 0; k < bf_image_manager::NSETS; ++k) {
+            BF_HIP_TRY(hipHostMalloc((void**)&r.h_depth[k], nd * 2));
+            BF_HIP_TRY(hipEventCreateWithFlags(&r.uploaded[k], hipEventDisableTiming));
+        }
+        BF_HIP_TRY(hipEventCreateWithFlags(&r.evDecoded, hipEventDisableTiming));
+        r.ready = true;
+    }
+    if (colourInBytes > r.colourInBytes || planeBytes > r.planeBytes) {          // a larger frame than any before it: the kernels of the frames before must be done with the buffers
+        BF_HIP_TRY(hipStreamSynchronize(im->stream));
+        if (colourInBytes > r.colourInBytes) { (void)hipFree(r.d_colourIn); r.d_colourIn = nullptr; r.colourInBytes = 0; BF_HIP_TRY(BF_MALLOC((void**)&r.d_colourIn, colourInBytes)); r.colourInBytes = colourInBytes; }
+        if (planeBytes > r.planeBytes) { (void)hipFree(r.d_planes); r.d_planes = nullptr; r.planeBytes = 0; BF_HIP_TRY(BF_MALLOC((void**)&r.d_planes, planeBytes)); r.planeBytes = planeBytes; }
+    }
+    return BF_OK;
+}
+
+// the staging slot of the next frame, free to write, its colour part at least `bytes` large
+int rawSlot(bf_image_manager* im, size_t bytes, uint32_t* slot) {
+    bf_image_manager::RawIngest& r = im->rawIn;
+    const uint32_t k = r.next % bf_image_manager::NSETS;
+    BF_HIP_TRY(hipEventSynchronize(r.uploaded[k]));
+    if (bytes > r.h_colourBytes[k]) {
+        (void)hipHostFree(r.h_colour[k]); r.h_colour[k] = nullptr; r.h_colourBytes[k] = 0;
+        BF_HIP_TRY(hipHostMalloc((void**)&r.h_colour[k], bytes));
+        r.h_colourBytes[k] = bytes;
+    }
+    *slot = k;
+    return BF_OK;
+}
+
+// colour: RAW_HOST_STORED - the stored bytes (compression says what they are); otherwise RGB8 (jpeg == null) or quantised coefficients (*jpeg)
+// waitUpload (RAW_HOST_DECODED): return only when the caller's buffers have been read; the frame loop passes false and waits once, at the end of its call
+int im_process_raw(bf_image_manager* im, const uint16_t* depth, float depthShift, const void* colour, uint64_t colourBytes, int32_t compression, const bf_jpeg_info* jpeg,
+                   RawWhere where, bool waitUpload, int* gotFrame) {
+    BF_REQUIRE(im && gotFrame, "null argument");
+    *gotFrame = 0;
+    if (!depth || !colour) return BF_OK;
+    if (!im->scratch && im->currFrame + 1 > im->gbs.s_maxNumImages * im->gbs.s_submapSize) return BF_OK;
+    BF_REQUIRE(depthShift > 0.0f && std::isfinite(depthShift), "depthShift must be positive");
+    const bf_rgbd_sensor_desc& sn = im->sensor;
+    const size_t nd = (size_t)sn.depthWidth * sn.depthHeight, nc = (size_t)sn.colorWidth * sn.colorHeight;
+    bf_image_manager::RawIngest& r = im->rawIn;
+    hipStream_t st = im->stream;
+    bf_jpeg_info parsed;
+    const void* srcColour = colour; const uint16_t* srcDepth = depth;
+    size_t upBytes = nc * 3;
+    if (where == RAW_HOST_STORED) {
+        BF_REQUIRE(compression == BF_SENS_COLOR_RAW || compression == BF_SENS_COLOR_PNG || compression == BF_SENS_COLOR_JPEG, "colour compression type is not supported");
+        jpeg = nullptr;
+        bool hostDecode = compression == BF_SENS_COLOR_PNG;
+        if (compression == BF_SENS_COLOR_RAW) BF_REQUIRE(colourBytes == nc * 3, "raw colour has the wrong size");
+        if (compression == BF_SENS_COLOR_JPEG) {
+            BF_TRY(bf_jpeg_parse((const uint8_t*)colour, colourBytes, sn.colorWidth, sn.colorHeight, &parsed));
+            if (jpeg_on_device(parsed)) { jpeg = &parsed; upBytes = (size_t)parsed.numBlocks * 128; } else hostDecode = true;
+        }
+        BF_TRY(rawEnsure(im, std::max(upBytes, nc * 3), jpeg ? parsed.planeBytes : 0));
+        uint32_t k = 0;
+        BF_TRY(rawSlot(im, std::max(upBytes, nc * 3), &k));
+        if (jpeg) {
+            const int rc = bf_jpeg_entropy_decode((const uint8_t*)colour, colourBytes, jpeg, (int16_t*)r.h_colour[k], (uint64_t)parsed.numBlocks * 64);
+            if (rc == BF_ERR_NOT_ON_DEVICE) { jpeg = nullptr; hostDecode = true; upBytes = nc * 3; }
+            else if (rc) return rc;
+        }
+        if (hostDecode) BF_TRY(bf_decode_color_rgb((const uint8_t*)colour, colourBytes, compression, sn.colorWidth, sn.colorHeight, r.h_colour[k]));
+        else if (!jpeg) memcpy(r.h_colour[k], colour, nc * 3);
+        memcpy(r.h_depth[k], depth, nd * 2);
+        srcColour = r.h_colour[k]; srcDepth = r.h_depth[k];
+        r.next++;
+        BF_HIP_TRY(hipMemcpyAsync(r.d_depthU16, srcDepth, nd * 2, hipMemcpyHostToDevice, st));
+        BF_HIP_TRY(hipMemcpyAsync(r.d_colourIn, srcColour, upBytes, hipMemcpyHostToDevice, st));
+        BF_HIP_TRY(hipEventRecord(r.uploaded[k], st));
+    } else {
+        if (jpeg) {
+            BF_REQUIRE(jpeg->width == sn.colorWidth && jpeg->height == sn.colorHeight, "the JPEG description has another size than the sensor's colour image");
+            if (!jpeg_on_device(*jpeg)) { set_error("jpeg: this sampling layout is reconstructed on the host only"); return BF_ERR_NOT_ON_DEVICE; }
+            upBytes = (size_t)jpeg->numBlocks * 128;
+        }
+        BF_TRY(rawEnsure(im, where == RAW_HOST_DECODED ? upBytes : 0, jpeg ? jpeg->planeBytes : 0));
+        if (where == RAW_HOST_DECODED) {
+            BF_HIP_TRY(hipMemcpyAsync(r.d_depthU16, depth, nd * 2, hipMemcpyHostToDevice, st));
+            BF_HIP_TRY(hipMemcpyAsync(r.d_colourIn, colour, upBytes, hipMemcpyHostToDevice, st));
+            BF_HIP_TRY(hipEventRecord(r.evDecoded, st));
+        }
+    }
+    const uint16_t* d_u16 = where == RAW_DEVICE ? depth : r.d_depthU16;
+    const uint8_t* d_col = where == RAW_DEVICE ? (const uint8_t*)colour : r.d_colourIn;
+    BF_TRY(bf_image_convert_depth_u16(r.d_depth, d_u16, depthShift, (uint32_t)nd, st));
+    if (jpeg) BF_TRY(bf_jpeg_reconstruct_device(jpeg, (const int16_t*)d_col, r.d_planes, r.d_rgbx, st));
+    else BF_TRY(bf_image_convert_rgb8_to_rgbx(r.d_rgbx, d_col, (uint32_t)nc, st));
+    BF_TRY(bf_image_manager_process_device(im, r.d_depth, r.d_rgbx, gotFrame));
+    if (where == RAW_HOST_DECODED && waitUpload) BF_HIP_TRY(hipEventSynchronize(r.evDecoded));      // the caller's buffers are free on return
+    return BF_OK;
+}
+}  // namespace
+
+int bf_image_manager_process_raw(bf_image_manager* im, const uint16_t* h_depthU16, float depthShift, const uint8_t* h_colour, uint64_t colourBytes, int32_t colourCompression,
+                                 int* gotFrame) {
+    return im_process_raw(im, h_depthU16, depthShift, h_colour, colourBytes, colourCompression, nullptr, RAW_HOST_STORED, true, gotFrame);
+}
+int bf_image_manager_process_raw_decoded(bf_image_manager* im, const uint16_t* h_depthU16, float depthShift, const void* h_colour, const bf_jpeg_info* jpeg, int* gotFrame) {
+    return im_process_raw(im, h_depthU16, depthShift, h_colour, 0, 0, jpeg, RAW_HOST_DECODED, true, gotFrame);
+}
+int bf_image_manager_process_raw_device(bf_image_manager* im, const uint16_t* d_depthU16, float depthShift, const void* d_colour, const bf_jpeg_info* jpeg, int* gotFrame) {
+    return im_process_raw(im, d_depthU16, depthShift, d_colour, 0, 0, jpeg, RAW_DEVICE, true, gotFrame);
 }
 
 int bf_image_manager_copy_to_bundling(bf_image_manager* im, float* d_depthRaw, float* d_depthFilt, uint8_t* d_color) {
@@ -2196,7 +2330,10 @@ int plFlush(bf_pipeline* p) {
     return bf_online_bundler_wait_solves(p->ob);          // a lagged solve has finished (it is APPLIED at its frame, not here)
 }
 
-int plFrame(bf_pipeline* p, const float* depth, const uint8_t* color, bool device, bool haveInput, int* gotFrame) {
+// a frame in sensor format for plFrame (bf_pipeline_process_frame_raw*): the arguments of im_process_raw
+struct PlRawFrame { const uint16_t* depth; float depthShift; const void* colour; uint64_t colourBytes; int32_t compression; const bf_jpeg_info* jpeg; int where; };
+
+int plFrame(bf_pipeline* p, const float* depth, const uint8_t* color, bool device, bool haveInput, int* gotFrame, const PlRawFrame* raw = nullptr) {
     hipStream_t sa = p->sBundle, sd = p->sIngest;
     const bool tm = p->timings;
     const bool ahead = p->lookahead && !tm && haveInput;
@@ -2213,7 +2350,8 @@ int plFrame(bf_pipeline* p, const float* depth, const uint8_t* color, bool devic
     const double tIn = plNow();
     if (tm) (void)hipEventRecord(p->ev[0], sd);
     int got = 0;
-    if (haveInput) BF_TRY(device ? bf_image_manager_process_device(p->im, depth, color, &got) : bf_image_manager_process(p->im, depth, color, &got));
+    if (haveInput && raw) BF_TRY(im_process_raw(p->im, raw->depth, raw->depthShift, raw->colour, raw->colourBytes, raw->compression, raw->jpeg, (RawWhere)raw->where, false, &got));   // (this call ends with the wait for evIngest)
+    else if (haveInput) BF_TRY(device ? bf_image_manager_process_device(p->im, depth, color, &got) : bf_image_manager_process(p->im, depth, color, &got));
     const uint32_t frame = p->im->currFrame > 0 ? p->im->currFrame - 1 : 0;
     if (got) BF_HIP_TRY(hipEventRecord(p->evIngest[frame % bf_pipeline::NEV], sd));
     if (got && !ahead) BF_HIP_TRY(hipStreamWaitEvent(sa, p->evIngest[frame % bf_pipeline::NEV], 0));      // the frame is detected on the bundling stream, from the ingest buffers
@@ -2437,6 +2575,21 @@ int bf_pipeline_process_frame(bf_pipeline* p, const float* h_depth, const uint8_
 int bf_pipeline_process_frame_device(bf_pipeline* p, const float* d_depth, const uint8_t* d_color, int* gotFrame) {
     BF_REQUIRE(p, "null pipeline");
     return plFrame(p, d_depth, d_color, true, true, gotFrame);
+}
+int bf_pipeline_process_frame_raw(bf_pipeline* p, const uint16_t* h_depthU16, float depthShift, const uint8_t* h_colour, uint64_t colourBytes, int32_t colourCompression, int* gotFrame) {
+    BF_REQUIRE(p, "null pipeline");
+    const PlRawFrame raw = {h_depthU16, depthShift, h_colour, colourBytes, colourCompression, nullptr, RAW_HOST_STORED};
+    return plFrame(p, nullptr, nullptr, true, true, gotFrame, &raw);
+}
+int bf_pipeline_process_frame_raw_decoded(bf_pipeline* p, const uint16_t* h_depthU16, float depthShift, const void* h_colour, const bf_jpeg_info* jpeg, int* gotFrame) {
+    BF_REQUIRE(p, "null pipeline");
+    const PlRawFrame raw = {h_depthU16, depthShift, h_colour, 0, 0, jpeg, RAW_HOST_DECODED};
+    return plFrame(p, nullptr, nullptr, true, true, gotFrame, &raw);
+}
+int bf_pipeline_process_frame_raw_device(bf_pipeline* p, const uint16_t* d_depthU16, float depthShift, const void* d_colour, const bf_jpeg_info* jpeg, int* gotFrame) {
+    BF_REQUIRE(p, "null pipeline");
+    const PlRawFrame raw = {d_depthU16, depthShift, d_colour, 0, 0, jpeg, RAW_DEVICE};
+    return plFrame(p, nullptr, nullptr, true, true, gotFrame, &raw);
 }
 int bf_pipeline_process_end_of_sequence(bf_pipeline* p, uint32_t* numActiveOperations) {
     BF_REQUIRE(p, "null pipeline");

@@ -20,6 +20,7 @@
 
 #include "../../include/bf_sensordata.h"
 #include "bf_internal.h"
+#include "bf_jpeg_recon.h"
 
 using namespace bf;
 
@@ -42,8 +43,6 @@ struct Huff {
         maxcode[17] = 0x7FFFFFFF;
     }
 };
-
-struct Comp { int id, h, v, tq, td, ta, pred; int bw, bh; std::vector<uint8_t> plane; int pw, ph; };   // plane: padded to whole MCUs
 
 struct BitReader {
     const uint8_t* p; const uint8_t* end;
@@ -81,66 +80,26 @@ int extend(int v, int n) { return v < (1 << (n - 1)) ? v - (1 << n) + 1 : v; }
 const int ZIGZAG[64] = {0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
                         35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
-inline uint8_t clamp8(int v) { return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
-inline int descale(int64_t x, int n) { return (int)((x + ((int64_t)1 << (n - 1))) >> n); }
+using bfjpeg::clamp8;
 
-// IJG jidctint ("islow"): two passes of the LL&M 8-point IDCT, CONST_BITS = 13, PASS1_BITS = 2; input already dequantised
+// IJG jidctint ("islow"): two passes of the LL&M 8-point IDCT (bf_jpeg_recon.h); input already dequantised
 void idctIslow(const int* in, uint8_t* out, int stride) {
-    const int CB = 13, P1 = 2;
-    const int64_t F0298 = 2446, F0390 = 3196, F0541 = 4433, F0765 = 6270, F0899 = 7373, F1175 = 9633, F1501 = 12299, F1847 = 15137, F1961 = 16069,
-                  F2053 = 16819, F2562 = 20995, F3072 = 25172;
     int ws[64];
     for (int c = 0; c < 8; ++c) {
         const int* ip = in + c;
-        if (ip[8] == 0 && ip[16] == 0 && ip[24] == 0 && ip[32] == 0 && ip[40] == 0 && ip[48] == 0 && ip[56] == 0) {
-            const int dc = ip[0] * (1 << P1);
+        if (ip[8] == 0 && ip[16] == 0 && ip[24] == 0 && ip[32] == 0 && ip[40] == 0 && ip[48] == 0 && ip[56] == 0) {      // == the butterfly: descale(dc << 13, 11) == dc << 2
+            const int dc = ip[0] * (1 << bfjpeg::PASS1_BITS);
             for (int r = 0; r < 8; ++r) ws[r * 8 + c] = dc;
             continue;
         }
-        int64_t z2 = ip[16], z3 = ip[48];
-        int64_t z1 = (z2 + z3) * F0541;
-        int64_t tmp2 = z1 + z3 * (-F1847), tmp3 = z1 + z2 * F0765;
-        z2 = ip[0]; z3 = ip[32];
-        int64_t tmp0 = (z2 + z3) * (1 << CB), tmp1 = (z2 - z3) * (1 << CB);
-        const int64_t tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
-        tmp0 = ip[56]; tmp1 = ip[40]; tmp2 = ip[24]; tmp3 = ip[8];
-        z1 = tmp0 + tmp3; z2 = tmp1 + tmp2; z3 = tmp0 + tmp2;
-        int64_t z4 = tmp1 + tmp3;
-        const int64_t z5 = (z3 + z4) * F1175;
-        tmp0 *= F0298; tmp1 *= F2053; tmp2 *= F3072; tmp3 *= F1501;
-        z1 *= -F0899; z2 *= -F2562; z3 *= -F1961; z4 *= -F0390;
-        z3 += z5; z4 += z5;
-        tmp0 += z1 + z3; tmp1 += z2 + z4; tmp2 += z2 + z3; tmp3 += z1 + z4;
-        ws[0 * 8 + c] = descale(tmp10 + tmp3, CB - P1); ws[7 * 8 + c] = descale(tmp10 - tmp3, CB - P1);
-        ws[1 * 8 + c] = descale(tmp11 + tmp2, CB - P1); ws[6 * 8 + c] = descale(tmp11 - tmp2, CB - P1);
-        ws[2 * 8 + c] = descale(tmp12 + tmp1, CB - P1); ws[5 * 8 + c] = descale(tmp12 - tmp1, CB - P1);
-        ws[3 * 8 + c] = descale(tmp13 + tmp0, CB - P1); ws[4 * 8 + c] = descale(tmp13 - tmp0, CB - P1);
+        const int64_t x[8] = {ip[0], ip[8], ip[16], ip[24], ip[32], ip[40], ip[48], ip[56]};
+        bfjpeg::idctColumn(x, ws + c, 8);
     }
-    for (int r = 0; r < 8; ++r) {
-        const int* w = ws + r * 8;
-        uint8_t* o = out + (size_t)r * stride;
-        int64_t z2 = w[2], z3 = w[6];
-        int64_t z1 = (z2 + z3) * F0541;
-        int64_t tmp2 = z1 + z3 * (-F1847), tmp3 = z1 + z2 * F0765;
-        int64_t tmp0 = ((int64_t)w[0] + w[4]) * (1 << CB), tmp1 = ((int64_t)w[0] - w[4]) * (1 << CB);
-        const int64_t tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
-        tmp0 = w[7]; tmp1 = w[5]; tmp2 = w[3]; tmp3 = w[1];
-        z1 = tmp0 + tmp3; z2 = tmp1 + tmp2; z3 = tmp0 + tmp2;
-        int64_t z4 = tmp1 + tmp3;
-        const int64_t z5 = (z3 + z4) * F1175;
-        tmp0 *= F0298; tmp1 *= F2053; tmp2 *= F3072; tmp3 *= F1501;
-        z1 *= -F0899; z2 *= -F2562; z3 *= -F1961; z4 *= -F0390;
-        z3 += z5; z4 += z5;
-        tmp0 += z1 + z3; tmp1 += z2 + z4; tmp2 += z2 + z3; tmp3 += z1 + z4;
-        const int S = CB + P1 + 3;
-        o[0] = clamp8(descale(tmp10 + tmp3, S) + 128); o[7] = clamp8(descale(tmp10 - tmp3, S) + 128);
-        o[1] = clamp8(descale(tmp11 + tmp2, S) + 128); o[6] = clamp8(descale(tmp11 - tmp2, S) + 128);
-        o[2] = clamp8(descale(tmp12 + tmp1, S) + 128); o[5] = clamp8(descale(tmp12 - tmp1, S) + 128);
-        o[3] = clamp8(descale(tmp13 + tmp0, S) + 128); o[4] = clamp8(descale(tmp13 - tmp0, S) + 128);
-    }
+    for (int r = 0; r < 8; ++r) bfjpeg::idctRow(ws + r * 8, out + (size_t)r * stride);
 }
 
 // IJG "fancy" (triangle) up-sampling of one chroma plane to full resolution.  sw x sh: the down-sampled size that covers the image.
+// (Row forms of bfjpeg::chromaAt, which the device uses per pixel.)
 void upsampleH2(const uint8_t* in, int sw, uint8_t* out) {             // one row, 2:1 horizontally (h2v1_fancy_upsample)
     if (sw == 1) { out[0] = out[1] = in[0]; return; }
     out[0] = in[0];
@@ -167,12 +126,20 @@ void upsampleH2V2Row(const uint8_t* near, const uint8_t* far, int sw, uint8_t* o
     out[2 * (sw - 1) + 1] = (uint8_t)((col[sw - 1] * 4 + 7) >> 4);
 }
 
-int decodeJpeg(const uint8_t* data, size_t size, uint32_t width, uint32_t height, uint8_t* rgb) {
-    if (size < 4 || data[0] != 0xFF || data[1] != 0xD8) { set_error("jpeg: no SOI marker"); return BF_ERR_INVALID_ARG; }
-    uint16_t qt[4][64]; bool qtPresent[4] = {false, false, false, false};
+// ---- (a) header parse: everything up to the first scan.  info: the POD description of bf_hip.h; the rest is what the entropy decode needs.
+struct Parsed {
+    bf_jpeg_info info;
     Huff dc[4], ac[4];
-    std::vector<Comp> comps;
-    int W = 0, H = 0, hmax = 1, vmax = 1, restart = 0;
+    int td[3], ta[3];
+    size_t scanStart;              // first byte of the entropy-coded data
+};
+
+int parseJpeg(const uint8_t* data, size_t size, uint32_t width, uint32_t height, Parsed& P) {      // width / height: the expected size (0 x 0: any)
+    if (size < 4 || data[0] != 0xFF || data[1] != 0xD8) { set_error("jpeg: no SOI marker"); return BF_ERR_INVALID_ARG; }
+    bf_jpeg_info& I = P.info;
+    memset(&I, 0, sizeof I);
+    int id[3] = {0, 0, 0};
+    int W = 0, H = 0, hmax = 1, vmax = 1, restart = 0, nc = 0;
     size_t pos = 2;
     bool sawSOF = false;
     auto u16 = [&](size_t p) { return (int)data[p] << 8 | data[p + 1]; };
@@ -192,15 +159,15 @@ int decodeJpeg(const uint8_t* data, size_t size, uint32_t width, uint32_t height
             while (p < segEnd) {
                 const int pq = data[p] >> 4, tq = data[p] & 15; ++p;
                 if (tq > 3 || p + (pq ? 128 : 64) > segEnd) { set_error("jpeg: bad DQT"); return BF_ERR_INVALID_ARG; }
-                for (int i = 0; i < 64; ++i) { qt[tq][ZIGZAG[i]] = (uint16_t)(pq ? u16(p) : data[p]); p += pq ? 2 : 1; }
-                qtPresent[tq] = true;
+                for (int i = 0; i < 64; ++i) { I.qt[tq][ZIGZAG[i]] = (uint16_t)(pq ? u16(p) : data[p]); p += pq ? 2 : 1; }
+                I.qtPresent[tq] = 1;
             }
         } else if (m == 0xC4) {                                                 // DHT
             size_t p = seg;
             while (p < segEnd) {
                 const int tc = data[p] >> 4, th = data[p] & 15; ++p;
                 if (tc > 1 || th > 3 || p + 16 > segEnd) { set_error("jpeg: bad DHT"); return BF_ERR_INVALID_ARG; }
-                Huff& h = tc ? ac[th] : dc[th];
+                Huff& h = tc ? P.ac[th] : P.dc[th];
                 int n = 0;
                 h.bits[0] = 0;
                 for (int l = 1; l <= 16; ++l) { h.bits[l] = data[p++]; n += h.bits[l]; }
@@ -212,14 +179,14 @@ int decodeJpeg(const uint8_t* data, size_t size, uint32_t width, uint32_t height
             if (seg + 6 > segEnd) { set_error("jpeg: short SOF segment"); return BF_ERR_INVALID_ARG; }      // precision, height, width, #components
             if (data[seg] != 8) { set_error("jpeg: only 8-bit samples are supported"); return BF_ERR_INVALID_ARG; }
             H = u16(seg + 1); W = u16(seg + 3);
-            const int nc = data[seg + 5];
+            nc = data[seg + 5];
             if ((nc != 1 && nc != 3) || seg + 6 + 3 * nc > segEnd) { set_error("jpeg: %d components are not supported", nc); return BF_ERR_INVALID_ARG; }
-            comps.resize(nc);
+            hmax = vmax = 1;
             for (int i = 0; i < nc; ++i) {
-                Comp& c = comps[i];
-                c.id = data[seg + 6 + 3 * i]; c.h = data[seg + 7 + 3 * i] >> 4; c.v = data[seg + 7 + 3 * i] & 15; c.tq = data[seg + 8 + 3 * i];
-                if (c.h < 1 || c.h > 2 || c.v < 1 || c.v > 2 || c.tq > 3) { set_error("jpeg: sampling factor %dx%d is not supported", c.h, c.v); return BF_ERR_INVALID_ARG; }
-                hmax = std::max(hmax, c.h); vmax = std::max(vmax, c.v);
+                bf_jpeg_component& c = I.comp[i];
+                id[i] = data[seg + 6 + 3 * i]; c.h = data[seg + 7 + 3 * i] >> 4; c.v = data[seg + 7 + 3 * i] & 15; c.tq = data[seg + 8 + 3 * i];
+                if (c.h < 1 || c.h > 2 || c.v < 1 || c.v > 2 || c.tq > 3) { set_error("jpeg: sampling factor %dx%d is not supported", (int)c.h, (int)c.v); return BF_ERR_INVALID_ARG; }
+                hmax = std::max(hmax, (int)c.h); vmax = std::max(vmax, (int)c.v);
             }
             sawSOF = true;
         } else if (m == 0xC2 || (m >= 0xC3 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC)) {
@@ -230,105 +197,162 @@ int decodeJpeg(const uint8_t* data, size_t size, uint32_t width, uint32_t height
             restart = u16(seg);
         } else if (m == 0xDA) {                                                 // SOS: the (single) scan follows
             if (!sawSOF) { set_error("jpeg: SOS before SOF"); return BF_ERR_INVALID_ARG; }
-            if ((uint32_t)W != width || (uint32_t)H != height) { set_error("jpeg: image is %dx%d, expected %ux%u", W, H, width, height); return BF_ERR_INVALID_ARG; }
+            if ((width || height) && ((uint32_t)W != width || (uint32_t)H != height)) { set_error("jpeg: image is %dx%d, expected %ux%u", W, H, width, height); return BF_ERR_INVALID_ARG; }
+            if (W < 1 || H < 1) { set_error("jpeg: image is %dx%d", W, H); return BF_ERR_INVALID_ARG; }
             if (seg + 1 > segEnd) { set_error("jpeg: short SOS segment"); return BF_ERR_INVALID_ARG; }
             const int ns = data[seg];
-            if (ns != (int)comps.size()) { set_error("jpeg: non-interleaved scans are not supported"); return BF_ERR_INVALID_ARG; }
+            if (ns != nc) { set_error("jpeg: non-interleaved scans are not supported"); return BF_ERR_INVALID_ARG; }
             if (seg + 1 + 2 * (size_t)ns + 3 > segEnd) { set_error("jpeg: short SOS segment"); return BF_ERR_INVALID_ARG; }      // component selectors + Ss, Se, Ah/Al
+            for (int i = 0; i < nc; ++i) P.td[i] = P.ta[i] = 0;
             for (int i = 0; i < ns; ++i) {
                 const int cid = data[seg + 1 + 2 * i], t = data[seg + 2 + 2 * i];
                 bool found = false;
-                for (Comp& c : comps) if (c.id == cid) { c.td = t >> 4; c.ta = t & 15; found = true; }
+                for (int k = 0; k < nc; ++k) if (id[k] == cid) { P.td[k] = t >> 4; P.ta[k] = t & 15; found = true; }
                 if (!found) { set_error("jpeg: scan names an unknown component"); return BF_ERR_INVALID_ARG; }
             }
             const int mcuW = 8 * hmax, mcuH = 8 * vmax, mcusX = (W + mcuW - 1) / mcuW, mcusY = (H + mcuH - 1) / mcuH;
-            for (Comp& c : comps) {
-                if (c.td > 3 || c.ta > 3 || !dc[c.td].present || !ac[c.ta].present || !qtPresent[c.tq]) { set_error("jpeg: missing Huffman or quantisation table"); return BF_ERR_INVALID_ARG; }
-                c.pw = mcusX * c.h * 8; c.ph = mcusY * c.v * 8;
-                c.plane.assign((size_t)c.pw * c.ph, 0);
-                c.pred = 0;
+            I.width = (uint32_t)W; I.height = (uint32_t)H; I.numComponents = (uint32_t)nc; I.hmax = (uint32_t)hmax; I.vmax = (uint32_t)vmax;
+            I.mcusX = (uint32_t)mcusX; I.mcusY = (uint32_t)mcusY; I.restartInterval = (uint32_t)restart;
+            if ((uint64_t)mcusX * mcusY * hmax * vmax * nc * 64 >= ((uint64_t)1 << 31)) { set_error("jpeg: a %dx%d image is too large", W, H); return BF_ERR_INVALID_ARG; }      // offsets are 32 bits
+            for (int i = 0; i < nc; ++i) {
+                bf_jpeg_component& c = I.comp[i];
+                if (P.td[i] > 3 || P.ta[i] > 3 || !P.dc[P.td[i]].present || !P.ac[P.ta[i]].present || !I.qtPresent[c.tq]) { set_error("jpeg: missing Huffman or quantisation table"); return BF_ERR_INVALID_ARG; }
+                c.blocksX = (uint32_t)mcusX * c.h; c.blocksY = (uint32_t)mcusY * c.v;
+                c.blockOffset = I.numBlocks; c.planeOffset = I.planeBytes;
+                I.numBlocks += c.blocksX * c.blocksY; I.planeBytes += c.blocksX * c.blocksY * 64;
             }
-            BitReader br; br.p = data + segEnd; br.end = data + size;
-            int untilRestart = restart;
-            int coef[64];
-            for (int my = 0; my < mcusY; ++my)
-                for (int mx = 0; mx < mcusX; ++mx) {
-                    if (restart && untilRestart == 0) {                          // RSTn: byte-align, skip the marker, reset predictors
-                        br.reset();
-                        while (br.p + 1 < br.end && !(br.p[0] == 0xFF && br.p[1] >= 0xD0 && br.p[1] <= 0xD7)) ++br.p;
-                        if (br.p + 1 < br.end) br.p += 2;
-                        for (Comp& c : comps) c.pred = 0;
-                        untilRestart = restart;
-                    }
-                    for (Comp& c : comps)
-                        for (int by = 0; by < c.v; ++by)
-                            for (int bx = 0; bx < c.h; ++bx) {
-                                memset(coef, 0, sizeof coef);
-                                const int t = decodeSymbol(br, dc[c.td]);
-                                if (t < 0 || t > 11) { set_error("jpeg: corrupt DC code"); return BF_ERR_INVALID_ARG; }
-                                const int diff = t ? extend(br.bits(t), t) : 0;
-                                c.pred += diff;
-                                coef[0] = c.pred * qt[c.tq][0];
-                                for (int k = 1; k < 64;) {
-                                    const int rs = decodeSymbol(br, ac[c.ta]);
-                                    if (rs < 0) { set_error("jpeg: corrupt AC code"); return BF_ERR_INVALID_ARG; }
-                                    const int r = rs >> 4, s = rs & 15;
-                                    if (s == 0) { if (r == 15) { k += 16; continue; } break; }
-                                    k += r;
-                                    if (k > 63) { set_error("jpeg: corrupt AC run"); return BF_ERR_INVALID_ARG; }
-                                    coef[ZIGZAG[k]] = extend(br.bits(s), s) * qt[c.tq][ZIGZAG[k]];
-                                    ++k;
-                                }
-                                idctIslow(coef, c.plane.data() + (size_t)((my * c.v + by) * 8) * c.pw + (size_t)(mx * c.h + bx) * 8, c.pw);
-                            }
-                    if (restart) --untilRestart;
-                }
-            // ---- up-sample chroma and convert
-            if (comps.size() == 1) {
-                for (int y = 0; y < H; ++y)
-                    for (int x = 0; x < W; ++x) { const uint8_t v = comps[0].plane[(size_t)y * comps[0].pw + x]; uint8_t* o = rgb + ((size_t)y * W + x) * 3; o[0] = o[1] = o[2] = v; }
-                return BF_OK;
-            }
-            if (comps[0].h != hmax || comps[0].v != vmax) { set_error("jpeg: sub-sampled luma is not supported"); return BF_ERR_INVALID_ARG; }
-            std::vector<uint8_t> full[2];
-            for (int ci = 1; ci < 3; ++ci) {
-                Comp& c = comps[ci];
-                const int fh = hmax / c.h, fv = vmax / c.v;
-                const int sw = (W * c.h + hmax - 1) / hmax, sh = (H * c.v + vmax - 1) / vmax;       // down-sampled size covering the image
-                std::vector<uint8_t>& f = full[ci - 1];
-                f.assign((size_t)(sw * fh + 2) * (sh * fv + 2), 0);
-                const int fw = sw * fh;
-                for (int y = 0; y < sh; ++y) {
-                    const uint8_t* row = c.plane.data() + (size_t)y * c.pw;
-                    if (fh == 1 && fv == 1) memcpy(f.data() + (size_t)y * fw, row, sw);
-                    else if (fh == 2 && fv == 1) upsampleH2(row, sw, f.data() + (size_t)y * fw);
-                    else if (fh == 2 && fv == 2) {
-                        const uint8_t* up = c.plane.data() + (size_t)(y > 0 ? y - 1 : 0) * c.pw;
-                        const uint8_t* dn = c.plane.data() + (size_t)(y < sh - 1 ? y + 1 : sh - 1) * c.pw;
-                        upsampleH2V2Row(row, up, sw, f.data() + (size_t)(2 * y) * fw);
-                        upsampleH2V2Row(row, dn, sw, f.data() + (size_t)(2 * y + 1) * fw);
-                    } else {                                                    // 1:2 vertically only (rare): replicate rows
-                        memcpy(f.data() + (size_t)(2 * y) * fw, row, sw);
-                        memcpy(f.data() + (size_t)(2 * y + 1) * fw, row, sw);
-                    }
-                }
-                c.bw = fw;
-            }
-            for (int y = 0; y < H; ++y)
-                for (int x = 0; x < W; ++x) {
-                    const int Y = comps[0].plane[(size_t)y * comps[0].pw + x];
-                    const int cb = full[0][(size_t)y * comps[1].bw + x] - 128, cr = full[1][(size_t)y * comps[2].bw + x] - 128;
-                    uint8_t* o = rgb + ((size_t)y * W + x) * 3;                  // jdcolor.c build_ycc_rgb_table: 16-bit fixed point
-                    o[0] = clamp8(Y + ((91881 * cr + 32768) >> 16));
-                    o[1] = clamp8(Y + ((-22554 * cb - 46802 * cr + 32768) >> 16));
-                    o[2] = clamp8(Y + ((116130 * cb + 32768) >> 16));
-                }
+            P.scanStart = segEnd;
             return BF_OK;
         }
         pos = segEnd;
     }
     set_error("jpeg: no scan found");
     return BF_ERR_INVALID_ARG;
+}
+
+// ---- (b) entropy decode of the scan: sink(component, bx, by, coef) receives every block in stream order, coef[64] in natural order -
+// quantised, or (DEQUANT) multiplied by the component's table on the way like the one-pass decoder always did
+template <bool DEQUANT, class Sink> int entropyDecode(const uint8_t* data, size_t size, const Parsed& P, Sink&& sink) {
+    const bf_jpeg_info& I = P.info;
+    const int nc = (int)I.numComponents, restart = (int)I.restartInterval;
+    int pred[3] = {0, 0, 0};
+    BitReader br; br.p = data + P.scanStart; br.end = data + size;
+    int untilRestart = restart;
+    int coef[64];
+    for (int my = 0; my < (int)I.mcusY; ++my)
+        for (int mx = 0; mx < (int)I.mcusX; ++mx) {
+            if (restart && untilRestart == 0) {                          // RSTn: byte-align, skip the marker, reset predictors
+                br.reset();
+                while (br.p + 1 < br.end && !(br.p[0] == 0xFF && br.p[1] >= 0xD0 && br.p[1] <= 0xD7)) ++br.p;
+                if (br.p + 1 < br.end) br.p += 2;
+                pred[0] = pred[1] = pred[2] = 0;
+                untilRestart = restart;
+            }
+            for (int ci = 0; ci < nc; ++ci) {
+                const bf_jpeg_component& c = I.comp[ci];
+                const uint16_t* qt = I.qt[c.tq];
+                const Huff& hdc = P.dc[P.td[ci]];
+                const Huff& hac = P.ac[P.ta[ci]];
+                for (int by = 0; by < (int)c.v; ++by)
+                    for (int bx = 0; bx < (int)c.h; ++bx) {
+                        memset(coef, 0, sizeof coef);
+                        const int t = decodeSymbol(br, hdc);
+                        if (t < 0 || t > 11) { set_error("jpeg: corrupt DC code"); return BF_ERR_INVALID_ARG; }
+                        const int diff = t ? extend(br.bits(t), t) : 0;
+                        pred[ci] += diff;
+                        coef[0] = DEQUANT ? pred[ci] * qt[0] : pred[ci];
+                        for (int k = 1; k < 64;) {
+                            const int rs = decodeSymbol(br, hac);
+                            if (rs < 0) { set_error("jpeg: corrupt AC code"); return BF_ERR_INVALID_ARG; }
+                            const int r = rs >> 4, s = rs & 15;
+                            if (s == 0) { if (r == 15) { k += 16; continue; } break; }
+                            k += r;
+                            if (k > 63) { set_error("jpeg: corrupt AC run"); return BF_ERR_INVALID_ARG; }
+                            coef[ZIGZAG[k]] = DEQUANT ? extend(br.bits(s), s) * qt[ZIGZAG[k]] : extend(br.bits(s), s);
+                            ++k;
+                        }
+                        const int rc = sink(ci, mx * (int)c.h + bx, my * (int)c.v + by, coef);
+                        if (rc) return rc;
+                    }
+            }
+            if (restart) --untilRestart;
+        }
+    return BF_OK;
+}
+
+// ---- (c) host reconstruction behind the inverse DCT: up-sample chroma and convert.  planes: the components' sample planes (bf_jpeg_component::planeOffset)
+int finishJpeg(const bf_jpeg_info& I, const uint8_t* planes, uint8_t* rgb) {
+    const int W = (int)I.width, H = (int)I.height, hmax = (int)I.hmax, vmax = (int)I.vmax;
+    const uint8_t* plane[3]; int pw[3];
+    for (int i = 0; i < (int)I.numComponents; ++i) { plane[i] = planes + I.comp[i].planeOffset; pw[i] = (int)I.comp[i].blocksX * 8; }
+    if (I.numComponents == 1) {
+        for (int y = 0; y < H; ++y)
+            for (int x = 0; x < W; ++x) { const uint8_t v = plane[0][(size_t)y * pw[0] + x]; uint8_t* o = rgb + ((size_t)y * W + x) * 3; o[0] = o[1] = o[2] = v; }
+        return BF_OK;
+    }
+    if ((int)I.comp[0].h != hmax || (int)I.comp[0].v != vmax) { set_error("jpeg: sub-sampled luma is not supported"); return BF_ERR_INVALID_ARG; }
+    std::vector<uint8_t> full[2];
+    int bw[3] = {0, 0, 0};
+    for (int ci = 1; ci < 3; ++ci) {
+        const bf_jpeg_component& c = I.comp[ci];
+        const int fh = hmax / (int)c.h, fv = vmax / (int)c.v;
+        const int sw = (W * (int)c.h + hmax - 1) / hmax, sh = (H * (int)c.v + vmax - 1) / vmax;       // down-sampled size covering the image
+        std::vector<uint8_t>& f = full[ci - 1];
+        f.assign((size_t)(sw * fh + 2) * (sh * fv + 2), 0);
+        const int fw = sw * fh;
+        for (int y = 0; y < sh; ++y) {
+            const uint8_t* row = plane[ci] + (size_t)y * pw[ci];
+            if (fh == 1 && fv == 1) memcpy(f.data() + (size_t)y * fw, row, sw);
+            else if (fh == 2 && fv == 1) upsampleH2(row, sw, f.data() + (size_t)y * fw);
+            else if (fh == 2 && fv == 2) {
+                const uint8_t* up = plane[ci] + (size_t)(y > 0 ? y - 1 : 0) * pw[ci];
+                const uint8_t* dn = plane[ci] + (size_t)(y < sh - 1 ? y + 1 : sh - 1) * pw[ci];
+                upsampleH2V2Row(row, up, sw, f.data() + (size_t)(2 * y) * fw);
+                upsampleH2V2Row(row, dn, sw, f.data() + (size_t)(2 * y + 1) * fw);
+            } else {                                                    // 1:2 vertically only (rare): replicate rows
+                memcpy(f.data() + (size_t)(2 * y) * fw, row, sw);
+                memcpy(f.data() + (size_t)(2 * y + 1) * fw, row, sw);
+            }
+        }
+        bw[ci] = fw;
+    }
+    for (int y = 0; y < H; ++y)
+        for (int x = 0; x < W; ++x)
+            bfjpeg::yccToRgb(plane[0][(size_t)y * pw[0] + x], full[0][(size_t)y * bw[1] + x], full[1][(size_t)y * bw[2] + x], rgb + ((size_t)y * W + x) * 3);
+    return BF_OK;
+}
+
+// (a) + (b) + (c) in one pass over the stream: every block goes through the inverse DCT as it leaves the entropy decoder
+int decodeJpeg(const uint8_t* data, size_t size, uint32_t width, uint32_t height, uint8_t* rgb) {
+    Parsed P;
+    int rc = parseJpeg(data, size, width, height, P);
+    if (rc) return rc;
+    const bf_jpeg_info& I = P.info;
+    std::vector<uint8_t> planes(I.planeBytes, 0);
+    rc = entropyDecode<true>(data, size, P, [&](int ci, int bx, int by, const int* coef) {
+        const bf_jpeg_component& c = I.comp[ci];
+        idctIslow(coef, planes.data() + c.planeOffset + ((size_t)by * 8 * c.blocksX + bx) * 8, (int)c.blocksX * 8);
+        return 0;
+    });
+    if (rc) return rc;
+    return finishJpeg(I, planes.data(), rgb);
+}
+
+// the same from a coefficient buffer (bf_jpeg_entropy_decode): what the device reconstruction computes, on the host
+int reconstructJpegHost(const bf_jpeg_info& I, const int16_t* coefficients, uint8_t* rgb) {
+    std::vector<uint8_t> planes(I.planeBytes, 0);
+    int coef[64];
+    for (int ci = 0; ci < (int)I.numComponents; ++ci) {
+        const bf_jpeg_component& c = I.comp[ci];
+        const uint16_t* qt = I.qt[c.tq];
+        for (uint32_t by = 0; by < c.blocksY; ++by)
+            for (uint32_t bx = 0; bx < c.blocksX; ++bx) {
+                const int16_t* q = coefficients + ((size_t)c.blockOffset + (size_t)by * c.blocksX + bx) * 64;
+                for (int k = 0; k < 64; ++k) coef[k] = (int)q[k] * (int)qt[k];
+                idctIslow(coef, planes.data() + c.planeOffset + ((size_t)by * 8 * c.blocksX + bx) * 8, (int)c.blocksX * 8);
+            }
+    }
+    return finishJpeg(I, planes.data(), rgb);
 }
 
 // ================================================================================================ PNG
@@ -569,6 +593,50 @@ int bf_decode_color_rgb(const uint8_t* data, uint64_t size, int32_t compressionT
     return BF_ERR_INVALID_ARG;
 } catch (const std::exception& e) {                   // e.g. std::bad_alloc on an absurd image size: no exception leaves the C ABI
     set_error("colour decoder: %s", e.what());
+    return BF_ERR_STATE;
+}
+
+int bf_jpeg_parse(const uint8_t* data, uint64_t size, uint32_t expectWidth, uint32_t expectHeight, bf_jpeg_info* info) try {
+    BF_REQUIRE(data && info, "null argument");
+    Parsed P;
+    const int rc = parseJpeg(data, (size_t)size, expectWidth, expectHeight, P);
+    if (rc) return rc;
+    *info = P.info;
+    return BF_OK;
+} catch (const std::exception& e) {
+    set_error("jpeg parser: %s", e.what());
+    return BF_ERR_STATE;
+}
+
+int bf_jpeg_entropy_decode(const uint8_t* data, uint64_t size, const bf_jpeg_info* info, int16_t* coefficients, uint64_t capacity) try {
+    BF_REQUIRE(data && info && coefficients, "null argument");
+    Parsed P;
+    const int rc = parseJpeg(data, (size_t)size, info->width, info->height, P);
+    if (rc) return rc;
+    BF_REQUIRE(memcmp(&P.info, info, sizeof *info) == 0, "the description does not belong to this stream");
+    BF_REQUIRE(capacity >= (uint64_t)info->numBlocks * 64, "coefficient buffer too small");
+    const bf_jpeg_info& I = P.info;
+    return entropyDecode<false>(data, (size_t)size, P, [&](int ci, int bx, int by, const int* coef) {
+        const bf_jpeg_component& c = I.comp[ci];
+        int16_t* o = coefficients + ((size_t)c.blockOffset + (size_t)by * c.blocksX + bx) * 64;
+        if (coef[0] < -32768 || coef[0] > 32767) {                   // only the DC predictor can leave int16 (AC magnitudes have at most 15 bits)
+            set_error("jpeg: a DC coefficient does not fit 16 bits; decode this stream with bf_decode_color_rgb");
+            return (int)BF_ERR_NOT_ON_DEVICE;
+        }
+        for (int k = 0; k < 64; ++k) o[k] = (int16_t)coef[k];
+        return 0;
+    });
+} catch (const std::exception& e) {
+    set_error("jpeg entropy decoder: %s", e.what());
+    return BF_ERR_STATE;
+}
+
+int bf_jpeg_reconstruct_host(const bf_jpeg_info* info, const int16_t* coefficients, uint8_t* rgbOut) try {
+    BF_REQUIRE(info && coefficients && rgbOut, "null argument");
+    BF_REQUIRE((info->numComponents == 1 || info->numComponents == 3) && info->width > 0 && info->height > 0, "bad description");
+    return reconstructJpegHost(*info, coefficients, rgbOut);
+} catch (const std::exception& e) {
+    set_error("jpeg reconstruction: %s", e.what());
     return BF_ERR_STATE;
 }
 

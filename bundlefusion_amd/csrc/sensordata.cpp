@@ -1,19 +1,23 @@
 // Recorded sequences: the ".sens" container (ml::SensorData version 4) as used by SensorDataReader.cpp:40-128.
-// Host-only.  The byte layout is documented in include/bf_sensordata.h; frames are indexed at open time and read on demand.
+// Host-only, except that the decode-ahead player at the end hands its frames to a pipeline's device ingest.
+// The byte layout is documented in include/bf_sensordata.h; frames are indexed at open time and read on demand.
 #include <zlib.h>
 
 #include <algorithm>
 #include <array>
 #include <cmath>
+#include <condition_variable>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <limits>
 #include <memory>
+#include <mutex>
 #include <new>
 #include <stdexcept>
 #include <memory>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "../../include/bf_sensordata.h"
@@ -23,6 +27,7 @@ using namespace bf;
 
 struct bf_sensor_data {
     FILE* f = nullptr;
+    std::string path;
     bf_sensor_data_info info;
     struct Frame { float T[16]; uint64_t tsColor, tsDepth, colorSize, depthSize; int64_t colorOffset, depthOffset; };
     std::vector<Frame> frames;
@@ -62,9 +67,31 @@ template <class F> int guarded(F f) {
     catch (const std::exception& e) { set_error("%s", e.what()); return BF_ERR_STATE; }
 }
 
-int readBytes(bf_sensor_data* sd, int64_t offset, uint64_t size, uint8_t* out) {
-    if (fseeko(sd->f, offset, SEEK_SET) != 0 || fread(out, 1, size, sd->f) != size) { set_error("sens: short read at offset %lld", (long long)offset); return BF_ERR_STATE; }
+int readBytes(FILE* f, int64_t offset, uint64_t size, uint8_t* out) {
+    if (fseeko(f, offset, SEEK_SET) != 0 || fread(out, 1, size, f) != size) { set_error("sens: short read at offset %lld", (long long)offset); return BF_ERR_STATE; }
     return BF_OK;
+}
+int readBytes(bf_sensor_data* sd, int64_t offset, uint64_t size, uint8_t* out) { return readBytes(sd->f, offset, size, out); }
+
+// SensorData::decompressDepthAlloc through file handle `f` (the reader's own, or a player thread's) with `scratch` for the compressed bytes
+int readDepthRaw(bf_sensor_data* sd, FILE* f, std::vector<uint8_t>& scratch, uint64_t frame, uint16_t* out) {
+    const bf_sensor_data::Frame& fr = sd->frames[frame];
+    const uint64_t bytes = (uint64_t)sd->info.depthWidth * sd->info.depthHeight * 2;
+    if (sd->info.depthCompressionType == BF_SENS_DEPTH_RAW_USHORT) {
+        if (fr.depthSize != bytes) { set_error("sens: frame %llu: raw depth has %llu bytes, expected %llu", (unsigned long long)frame, (unsigned long long)fr.depthSize, (unsigned long long)bytes); return BF_ERR_STATE; }
+        return readBytes(f, fr.depthOffset, bytes, reinterpret_cast<uint8_t*>(out));
+    }
+    if (sd->info.depthCompressionType == BF_SENS_DEPTH_ZLIB_USHORT) {
+        scratch.resize(fr.depthSize);
+        const int rc = readBytes(f, fr.depthOffset, fr.depthSize, scratch.data());
+        if (rc) return rc;
+        uLongf dstLen = (uLongf)bytes;
+        const int z = uncompress(reinterpret_cast<Bytef*>(out), &dstLen, scratch.data(), (uLong)fr.depthSize);
+        if (z != Z_OK || dstLen != bytes) { set_error("sens: frame %llu: zlib depth does not inflate to %llu bytes (zlib %d)", (unsigned long long)frame, (unsigned long long)bytes, z); return BF_ERR_STATE; }
+        return BF_OK;
+    }
+    set_error("sens: depth compression type %d is not supported (raw and zlib u16 are)", sd->info.depthCompressionType);   // "unknown depth compression type"
+    return BF_ERR_INVALID_ARG;
 }
 
 }  // namespace
@@ -80,6 +107,7 @@ int bf_sensor_data_open(const char* filename, bf_sensor_data** out) {
     std::unique_ptr<bf_sensor_data, Closer> guard(new bf_sensor_data);          // an exception below (bad_alloc) must not leak sd / its FILE*
     bf_sensor_data* sd = guard.get();
     sd->f = f;
+    sd->path = filename;
     bf_sensor_data_info& h = sd->info;
     memset(&h, 0, sizeof h);
     const int64_t total = fileSize(f);
@@ -181,23 +209,7 @@ int bf_sensor_data_get_frame_sizes(bf_sensor_data* sd, uint64_t frame, uint64_t*
 int bf_sensor_data_read_depth_raw(bf_sensor_data* sd, uint64_t frame, uint16_t* out) {             // SensorData::decompressDepthAlloc
     return guarded([&]() -> int {
     BF_REQUIRE(sd && out && frame < sd->frames.size(), "bad argument");
-    const bf_sensor_data::Frame& fr = sd->frames[frame];
-    const uint64_t bytes = (uint64_t)sd->info.depthWidth * sd->info.depthHeight * 2;
-    if (sd->info.depthCompressionType == BF_SENS_DEPTH_RAW_USHORT) {
-        if (fr.depthSize != bytes) { set_error("sens: frame %llu: raw depth has %llu bytes, expected %llu", (unsigned long long)frame, (unsigned long long)fr.depthSize, (unsigned long long)bytes); return BF_ERR_STATE; }
-        return readBytes(sd, fr.depthOffset, bytes, reinterpret_cast<uint8_t*>(out));
-    }
-    if (sd->info.depthCompressionType == BF_SENS_DEPTH_ZLIB_USHORT) {
-        sd->scratch.resize(fr.depthSize);
-        const int rc = readBytes(sd, fr.depthOffset, fr.depthSize, sd->scratch.data());
-        if (rc) return rc;
-        uLongf dstLen = (uLongf)bytes;
-        const int z = uncompress(reinterpret_cast<Bytef*>(out), &dstLen, sd->scratch.data(), (uLong)fr.depthSize);
-        if (z != Z_OK || dstLen != bytes) { set_error("sens: frame %llu: zlib depth does not inflate to %llu bytes (zlib %d)", (unsigned long long)frame, (unsigned long long)bytes, z); return BF_ERR_STATE; }
-        return BF_OK;
-    }
-    set_error("sens: depth compression type %d is not supported (raw and zlib u16 are)", sd->info.depthCompressionType);   // "unknown depth compression type"
-    return BF_ERR_INVALID_ARG;
+    return readDepthRaw(sd, sd->f, sd->scratch, frame, out);
     });
 }
 
@@ -545,6 +557,190 @@ int bf_sensor_data_evaluate_trajectory(bf_sensor_data* sd, const float* trajecto
     const uint32_t n = (uint32_t)std::min<uint64_t>(numTransforms, nRef);
     return bf_evaluate_ate_rmse(trajectory, ref.data(), n, rmse, numEvaluated);
     });
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ decode-ahead player
+// Frame k lives in slot k % numSlots.  A worker claims the next unclaimed frame as soon as that frame's slot has been handed on, reads and decodes it
+// through its own file handle, and marks the slot ready; bf_sens_player_next waits for the slot of the next frame in order.  Which thread decodes a
+// frame has no influence on the bytes in its slot.
+struct bf_sens_player {
+    bf_pipeline* pipe = nullptr;
+    bf_sensor_data* sd = nullptr;
+    struct Slot {
+        uint16_t* depth = nullptr; uint8_t* colour = nullptr;
+        int state = 0;                        // 0 free, 1 being decoded, 2 ready
+        uint64_t frame = 0;
+        int rc = BF_OK; std::string err;
+        bool coefficients = false; bf_jpeg_info jpeg; uint64_t colourBytes = 0;
+    };
+    std::vector<Slot> slots;
+    size_t colourCapacity = 0;
+    bool pinned = false;
+    std::mutex m;
+    std::condition_variable cvWork, cvReady;
+    uint64_t nextClaim = 0, nextOut = 0, numFrames = 0;
+    bool stop = false;
+    std::vector<std::thread> threads;
+};
+
+namespace {
+
+void playerDecode(bf_sens_player* pl, FILE* f, std::vector<uint8_t>& scratch, bf_sens_player::Slot& s) {
+    bf_sensor_data* sd = pl->sd;
+    const bf_sensor_data_info& h = sd->info;
+    const bf_sensor_data::Frame& fr = sd->frames[s.frame];
+    const size_t nc = (size_t)h.colorWidth * h.colorHeight;
+    s.coefficients = false; s.colourBytes = nc * 3;
+    s.rc = guarded([&]() -> int {
+        int rc = readDepthRaw(sd, f, scratch, s.frame, s.depth);
+        if (rc) return rc;
+        if (fr.colorSize == 0) { set_error("sens: frame %llu has no colour data: the device ingest needs colour (use the host ingest for this file)", (unsigned long long)s.frame); return BF_ERR_NOT_ON_DEVICE; }
+        const int32_t ct = h.colorCompressionType;
+        if (ct == BF_SENS_COLOR_RAW) {
+            if (fr.colorSize != nc * 3) { set_error("sens: frame %llu: raw colour has %llu bytes, expected %llu", (unsigned long long)s.frame, (unsigned long long)fr.colorSize, (unsigned long long)(nc * 3)); return BF_ERR_STATE; }
+            return readBytes(f, fr.colorOffset, fr.colorSize, s.colour);
+        }
+        if (ct != BF_SENS_COLOR_PNG && ct != BF_SENS_COLOR_JPEG) { set_error("sens: colour compression type %d is not supported", ct); return BF_ERR_INVALID_ARG; }
+        scratch.resize(fr.colorSize);
+        rc = readBytes(f, fr.colorOffset, fr.colorSize, scratch.data());
+        if (rc) return rc;
+        if (sd->decoder) {
+            if (sd->decoder(sd->decoderUser, scratch.data(), fr.colorSize, ct, h.colorWidth, h.colorHeight, s.colour) != 0) { set_error("sens: frame %llu: the colour decoder failed", (unsigned long long)s.frame); return BF_ERR_STATE; }
+            return BF_OK;
+        }
+        if (ct == BF_SENS_COLOR_JPEG) {
+            rc = bf_jpeg_parse(scratch.data(), fr.colorSize, h.colorWidth, h.colorHeight, &s.jpeg);
+            if (rc) return rc;
+            if (jpeg_on_device(s.jpeg) && (size_t)s.jpeg.numBlocks * 128 <= pl->colourCapacity) {
+                rc = bf_jpeg_entropy_decode(scratch.data(), fr.colorSize, &s.jpeg, reinterpret_cast<int16_t*>(s.colour), (uint64_t)s.jpeg.numBlocks * 64);
+                if (rc == BF_OK) { s.coefficients = true; s.colourBytes = (uint64_t)s.jpeg.numBlocks * 128; return BF_OK; }
+                if (rc != BF_ERR_NOT_ON_DEVICE) return rc;
+            }
+        }
+        return bf_decode_color_rgb(scratch.data(), fr.colorSize, ct, h.colorWidth, h.colorHeight, s.colour);
+    });
+    if (s.rc) s.err = bf_last_error();
+}
+
+void playerWorker(bf_sens_player* pl) {
+    FILE* f = fopen(pl->sd->path.c_str(), "rb");          // a handle of its own: the reader's is not shared between threads
+    std::vector<uint8_t> scratch;
+    for (;;) {
+        bf_sens_player::Slot* s = nullptr;
+        {
+            std::unique_lock<std::mutex> lk(pl->m);
+            pl->cvWork.wait(lk, [&] { return pl->stop || (pl->nextClaim < pl->numFrames && pl->slots[pl->nextClaim % pl->slots.size()].state == 0); });
+            if (pl->stop) break;
+            s = &pl->slots[pl->nextClaim % pl->slots.size()];
+            s->state = 1; s->frame = pl->nextClaim++;
+        }
+        if (f) playerDecode(pl, f, scratch, *s);
+        else { s->rc = BF_ERR_STATE; s->err = "could not open file " + pl->sd->path; }
+        {
+            std::lock_guard<std::mutex> lk(pl->m);
+            s->state = 2;
+        }
+        pl->cvReady.notify_all();
+    }
+    if (f) fclose(f);
+}
+
+// the slot of the next frame in order, decoded; null at the end of the file
+bf_sens_player::Slot* playerWait(bf_sens_player* pl) {
+    std::unique_lock<std::mutex> lk(pl->m);
+    if (pl->nextOut >= pl->numFrames) return nullptr;
+    bf_sens_player::Slot& s = pl->slots[pl->nextOut % pl->slots.size()];
+    pl->cvReady.wait(lk, [&] { return s.state == 2 && s.frame == pl->nextOut; });
+    return &s;
+}
+
+void playerRelease(bf_sens_player* pl, bf_sens_player::Slot* s) {
+    {
+        std::lock_guard<std::mutex> lk(pl->m);
+        s->state = 0; pl->nextOut++;
+    }
+    pl->cvWork.notify_all();
+}
+
+}  // namespace
+
+extern "C" {
+
+int bf_sens_player_destroy(bf_sens_player* pl) {
+    if (!pl) return BF_OK;
+    {
+        std::lock_guard<std::mutex> lk(pl->m);
+        pl->stop = true;
+    }
+    pl->cvWork.notify_all();
+    for (std::thread& t : pl->threads) t.join();
+    for (bf_sens_player::Slot& s : pl->slots) {
+        if (pl->pinned) { (void)hipHostFree(s.depth); (void)hipHostFree(s.colour); }
+        else { free(s.depth); free(s.colour); }
+    }
+    delete pl;
+    return BF_OK;
+}
+
+int bf_sens_player_create(bf_pipeline* pipeline, bf_sensor_data* sd, uint32_t numThreads, bf_sens_player** out) {
+    return guarded([&]() -> int {
+    BF_REQUIRE(sd && out, "null argument");
+    BF_REQUIRE(numThreads <= 12, "at most 12 decode threads");
+    if (numThreads == 0) numThreads = 4;
+    const bf_sensor_data_info& h = sd->info;
+    BF_REQUIRE(h.depthWidth > 0 && h.depthHeight > 0 && h.colorWidth > 0 && h.colorHeight > 0, "the file has no depth or no colour images");
+    bf_sens_player* pl = new bf_sens_player;
+    pl->pipe = pipeline; pl->sd = sd; pl->numFrames = sd->frames.size(); pl->pinned = pipeline != nullptr;
+    // the coefficients of any layout the device takes: three components at no more than full resolution, padded to whole 16 x 16 MCUs, 2 bytes each
+    const size_t padW = ((size_t)h.colorWidth + 15) / 16 * 16, padH = ((size_t)h.colorHeight + 15) / 16 * 16;
+    pl->colourCapacity = std::max((size_t)h.colorWidth * h.colorHeight * 3, padW * padH * 6);
+    const size_t depthBytes = (size_t)h.depthWidth * h.depthHeight * 2;
+    pl->slots.resize(numThreads + 2);
+    for (bf_sens_player::Slot& s : pl->slots) {
+        if (pl->pinned) {
+            if (hipHostMalloc((void**)&s.depth, depthBytes) != hipSuccess || hipHostMalloc((void**)&s.colour, pl->colourCapacity) != hipSuccess) {
+                set_error("bf_sens_player_create: no pinned host memory (%s)", hipGetErrorString(hipGetLastError()));
+                bf_sens_player_destroy(pl);
+                return BF_ERR_HIP;
+            }
+        } else {
+            s.depth = (uint16_t*)malloc(depthBytes); s.colour = (uint8_t*)malloc(pl->colourCapacity);
+            if (!s.depth || !s.colour) { bf_sens_player_destroy(pl); throw std::bad_alloc(); }
+        }
+    }
+    for (uint32_t t = 0; t < numThreads; ++t) pl->threads.emplace_back(playerWorker, pl);
+    *out = pl;
+    return BF_OK;
+    });
+}
+
+int bf_sens_player_peek(bf_sens_player* pl, bf_sens_frame* out, int* gotFrame) {
+    BF_REQUIRE(pl && out && gotFrame, "null argument");
+    *gotFrame = 0;
+    bf_sens_player::Slot* s = playerWait(pl);
+    if (!s) return BF_OK;
+    if (s->rc) { set_error("%s", s->err.c_str()); return s->rc; }
+    memset(out, 0, sizeof *out);
+    out->frame = s->frame; out->depthU16 = s->depth; out->colour = s->colour; out->colourBytes = s->colourBytes; out->jpegCoefficients = s->coefficients ? 1 : 0;
+    if (s->coefficients) out->jpeg = s->jpeg;
+    *gotFrame = 1;
+    return BF_OK;
+}
+
+int bf_sens_player_next(bf_sens_player* pl, int* gotFrame) {
+    BF_REQUIRE(pl && gotFrame, "null argument");
+    *gotFrame = 0;
+    bf_sens_player::Slot* s = playerWait(pl);
+    if (!s) return BF_OK;
+    int rc = s->rc, got = 1;
+    if (rc) set_error("%s", s->err.c_str());
+    else if (pl->pipe) rc = bf_pipeline_process_frame_raw_decoded(pl->pipe, s->depth, pl->sd->info.depthShift, s->colour, s->coefficients ? &s->jpeg : nullptr, &got);
+    playerRelease(pl, s);                    // a failed frame is passed over: the caller decides whether to go on
+    if (rc) return rc;
+    *gotFrame = got;
+    return BF_OK;
 }
 
 }  // extern "C"

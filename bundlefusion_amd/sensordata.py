@@ -1,6 +1,6 @@
 """ctypes view of include/bf_sensordata.h: recorded RGB-D sequences (".sens", ml::SensorData version 4).
 
-Host-only.  JPEG / PNG colour frames are decoded with Pillow through the C ABI's decoder callback when Pillow is
+Host-only but for SensPlayer over a pipeline, which feeds the device ingest.  JPEG / PNG colour frames are decoded with Pillow through the C ABI's decoder callback when Pillow is
 importable (the reference decodes them with stb_image inside mLib); raw colour and raw / zlib depth need nothing.
 """
 import ctypes as C
@@ -8,7 +8,7 @@ import io
 
 import numpy as np
 
-from .capi import lib, check, RGBDSensorDesc
+from .capi import lib, check, RGBDSensorDesc, JpegInfo, BF_ERR_NOT_ON_DEVICE
 
 COLOR_RAW, COLOR_PNG, COLOR_JPEG = 0, 1, 2
 DEPTH_RAW_USHORT, DEPTH_ZLIB_USHORT, DEPTH_OCCI_USHORT = 0, 1, 2
@@ -46,6 +46,68 @@ lib.bf_sensor_data_writer_close.argtypes = [C.c_void_p]
 lib.bf_sensor_data_save_with_trajectory.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint64]
 lib.bf_evaluate_ate_rmse.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]
 lib.bf_sensor_data_evaluate_trajectory.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]
+lib.bf_decode_color_rgb.argtypes = [C.c_void_p, C.c_uint64, C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p]
+lib.bf_encode_jpeg_rgb.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+lib.bf_jpeg_parse.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(JpegInfo)]
+lib.bf_jpeg_entropy_decode.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(JpegInfo), C.c_void_p, C.c_uint64]
+lib.bf_jpeg_reconstruct_host.argtypes = [C.POINTER(JpegInfo), C.c_void_p, C.c_void_p]
+
+
+class SensFrame(C.Structure):
+    _fields_ = [("frame", C.c_uint64), ("depthU16", C.c_void_p), ("colour", C.c_void_p), ("colourBytes", C.c_uint64), ("jpegCoefficients", C.c_int32), ("jpeg", JpegInfo)]
+
+
+lib.bf_sens_player_create.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]
+lib.bf_sens_player_next.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+lib.bf_sens_player_peek.argtypes = [C.c_void_p, C.POINTER(SensFrame), C.POINTER(C.c_int)]
+lib.bf_sens_player_destroy.argtypes = [C.c_void_p]
+
+
+def decode_color_rgb(blob, compression, width, height):
+    """the built-in colour decoder (bf_decode_color_rgb): stored bytes -> RGB8 (h, w, 3)"""
+    buf = np.frombuffer(blob, np.uint8)
+    out = np.empty((height, width, 3), np.uint8)
+    check(lib.bf_decode_color_rgb(buf.ctypes.data, buf.size, compression, width, height, out.ctypes.data))
+    return out
+
+
+def encode_jpeg_rgb(rgb, quality=90):
+    """baseline 4:4:4 JPEG of an RGB8 image (bf_encode_jpeg_rgb), as bytes"""
+    a = np.ascontiguousarray(rgb, np.uint8)
+    h, w = a.shape[:2]
+    n = C.c_uint64()
+    check(lib.bf_encode_jpeg_rgb(a.ctypes.data, w, h, quality, None, 0, C.byref(n)))
+    buf = np.empty(n.value, np.uint8)
+    check(lib.bf_encode_jpeg_rgb(a.ctypes.data, w, h, quality, buf.ctypes.data, n.value, C.byref(n)))
+    return buf.tobytes()
+
+
+def jpeg_parse(blob, width=0, height=0):
+    """headers of a baseline JPEG stream -> JpegInfo (bf_jpeg_parse); width x height: the size the container states (0 x 0: any)"""
+    buf = np.frombuffer(blob, np.uint8)
+    info = JpegInfo()
+    check(lib.bf_jpeg_parse(buf.ctypes.data, buf.size, width, height, C.byref(info)))
+    return info
+
+
+def jpeg_entropy_decode(blob, info):
+    """the scan's quantised coefficients, int16 (numBlocks, 64) in the layout of bf_jpeg_info, or None where they do not fit int16 (BF_ERR_NOT_ON_DEVICE)"""
+    buf = np.frombuffer(blob, np.uint8)
+    coef = np.empty((info.numBlocks, 64), np.int16)
+    rc = lib.bf_jpeg_entropy_decode(buf.ctypes.data, buf.size, C.byref(info), coef.ctypes.data, coef.size)
+    if rc == BF_ERR_NOT_ON_DEVICE:
+        return None
+    check(rc)
+    return coef
+
+
+def jpeg_reconstruct_host(info, coef):
+    """coefficients -> RGB8 (h, w, 3) on the host: the image the device reconstruction gives"""
+    coef = np.ascontiguousarray(coef, np.int16)
+    assert coef.size == info.numBlocks * 64
+    out = np.empty((info.height, info.width, 3), np.uint8)
+    check(lib.bf_jpeg_reconstruct_host(C.byref(info), coef.ctypes.data, out.ctypes.data))
+    return out
 
 
 def _pillow_decode(_user, data, size, _ctype, width, height, out):
@@ -149,6 +211,55 @@ class SensorData:
         rmse, n = C.c_float(), C.c_uint32()
         check(lib.bf_sensor_data_evaluate_trajectory(self._h, T.ctypes.data, len(T), C.byref(rmse), C.byref(n)))
         return rmse.value, n.value
+
+
+class SensPlayer:
+    """Decode-ahead player (bf_sens_player): `threads` workers read, inflate and entropy-decode the frames of `sensor_data` ahead of the loop; next() hands
+    the next frame, in order, to `pipeline`'s device ingest.  pipeline None: decode only - peek() shows the slot next() would hand over (no GPU needed).
+    Open the file with SensorData(path, use_pillow=False): a decoder callback would be called from every worker thread, and its frames travel as RGB8."""
+
+    def __init__(self, pipeline, sensor_data, threads=4):
+        self._h = C.c_void_p()
+        self._pipe, self._sd = pipeline, sensor_data                      # both must outlive the player
+        check(lib.bf_sens_player_create(pipeline._h if pipeline is not None else None, sensor_data._h, int(threads), C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib.bf_sens_player_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def next(self):
+        """-> whether a frame was handed over (False at the end of the file); raises at the frame that failed to decode"""
+        got = C.c_int()
+        check(lib.bf_sens_player_next(self._h, C.byref(got)))
+        return bool(got.value)
+
+    def peek(self):
+        """copies of the next frame's slot: (frame, depth u16 (h, w), colour, JpegInfo or None) - colour is RGB8 (h, w, 3), or int16 coefficients (numBlocks, 64)
+        with a JpegInfo; None at the end of the file"""
+        fr, got = SensFrame(), C.c_int()
+        check(lib.bf_sens_player_peek(self._h, C.byref(fr), C.byref(got)))
+        if not got.value:
+            return None
+        i = self._sd.info
+        depth = np.frombuffer((C.c_uint8 * (i.depthWidth * i.depthHeight * 2)).from_address(fr.depthU16), np.uint16).reshape(i.depthHeight, i.depthWidth).copy()
+        raw = np.frombuffer((C.c_uint8 * fr.colourBytes).from_address(fr.colour), np.uint8).copy()
+        if fr.jpegCoefficients:
+            info = JpegInfo.from_buffer_copy(fr.jpeg)
+            return fr.frame, depth, raw.view(np.int16).reshape(info.numBlocks, 64), info
+        return fr.frame, depth, raw.reshape(i.colorHeight, i.colorWidth, 3), None
 
 
 class SensorDataWriter:

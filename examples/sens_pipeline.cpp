@@ -1,8 +1,12 @@
 // Plays a recorded ".sens" file through the whole-loop C entry points (bf_pipeline_*: four streams, volume worker thread,
 // one-frame detection look-ahead) and evaluates the optimised trajectory against the poses stored in the file.
 // Build:  g++ -std=c++17 -I include examples/sens_pipeline.cpp -L bundlefusion_amd/lib -lbf_hip -Wl,-rpath,$PWD/bundlefusion_amd/lib -o sens_pipeline
-// Run:    ./sens_pipeline sequence.sens [zParametersDefault.txt zParametersBundlingDefault.txt]
+// Run:    ./sens_pipeline sequence.sens [--ingest host|device] [--decode-threads N] [zParametersDefault.txt zParametersBundlingDefault.txt]
+//   --ingest host    (default) frames are decoded to float depth / RGBX on this thread (SensorDataReader) and handed over as host buffers
+//   --ingest device  SensPlayer: N threads (default 4, at most 12) decode ahead; depth conversion and JPEG reconstruction run on the device.  Same results.
 #include <cstdio>
+#include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "bundlefusion/bundlefusion.hpp"
@@ -10,23 +14,38 @@
 using namespace bundlefusion;
 
 int main(int argc, char** argv) {
-    if (argc < 2) { std::printf("usage: %s sequence.sens [zParametersDefault.txt zParametersBundlingDefault.txt]\n", argv[0]); return 0; }
+    if (argc < 2) { std::printf("usage: %s sequence.sens [--ingest host|device] [--decode-threads N] [zParametersDefault.txt zParametersBundlingDefault.txt]\n", argv[0]); return 0; }
     try {
+        bool deviceIngest = false;
+        unsigned int decodeThreads = 4;
+        std::vector<const char*> files;
+        for (int i = 2; i < argc; ++i) {
+            if (!std::strcmp(argv[i], "--ingest") && i + 1 < argc) { deviceIngest = !std::strcmp(argv[++i], "device"); }
+            else if (!std::strcmp(argv[i], "--decode-threads") && i + 1 < argc) decodeThreads = (unsigned int)std::atoi(argv[++i]);
+            else files.push_back(argv[i]);
+        }
         GlobalAppState& gas = GlobalAppState::get();
         GlobalBundlingState& gbs = GlobalBundlingState::get();
-        if (argc >= 4) { gas.readMembers(argv[2]); gbs.readMembers(argv[3]); }
-        SensorDataReader sensor;
+        if (files.size() >= 2) { gas.readMembers(files[0]); gbs.readMembers(files[1]); }
+        SensorDataReader sensor;                                     // (the device ingest uses it for the description and the evaluation only)
         sensor.createFirstConnected(argv[1]);
-        if (argc < 4) { gas.s_integrationWidth = sensor.getDepthWidth(); gas.s_integrationHeight = sensor.getDepthHeight(); }
+        if (files.size() < 2) { gas.s_integrationWidth = sensor.getDepthWidth(); gas.s_integrationHeight = sensor.getDepthHeight(); }
         gas.s_sensorIdx = 8;
         bf_pipeline* p = nullptr;
         check(bf_pipeline_create(&gas, &gbs, &sensor.desc(), &p));
         unsigned int frames = 0;
-        while (sensor.processDepth() && sensor.processColor()) {
-            int got = 0;
-            check(bf_pipeline_process_frame(p, sensor.getDepthFloat(), sensor.getColorRGBX(), &got));     // buffers are free again on return
-            if (!got) break;
-            ++frames;
+        if (deviceIngest) {
+            SensPlayer player;
+            player.open(argv[1]);
+            player.start(p, decodeThreads);
+            while (player.next()) ++frames;
+        } else {
+            while (sensor.processDepth() && sensor.processColor()) {
+                int got = 0;
+                check(bf_pipeline_process_frame(p, sensor.getDepthFloat(), sensor.getColorRGBX(), &got));     // buffers are free again on return
+                if (!got) break;
+                ++frames;
+            }
         }
         for (int k = 0; k < 5; ++k) check(bf_pipeline_process_end_of_sequence(p, nullptr));               // let the last solves and fixes finish
         check(bf_pipeline_synchronize(p));

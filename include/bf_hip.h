@@ -34,7 +34,8 @@ typedef enum bf_status {
     BF_ERR_HIP = -2,           /* a HIP runtime call failed                      */
     BF_ERR_NO_DEVICE = -3,     /* no gfx950 device / extension unusable          */
     BF_ERR_CAPACITY = -4,      /* a fixed-capacity buffer overflowed             */
-    BF_ERR_STATE = -5          /* call order violated (e.g. GC before compactify) */
+    BF_ERR_STATE = -5,         /* call order violated (e.g. GC before compactify) */
+    BF_ERR_NOT_ON_DEVICE = -6  /* a valid input that only the host path handles (bf_jpeg_*): decode on the host instead */
 } bf_status;
 
 BF_API const char* bf_last_error(void);
@@ -568,7 +569,47 @@ BF_API int bf_image_resample_to_intensity(float* d_output, uint32_t outputWidth,
                                           uint32_t inputWidth, uint32_t inputHeight, void* hip_stream);
 
 /* ------------------------------------------------------------------------- */
-/* Marching cubes over the voxel hash:                                         */
+/* Sensor-format ingest (csrc/sensoringest.hip): what SensorDataReader::      */
+/* processDepth (SensorDataReader.cpp:98-111) does on the host, on the device */
+/* (device pointers, asynchronous on hip_stream)                              */
+/* ------------------------------------------------------------------------- */
+/* u16 depth -> metres: 0 -> -inf, otherwise (float)raw / depthShift (a correctly rounded division: the bytes of bf_sensor_data_read_depth) */
+BF_API int bf_image_convert_depth_u16(float* d_output, const uint16_t* d_input, float depthShift, uint32_t numPixels, void* hip_stream);
+/* RGB8 -> RGBX8 with X = 255 (the vec4uc(vec3uc) widening; the bytes of bf_sensor_data_read_color_rgbx) */
+BF_API int bf_image_convert_rgb8_to_rgbx(uint8_t* d_output, const uint8_t* d_input, uint32_t numPixels, void* hip_stream);
+
+/* A baseline JPEG frame between its entropy decode (host: bf_jpeg_parse / bf_jpeg_entropy_decode, bf_sensordata.h) and its reconstruction
+ * (host: inside bf_decode_color_rgb; device: bf_jpeg_reconstruct_device).
+ * Coefficient buffer: numBlocks * 64 int16, QUANTISED, each block in natural (row-major, not zigzag) order.  Blocks are stored
+ * component after component (comp[c].blockOffset), and inside a component in raster order of its block grid, which is padded to whole
+ * MCUs: block (bx, by) of component c is block number comp[c].blockOffset + by * comp[c].blocksX + bx. */
+typedef struct bf_jpeg_component {
+    uint32_t h, v;                  /* sampling factors (1 or 2) */
+    uint32_t tq;                    /* its quantisation table */
+    uint32_t blocksX, blocksY;      /* block grid = mcusX * h, mcusY * v */
+    uint32_t blockOffset;           /* first block of the component in the coefficient buffer */
+    uint32_t planeOffset;           /* first byte of its sample plane (8 blocksX x 8 blocksY bytes) in the reconstruction's scratch */
+    uint32_t reserved;
+} bf_jpeg_component;
+typedef struct bf_jpeg_info {
+    uint32_t width, height;
+    uint32_t numComponents;         /* 1 (grey) or 3 (YCbCr) */
+    uint32_t hmax, vmax, mcusX, mcusY;
+    uint32_t restartInterval;       /* in MCUs, 0 = none */
+    uint32_t numBlocks;             /* of all components: the coefficient buffer holds numBlocks * 64 int16 */
+    uint32_t planeBytes;            /* scratch of the reconstruction: the sample planes of all components */
+    bf_jpeg_component comp[3];
+    uint16_t qt[4][64];             /* quantisation tables, natural order (8- or 16-bit precision) */
+    uint8_t qtPresent[4];
+} bf_jpeg_info;
+/* dequantise, islow inverse DCT, chroma up-sampling, YCbCr -> RGB, written as width*height RGBX8 with X = 255: byte for byte the image
+ * bf_decode_color_rgb gives, widened.  d_planes: info->planeBytes bytes of scratch (8-byte aligned).  Layouts: 1 component; 3 components with luma at
+ * hmax x vmax and each chroma component at 1x1, 2x1 or 2x2 of it.  Everything else the host decoder reads (chroma sub-sampled vertically only)
+ * returns BF_ERR_NOT_ON_DEVICE and launches nothing. */
+BF_API int bf_jpeg_reconstruct_device(const bf_jpeg_info* info, const int16_t* d_coefficients, uint8_t* d_planes, uint8_t* d_rgbxOut, void* hip_stream);
+
+/* ------------------------------------------------------------------------- */
+/* Marching cubes over the voxel hash:                                        */
 /* DepthSensing/CUDAMarchingCubesHashSDF.h:8-58, .cpp, CUDAMarchingCubesSDF.cu, */
 /* MarchingCubesSDFUtil.h:9-287 (a consumer of getHashData(): it reads the raw  */
 /* arrays in the reference layout)                                             */

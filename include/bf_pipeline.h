@@ -124,6 +124,21 @@ BF_API int bf_image_manager_reset(bf_image_manager* im);
  * The _device form takes the same two images already resident in HBM (no PCIe transfer).          */
 BF_API int bf_image_manager_process(bf_image_manager* im, const float* h_depth, const uint8_t* h_colorRGBX, int* gotFrame);
 BF_API int bf_image_manager_process_device(bf_image_manager* im, const float* d_depth, const uint8_t* d_colorRGBX, int* gotFrame);
+/* MI355X addition: the same for a frame in SENSOR format - u16 depth (metres = raw / depthShift, 0 invalid) and colour as stored in a recording
+ * (colourCompression: 0 raw RGB8, 1 PNG, 2 JPEG - the BF_SENS_COLOR_* values of bf_sensordata.h).  The call copies the frame into pinned staging owned
+ * by the manager (the caller's buffers are free on return), uploads the u16 image and the RGB8 bytes or - JPEG - the quantised coefficients, converts /
+ * reconstructs on the device (bf_image_convert_depth_u16, bf_image_convert_rgb8_to_rgbx, bf_jpeg_reconstruct_device) and continues as
+ * bf_image_manager_process_device.  PNG, and JPEG the device declines, are decoded on the host inside the call.  The stored images are those of
+ * bf_image_manager_process on the host-decoded frame, byte for byte.
+ *   _raw_decoded: host buffers with the entropy decode done (jpeg != NULL: h_colour holds jpeg->numBlocks * 64 coefficients; NULL: RGB8); uploaded from where
+ *                 they are (pinned memory makes that a DMA), free on return.
+ *   _raw_device:  the same buffers already in device memory. */
+BF_API int bf_image_manager_process_raw(bf_image_manager* im, const uint16_t* h_depthU16, float depthShift, const uint8_t* h_colour, uint64_t colourBytes,
+                                        int32_t colourCompression, int* gotFrame);
+BF_API int bf_image_manager_process_raw_decoded(bf_image_manager* im, const uint16_t* h_depthU16, float depthShift, const void* h_colour, const bf_jpeg_info* jpeg,
+                                                int* gotFrame);
+BF_API int bf_image_manager_process_raw_device(bf_image_manager* im, const uint16_t* d_depthU16, float depthShift, const void* d_colour, const bf_jpeg_info* jpeg,
+                                               int* gotFrame);
 /* copyToBundling(d_depthRaw, d_depthFilt, d_color)  .h:223-227 */
 BF_API int bf_image_manager_copy_to_bundling(bf_image_manager* im, float* d_depthRaw, float* d_depthFilt, uint8_t* d_color);
 /* the device input buffers themselves (d_depthInputRaw, d_depthInputFiltered, d_colorInput) */
@@ -354,6 +369,11 @@ BF_API int bf_pipeline_get_solve_lag(bf_pipeline* p, uint32_t* lag);
  * accessor below - results are those of the serial order. */
 BF_API int bf_pipeline_process_frame(bf_pipeline* p, const float* h_depth, const uint8_t* h_colorRGBX, int* gotFrame);
 BF_API int bf_pipeline_process_frame_device(bf_pipeline* p, const float* d_depth, const uint8_t* d_colorRGBX, int* gotFrame);
+/* the same with a frame in sensor format, converted / reconstructed on the device on the ingest stream: see bf_image_manager_process_raw* */
+BF_API int bf_pipeline_process_frame_raw(bf_pipeline* p, const uint16_t* h_depthU16, float depthShift, const uint8_t* h_colour, uint64_t colourBytes,
+                                         int32_t colourCompression, int* gotFrame);
+BF_API int bf_pipeline_process_frame_raw_decoded(bf_pipeline* p, const uint16_t* h_depthU16, float depthShift, const void* h_colour, const bf_jpeg_info* jpeg, int* gotFrame);
+BF_API int bf_pipeline_process_frame_raw_device(bf_pipeline* p, const uint16_t* d_depthU16, float depthShift, const void* d_colour, const bf_jpeg_info* jpeg, int* gotFrame);
 /* one iteration after the sensor stopped delivering frames (solve + re-integration continue, :175-196) */
 BF_API int bf_pipeline_process_end_of_sequence(bf_pipeline* p, uint32_t* numActiveOperations);
 BF_API int bf_pipeline_synchronize(bf_pipeline* p);

@@ -18,7 +18,8 @@
  *        colour bytes, depth bytes
  *   u64  numIMUFrames, then per IMU frame 5 x f64[3] + u64 time stamp (128 B)      (may be absent in older files)
  *
- * All functions run on the host only (no GPU needed); status / error conventions as in bf_hip.h.
+ * All functions run on the host only (no GPU needed), with one exception: a bf_sens_player created over a pipeline feeds that pipeline's
+ * device ingest (bf_sens_player_next).  Status / error conventions as in bf_hip.h.
  */
 #ifndef BF_SENSORDATA_H
 #define BF_SENSORDATA_H
@@ -55,6 +56,16 @@ BF_API int bf_decode_color_rgb(const uint8_t* data, uint64_t size, int32_t compr
  * (TYPE_JPEG, RGBDSensor.cpp:276).  out == NULL: only *size is returned (the stream is kept for the following call with a buffer). */
 BF_API int bf_encode_jpeg_rgb(const uint8_t* rgb, uint32_t width, uint32_t height, int32_t quality, uint8_t* out, uint64_t capacity, uint64_t* size);
 
+/* The built-in JPEG decoder in its stages, for callers that reconstruct on the device (bf_jpeg_info, bf_jpeg_reconstruct_device: bf_hip.h):
+ *   bf_jpeg_parse           headers up to the scan -> *info.  expectWidth x expectHeight: the size the container states (0 x 0: any)
+ *   bf_jpeg_entropy_decode  Huffman decode of the scan into info->numBlocks * 64 int16 (layout: bf_jpeg_info); capacity in int16.
+ *                           BF_ERR_NOT_ON_DEVICE for a (hostile) stream whose DC values leave int16: bf_decode_color_rgb still reads it
+ *   bf_jpeg_reconstruct_host  the coefficients -> width*height RGB8: what bf_jpeg_reconstruct_device computes, on the host
+ * bf_decode_color_rgb is these three in one pass; they reject what it rejects, with the same messages. */
+BF_API int bf_jpeg_parse(const uint8_t* data, uint64_t size, uint32_t expectWidth, uint32_t expectHeight, bf_jpeg_info* info);
+BF_API int bf_jpeg_entropy_decode(const uint8_t* data, uint64_t size, const bf_jpeg_info* info, int16_t* coefficients, uint64_t capacity);
+BF_API int bf_jpeg_reconstruct_host(const bf_jpeg_info* info, const int16_t* coefficients, uint8_t* rgbOut);
+
 /* SensorData::loadFromFile (frames are indexed and read on demand, so a file larger than host memory can be played) */
 BF_API int bf_sensor_data_open(const char* filename, bf_sensor_data** out);
 BF_API int bf_sensor_data_close(bf_sensor_data* sd);
@@ -75,6 +86,29 @@ BF_API int bf_sensor_data_read_color_compressed(bf_sensor_data* sd, uint64_t fra
 /* decompressColorAlloc + the vec4uc(vec3uc) widening of processDepth (:107-111): colourWidth*colourHeight RGBX, X = 255.
  * A file without colour (size 0) yields zeros like the reference's untouched m_colorRGBX. */
 BF_API int bf_sensor_data_read_color_rgbx(bf_sensor_data* sd, uint64_t frame, uint8_t* h_rgbx);
+
+/* Decode-ahead player: `numThreads` worker threads (0: 4; at most 12) read, inflate and entropy-decode the frames of `sd` in order into a ring of
+ * pinned slots; bf_sens_player_next hands the next frame, strictly in frame order, to the pipeline's device ingest
+ * (bf_pipeline_process_frame_raw_decoded) and recycles its slot.  JPEG colour in a layout the device reconstructs travels as quantised
+ * coefficients; everything else (PNG, other JPEG layouts, a decoder installed with bf_sensor_data_set_color_decoder) is decoded to RGB8 by the
+ * worker.  The result does not depend on numThreads.  A frame that fails to decode fails the bf_sens_player_next call of THAT frame (status and
+ * bf_last_error of the worker); the frames before it are delivered.  *gotFrame = 0 with BF_OK at the end of the file (or when the pipeline is full).
+ * `pipeline` may be NULL: the player then only decodes, and bf_sens_player_peek is the way to look at the slots (no GPU needed).  `sd` must outlive
+ * the player and must not be read through other calls meanwhile. */
+typedef struct bf_sens_player bf_sens_player;
+typedef struct bf_sens_frame {                /* one decoded slot; the pointers are valid until the next bf_sens_player_next / _destroy */
+    uint64_t frame;
+    const uint16_t* depthU16;                 /* depthWidth * depthHeight */
+    const void* colour;                       /* jpegCoefficients ? int16 coefficients (jpeg.numBlocks * 64) : RGB8 (colourWidth * colourHeight * 3; NULL: no colour stored) */
+    uint64_t colourBytes;
+    int32_t jpegCoefficients;
+    bf_jpeg_info jpeg;                        /* valid when jpegCoefficients */
+} bf_sens_frame;
+BF_API int bf_sens_player_create(bf_pipeline* pipeline, bf_sensor_data* sd, uint32_t numThreads, bf_sens_player** out);
+BF_API int bf_sens_player_next(bf_sens_player* pl, int* gotFrame);
+/* the frame bf_sens_player_next would hand over (waits for its worker); *gotFrame = 0 at the end of the file */
+BF_API int bf_sens_player_peek(bf_sens_player* pl, bf_sens_frame* out, int* gotFrame);
+BF_API int bf_sens_player_destroy(bf_sens_player* pl);
 
 /* SensorData::saveToFile, incrementally.  info: sensorName, calibration, compression types (colour: frames are stored as
  * given; depth: RAW_USHORT or ZLIB_USHORT, compressed here), sizes, depthShift; numFrames is filled in by _close. */

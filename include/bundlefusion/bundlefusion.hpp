@@ -434,6 +434,54 @@ private:
     bool m_bHasColorData = false, m_playData = true, m_bIsReceivingFrames = false;
 };
 
+// ---- SensPlayer: a ".sens" file played into a bf_pipeline's DEVICE ingest (no counterpart in the reference, whose reader hands out floats on one host thread):
+// worker threads read, inflate and entropy-decode ahead; the u16 depth and the RGB8 / JPEG coefficients are converted and reconstructed on the device.
+// The results are those of SensorDataReader + bf_pipeline_process_frame, bit for bit.  open() first (the pipeline needs desc()), then start(), then next() per frame.
+class SensPlayer {
+public:
+    SensPlayer() { std::memset(&m_desc, 0, sizeof m_desc); std::memset(&m_info, 0, sizeof m_info); }
+    ~SensPlayer() { close(); }
+    SensPlayer(const SensPlayer&) = delete;
+    void open(const std::string& filename) {
+        close();
+        check(bf_sensor_data_open(filename.c_str(), &m_sd));
+        check(bf_sensor_data_get_info(m_sd, &m_info));
+        check(bf_sensor_data_get_sensor_desc(m_sd, &m_desc));
+    }
+    void start(bf_pipeline* pipeline, unsigned int numThreads = 4) {          // numThreads: 1 .. 12 decode threads (0: the default, 4)
+        if (!m_sd) throw std::runtime_error("SensPlayer::start before open");
+        if (m_player) { bf_sens_player_destroy(m_player); m_player = nullptr; }
+        check(bf_sens_player_create(pipeline, m_sd, numThreads, &m_player));
+    }
+    bool next() {                                                              // false behind the last frame (or when the pipeline takes no more frames)
+        if (!m_player) throw std::runtime_error("SensPlayer::next before start");
+        int got = 0;
+        check(bf_sens_player_next(m_player, &got));
+        return got != 0;
+    }
+    void close() {
+        if (m_player) bf_sens_player_destroy(m_player);
+        m_player = nullptr;
+        if (m_sd) bf_sensor_data_close(m_sd);
+        m_sd = nullptr;
+    }
+    const bf_rgbd_sensor_desc& desc() const { return m_desc; }
+    const bf_sensor_data_info& info() const { return m_info; }
+    unsigned int getNumFrames() const { return (unsigned int)m_info.numFrames; }
+    std::string getSensorName() const { return m_info.sensorName; }
+    std::pair<float, unsigned int> evaluateTrajectory(const std::vector<mat4f>& trajectory) const {
+        float rmse = 0.0f; uint32_t n = 0;
+        check(bf_sensor_data_evaluate_trajectory(m_sd, trajectory.empty() ? nullptr : trajectory[0].m, trajectory.size(), &rmse, &n));
+        std::printf("*********************************\nate rmse = %g, %u\n*********************************\n", rmse, n);
+        return std::make_pair(rmse, (unsigned int)n);
+    }
+private:
+    bf_sensor_data* m_sd = nullptr;
+    bf_sens_player* m_player = nullptr;
+    bf_sensor_data_info m_info;
+    bf_rgbd_sensor_desc m_desc;
+};
+
 // ---- CUDAImageManager (CUDAImageManager.h:10-337)
 class CUDAImageManager {
 public:

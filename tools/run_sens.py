@@ -2,7 +2,10 @@
 optimised trajectory against the poses stored in the file (SensorDataReader::evaluateTrajectory).
 
 usage: python tools/run_sens.py sequence.sens [--voxel 0.01] [--app zParametersDefault.txt] [--bundling zParametersBundlingDefault.txt]
-Frames are decoded on the host and handed over as host buffers (the PCIe path of bf_pipeline_process_frame).
+                                [--ingest host|device] [--decode-threads N]
+--ingest host (default): frames are decoded on the host and handed over as host buffers (the PCIe path of bf_pipeline_process_frame).
+--ingest device: sensordata.SensPlayer - N threads (default 4, at most 12) read, inflate and entropy-decode ahead, the u16 depth and the RGB8 / JPEG
+coefficients go up the bus and are converted / reconstructed on the device (bf_pipeline_process_frame_raw_decoded).  Same results, bit for bit.
 """
 import argparse
 import os
@@ -26,9 +29,12 @@ def main():
     ap.add_argument("--blocks", type=int, default=None)
     ap.add_argument("--frames", type=int, default=0, help="play only the first N frames")
     ap.add_argument("--tail", type=int, default=5, help="end-of-sequence iterations")
+    ap.add_argument("--ingest", choices=("host", "device"), default="host", help="where frames are converted to float depth / RGBX")
+    ap.add_argument("--decode-threads", type=int, default=4, help="decode-ahead threads of --ingest device (1 .. 12)")
+    ap.add_argument("--decoder", choices=("auto", "builtin"), default="auto", help="--ingest host: auto decodes JPEG / PNG with Pillow where it is installed, builtin with the library's decoder")
     ap.add_argument("--save", default=None, help="write a copy of the file with the optimised trajectory (SensorDataReader::saveToFile)")
     a = ap.parse_args()
-    sd = sdm.SensorData(a.sens)
+    sd = sdm.SensorData(a.sens, use_pillow=a.ingest == "host" and a.decoder == "auto")        # (the player's workers decode with the library's own decoder)
     n = len(sd) if a.frames <= 0 else min(a.frames, len(sd))
     desc = sd.sensor_desc()
     gas = bf.capi.default_app_state(a.app)
@@ -44,17 +50,24 @@ def main():
     p = bf.capi.Pipeline(gas, gbs, desc)
     t0 = time.time()
     keep = []                                               # the last few host frames stay alive while their upload may be in flight
-    for k in range(n):
-        depth = sd.depth(k)                                 # metres, -inf invalid
-        color = sd.color_rgbx(k)
-        if not p.process_frame(depth, color):
-            raise RuntimeError("frame not accepted")
-        keep = (keep + [(depth, color)])[-4:]
+    if a.ingest == "device":
+        with sdm.SensPlayer(p, sd, a.decode_threads) as player:
+            for k in range(n):
+                if not player.next():
+                    raise RuntimeError("frame not accepted")
+    else:
+        for k in range(n):
+            depth = sd.depth(k)                                 # metres, -inf invalid
+            color = sd.color_rgbx(k)
+            if not p.process_frame(depth, color):
+                raise RuntimeError("frame not accepted")
+            keep = (keep + [(depth, color)])[-4:]
     for _ in range(a.tail):
         p.process_end_of_sequence()
     p.synchronize()
     dt = time.time() - t0
-    print("%s: %d frames  wall %.3f s -> %.1f frames/s (decode + PCIe included)" % (sd.sensor_name, n, dt, n / dt))
+    print("%s: %d frames  wall %.3f s -> %.1f frames/s (decode + PCIe included; ingest %s%s)" % (
+        sd.sensor_name, n, dt, n / dt, a.ingest, ", %d decode threads" % a.decode_threads if a.ingest == "device" else ""))
     print("counters", p.counters())
     traj = p.optimized_trajectory()
     valid = np.isfinite(traj[:, 0, 0])
