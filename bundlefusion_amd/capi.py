@@ -820,6 +820,7 @@ class GlobalAppState(C.Structure):
         ("s_rayCastWidth", C.c_uint32), ("s_rayCastHeight", C.c_uint32),
         ("s_SDFRayIncrementFactor", C.c_float), ("s_SDFRayThresSampleDistFactor", C.c_float), ("s_SDFRayThresDistFactor", C.c_float),
         ("s_SDFUseGradients", C.c_int32),
+        ("s_remappingDepthDiscontinuityThresOffset", C.c_float), ("s_remappingDepthDiscontinuityThresLin", C.c_float),
     ]
 
 
@@ -874,16 +875,19 @@ def default_bundling_state(path=None):
     return g
 
 
-def sensor_desc(width, height, K):
-    """A sensor whose depth and colour cameras coincide (identity extrinsics), intrinsics K (4x4)."""
+def sensor_desc(width, height, K, color_K=None, depth_extrinsics=None):
+    """A sensor of one image size with depth intrinsics K (4x4).  By default its depth and colour cameras coincide (identity extrinsics, the same
+    intrinsics); color_K gives the colour camera intrinsics of its own, depth_extrinsics (4x4, depth camera -> colour camera) a displaced depth camera."""
     s = RGBDSensorDesc()
     s.depthWidth = s.colorWidth = width
     s.depthHeight = s.colorHeight = height
     k = np.asarray(K, np.float32).reshape(16)
+    kc = k if color_K is None else np.asarray(color_K, np.float32).reshape(16)
     eye = np.eye(4, dtype=np.float32).reshape(16)
+    ext = eye if depth_extrinsics is None else np.asarray(depth_extrinsics, np.float32).reshape(16)
     for i in range(16):
-        s.depthIntrinsics[i] = s.colorIntrinsics[i] = float(k[i])
-        s.depthExtrinsics[i] = s.colorExtrinsics[i] = float(eye[i])
+        s.depthIntrinsics[i] = float(k[i]); s.colorIntrinsics[i] = float(kc[i])
+        s.depthExtrinsics[i] = float(ext[i]); s.colorExtrinsics[i] = float(eye[i])
     return s
 
 
@@ -938,6 +942,38 @@ def image_resample_to_intensity(out, inp, stream=0):
 def image_interleave_texels(texels, depth, color, stream=0):
     """{depth f32 bits, colour RGBX8} per pixel: `texels` holds depth.numel() x 8 bytes"""
     check(lib.bf_image_interleave_texels(_p(texels), _p(depth), _p(color), depth.numel(), C.c_void_p(stream)))
+
+
+# --------------------------------------------------------------------------- depth registration (csrc/calibrator.hip)
+class ImageCalibrator:
+    """Python view of `bf_image_calibrator` (== the reference's CUDAImageCalibrator): re-renders a depth image into the colour camera.  width x height: the
+    depth image's size; `stream`: a hipStream_t (0: the null stream)."""
+
+    def __init__(self, width, height, stream=0):
+        self._h = C.c_void_p()
+        self.w, self.h = int(width), int(height)
+        check(lib.bf_image_calibrator_create(self.w, self.h, C.byref(self._h)))
+        if stream:
+            check(lib.bf_image_calibrator_set_stream(self._h, C.c_void_p(stream)))
+
+    def close(self):
+        if self._h:
+            lib.bf_image_calibrator_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def process(self, depth, color_intrinsics, depth_intrinsics_inv, depth_extrinsics, thresh_offset=0.012, thresh_lin=0.01):
+        """depth: float32 torch device tensor (h, w), replaced in place by the depth seen from the colour camera (-inf where nothing was drawn).
+        color_intrinsics: the colour camera's at the depth image's size; depth_extrinsics: depth camera -> colour camera (4x4 each)."""
+        assert tuple(depth.shape) == (self.h, self.w) and depth.is_contiguous()
+        check(lib.bf_image_calibrator_process(self._h, _p(depth), mat16(color_intrinsics), mat16(depth_intrinsics_inv), mat16(depth_extrinsics),
+                                              C.c_float(thresh_offset), C.c_float(thresh_lin)))
+        return depth
 
 
 # --------------------------------------------------------------------------- sensor-format ingest (csrc/sensoringest.hip)
@@ -1009,6 +1045,29 @@ class ImageManager:
 
     def set_store_texels(self, enable=True):
         check(lib.bf_image_manager_set_store_texels(self._h, int(enable)))
+
+    def set_camera_calibration(self, enable=True, thresh_offset=0.012, thresh_lin=0.01):
+        """s_bUseCameraCalibration: register every frame's depth to the colour camera at ingest (before the first frame).  Returns whether it is active:
+        a sensor with identity depth extrinsics has nothing to register and stays off."""
+        check(lib.bf_image_manager_set_camera_calibration(self._h, int(enable), C.c_float(thresh_offset), C.c_float(thresh_lin)))
+        return self.camera_calibration()
+
+    def camera_calibration(self):
+        a = C.c_int()
+        check(lib.bf_image_manager_get_camera_calibration(self._h, C.byref(a)))
+        return bool(a.value)
+
+    def depth_intrinsics(self):
+        """(K, K^-1) of the depth camera at integration resolution, 4x4 each, as the manager computed them"""
+        k, ki = (C.c_float * 16)(), (C.c_float * 16)()
+        check(lib.bf_image_manager_get_depth_intrinsics(self._h, k, ki))
+        return np.array(k[:], np.float32).reshape(4, 4), np.array(ki[:], np.float32).reshape(4, 4)
+
+    def sift_depth(self):
+        """(width, height, 4x4 intrinsics) of the depth image the SIFT keys sample: the colour camera's intrinsics while registration is active"""
+        w, h, k = C.c_uint32(), C.c_uint32(), (C.c_float * 16)()
+        check(lib.bf_image_manager_get_sift_depth(self._h, C.byref(w), C.byref(h), k))
+        return w.value, h.value, np.array(k[:], np.float32).reshape(4, 4)
 
     def reset(self):
         check(lib.bf_image_manager_reset(self._h))
@@ -1325,6 +1384,13 @@ class Pipeline:
         d = np.zeros((h.value, w.value), np.float32); c = np.zeros((h.value, w.value, 4), np.uint8)
         check(lib.bf_image_manager_get_integrate_frame_cpu(im, frame, d.ctypes.data_as(C.c_void_p), c.ctypes.data_as(C.c_void_p)))
         return d, c
+
+    def camera_calibration(self):
+        """whether the loop registers depth to the colour camera: gas.s_bUseCameraCalibration and a sensor with non-identity depth extrinsics"""
+        im = C.c_void_p(); a = C.c_int()
+        check(lib.bf_pipeline_get_image_manager(self._h, C.byref(im)))
+        check(lib.bf_image_manager_get_camera_calibration(im, C.byref(a)))
+        return bool(a.value)
 
     def bundler(self, which):
         ob = C.c_void_p(); b = C.c_void_p()

@@ -190,6 +190,11 @@ struct bf_image_manager {
     float* d_stageDepth = nullptr; uint8_t* d_stageColor = nullptr;
     int activeDepth = -1, activeColor = -1;
     uint32_t currFrame = 0;
+    // s_bUseCameraCalibration (bf_image_manager_set_camera_calibration): the calibrator exists only while active.  calibColorIntrinsics = the colour intrinsics at the
+    // depth image's size (m_SIFTdepthIntrinsics of CUDAImageManager.h:184-190), calibDepthIntrinsicsInv = the sensor's own (CUDAImageManager.cpp:80)
+    bf_image_calibrator* calib = nullptr;
+    float calibThreshOffset = 0.0f, calibThreshLin = 0.0f;
+    m44 calibColorIntrinsics, calibDepthIntrinsicsInv;
     size_t nInt() const { return (size_t)wInt * hInt; }
     // sensor-format ingest (bf_image_manager_process_raw*), allocated at its first use.  Device side: the uploaded u16 / RGB8 / coefficient bytes, the decoder's sample
     // planes and the converted frame - one set: every user is on `stream`, in order.  Host side: NSETS pinned staging slots (frame n copies into slot n % NSETS; the
@@ -254,6 +259,7 @@ int bf_image_manager_destroy(bf_image_manager* im) {
     bf_image_manager_reset(im);
     for (uint32_t k = 0; k < (im->scratch ? 1u : bf_image_manager::NSETS); ++k) { (void)hipFree(im->rawSet[k]); (void)hipFree(im->filtSet[k]); (void)hipFree(im->colSet[k]); }
     (void)hipFree(im->d_stageDepth); (void)hipFree(im->d_stageColor);
+    bf_image_calibrator_destroy(im->calib);
     {
         bf_image_manager::RawIngest& r = im->rawIn;
         (void)hipFree(r.d_depthU16); (void)hipFree(r.d_colourIn); (void)hipFree(r.d_planes); (void)hipFree(r.d_depth); (void)hipFree(r.d_rgbx);
@@ -278,6 +284,36 @@ int bf_image_manager_get_integrate_frame_texels(bf_image_manager* im, uint32_t f
     if (!im->storeTexels || frame >= im->currFrame || frame / bf_image_manager::SLAB >= im->texelSlabs.size()) return BF_OK;
     *d_texels = im->texelSlabs[frame / bf_image_manager::SLAB] + (size_t)(frame % bf_image_manager::SLAB) * im->nInt() * 8;
     return BF_OK;
+}
+// s_bUseCameraCalibration.  A sensor whose depth extrinsics are the identity switches the flag off (RGBDSensor::initializeDepthExtrinsics, RGBDSensor.cpp:126-131)
+int bf_image_manager_set_camera_calibration(bf_image_manager* im, int enable, float threshOffset, float threshLin) {
+    BF_REQUIRE(im, "null manager");
+    BF_REQUIRE(im->currFrame == 0, "set_camera_calibration after the first frame");
+    const m44 I = identity44();
+    const bool want = enable != 0 && !std::equal(I.e, I.e + 16, im->depthExtrinsics.e);
+    if (want) {
+        BF_REQUIRE(std::isfinite(threshOffset) && std::isfinite(threshLin), "the thresholds must be finite");
+        if (!im->calib) BF_TRY(bf_image_calibrator_create(im->sensor.depthWidth, im->sensor.depthHeight, &im->calib));
+        im->calibThreshOffset = threshOffset; im->calibThreshLin = threshLin;
+        im->calibColorIntrinsics = scaleIntrinsics(im->sensor.colorIntrinsics, im->sensor.depthWidth, im->sensor.depthHeight, im->sensor.colorWidth, im->sensor.colorHeight);
+        im->calibDepthIntrinsicsInv = inverse44(toM(im->sensor.depthIntrinsics));
+        im->siftDepthIntrinsics = im->calibColorIntrinsics;
+    } else {
+        bf_image_calibrator_destroy(im->calib); im->calib = nullptr;
+        im->siftDepthIntrinsics = toM(im->sensor.depthIntrinsics);
+    }
+    return BF_OK;
+}
+int bf_image_manager_get_camera_calibration(bf_image_manager* im, int* active) {
+    BF_REQUIRE(im && active, "null argument");
+    *active = im->calib ? 1 : 0;
+    return BF_OK;
+}
+// register the frame's raw depth (already in d_depthInputRaw) to the colour camera, in place, on the ingest stream  (CUDAImageManager.cpp:74-90)
+static int im_register_depth(bf_image_manager* im) {
+    BF_TRY(bf_image_calibrator_set_stream(im->calib, im->stream));
+    return bf_image_calibrator_process(im->calib, im->d_depthInputRaw, im->calibColorIntrinsics.e, im->calibDepthIntrinsicsInv.e, im->depthExtrinsics.e, im->calibThreshOffset,
+                                       im->calibThreshLin);
 }
 // see bf_image_manager::inputGuard: set k (0 / 1) is overwritten by frames of parity k; `hip_event` (or null) is recorded by whoever reads a frame's
 // input buffers on ANOTHER stream than the ingest's, after its last read
@@ -320,6 +356,11 @@ static int im_process(bf_image_manager* im, const float* depth, const uint8_t* c
     // images in three launches - erosion 1 straight from the caller's depth with the colour copies riding along, erosion 2, depth filter writing the stored frame too
     if (kind == hipMemcpyDeviceToDevice && im->onGPU && !im->storeTexels && nc == nd && sn.colorWidth == im->wInt && sn.colorHeight == im->hInt && sn.depthWidth == im->wInt &&
         sn.depthHeight == im->hInt && im->gbs.s_erodeSIFTdepth && im->gbs.s_depthFilter) {
+        if (im->calib) {                                    // registration needs the frame in a buffer of the manager's: one copy more, the erosion then reads that
+            BF_HIP_TRY(hipMemcpyAsync(im->d_depthInputRaw, depth, nd * 4, kind, st));
+            BF_TRY(im_register_depth(im));
+            depth = im->d_depthInputRaw;
+        }
         BF_TRY(bf_image_erode_depth_map_and_copy(im->d_depthInputFiltered, depth, 3, sn.depthWidth, sn.depthHeight, 0.05f, 0.3f, color, im->d_colorInput, frameColor, st));
         BF_TRY(bf_image_erode_depth_map(im->d_depthInputRaw, im->d_depthInputFiltered, 3, sn.depthWidth, sn.depthHeight, 0.05f, 0.3f, st));
         BF_TRY(bf_image_gauss_filter_depth_map2(im->d_depthInputFiltered, frameDepth, im->d_depthInputRaw, im->gbs.s_depthSigmaD, im->gbs.s_depthSigmaR, sn.depthWidth, sn.depthHeight, st));
@@ -335,6 +376,7 @@ static int im_process(bf_image_manager* im, const float* depth, const uint8_t* c
     else BF_TRY(bf_image_resample_uchar4(colorDst, im->wInt, im->hInt, im->d_colorInput, sn.colorWidth, sn.colorHeight, st));
     // ---- depth  (.cpp:66-112): two 7x7 erosions ping-pong (the twice-eroded map ends in d_depthInputRaw), then the range-gated Gaussian
     BF_HIP_TRY(hipMemcpyAsync(im->d_depthInputRaw, depth, nd * 4, kind, st));
+    if (im->calib) BF_TRY(im_register_depth(im));
     if (im->gbs.s_erodeSIFTdepth) {
         BF_TRY(bf_image_erode_depth_map(im->d_depthInputFiltered, im->d_depthInputRaw, 3, sn.depthWidth, sn.depthHeight, 0.05f, 0.3f, st));
         BF_TRY(bf_image_erode_depth_map(im->d_depthInputRaw, im->d_depthInputFiltered, 3, sn.depthWidth, sn.depthHeight, 0.05f, 0.3f, st));
@@ -2407,6 +2449,8 @@ int bf_pipeline_create(const bf_global_app_state* gas, const bf_global_bundling_
     int rc = bf_image_manager_create(gas->s_integrationWidth, gas->s_integrationHeight, gbs->s_widthSIFT, gbs->s_heightSIFT, sensor, gbs, 1, &p->im);
     // (bf_image_manager_set_store_texels - a third plane per stored frame, depth and colour interleaved for the fast voxel update - is not used here: measured no
     // gain, 680 vs 685 frames/s, gpurun r04l; since round 5 the batch's march writes the texels of its operators.)
+    if (!rc && gas->s_bUseCameraCalibration)
+        rc = bf_image_manager_set_camera_calibration(p->im, 1, gas->s_remappingDepthDiscontinuityThresOffset, gas->s_remappingDepthDiscontinuityThresLin);
     if (!rc) rc = bf_online_bundler_create(sensor, p->im, gas, gbs, &p->ob);
     bf_hash_params hp;                                          // CUDASceneRepHashSDF::parametersFromGlobalAppState :39-59
     memset(&hp, 0, sizeof hp);
@@ -2420,7 +2464,10 @@ int bf_pipeline_create(const bf_global_app_state* gas, const bf_global_bundling_
     hp.m_streamingInitialChunkListSize = gas->s_streamingInitialChunkListSize;
     if (!rc) rc = bf_scene_create(&hp, &p->scene);
     if (rc) { bf_pipeline_destroy(p); return rc; }
-    p->cam.fx = p->im->depthIntrinsics.e[0]; p->cam.fy = p->im->depthIntrinsics.e[5]; p->cam.mx = p->im->depthIntrinsics.e[2]; p->cam.my = p->im->depthIntrinsics.e[6];
+    {   // registered depth lives in the colour camera: integrate with its intrinsics (DepthSensing.cpp:285-288)
+        const m44& K = p->im->calib ? p->im->colorIntrinsics : p->im->depthIntrinsics;
+        p->cam.fx = K.e[0]; p->cam.fy = K.e[5]; p->cam.mx = K.e[2]; p->cam.my = K.e[6];
+    }
     p->cam.m_sensorDepthWorldMin = gas->s_renderDepthMin; p->cam.m_sensorDepthWorldMax = gas->s_renderDepthMax;      // DepthSensing.cpp:636-643
     p->cam.m_imageWidth = gas->s_integrationWidth; p->cam.m_imageHeight = gas->s_integrationHeight;
     for (auto& e : p->ev) BF_HIP_TRY(hipEventCreate(&e));
@@ -2704,6 +2751,8 @@ int bf_chunk_worker_create(const bf_global_app_state* gas, const bf_global_bundl
     w->siftIntrinsics = scaleIntrinsics(sensor->colorIntrinsics, gbs->s_widthSIFT, gbs->s_heightSIFT, sensor->colorWidth, sensor->colorHeight);
     w->siftIntrinsicsInv = inverse44(w->siftIntrinsics);
     int rc = bf_image_manager_create(gas->s_integrationWidth, gas->s_integrationHeight, gbs->s_widthSIFT, gbs->s_heightSIFT, sensor, gbs, 2, &w->im);
+    if (!rc && gas->s_bUseCameraCalibration)            // the worker's ingest sees the frames the main loop's does
+        rc = bf_image_manager_set_camera_calibration(w->im, 1, gas->s_remappingDepthDiscontinuityThresOffset, gas->s_remappingDepthDiscontinuityThresLin);
     if (!rc) rc = bf_bundler_create(gbs->s_submapSize + 1, gbs->s_maxNumKeysPerImage, w->siftIntrinsicsInv.e, w->im, 1, gas, gbs, &w->local);
     if (!rc) rc = bf_siftmgr_create(2, gbs->s_maxNumKeysPerImage, &w->fuseMgr);
     if (rc) { bf_chunk_worker_destroy(w); return rc; }

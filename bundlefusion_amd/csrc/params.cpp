@@ -90,6 +90,7 @@ void readApp(Reader& r, bf_global_app_state& g) {
     r.u("s_rayCastWidth", g.s_rayCastWidth); r.u("s_rayCastHeight", g.s_rayCastHeight);
     r.f("s_SDFRayIncrementFactor", g.s_SDFRayIncrementFactor); r.f("s_SDFRayThresSampleDistFactor", g.s_SDFRayThresSampleDistFactor);
     r.f("s_SDFRayThresDistFactor", g.s_SDFRayThresDistFactor); r.b("s_SDFUseGradients", g.s_SDFUseGradients);
+    r.f("s_remappingDepthDiscontinuityThresOffset", g.s_remappingDepthDiscontinuityThresOffset); r.f("s_remappingDepthDiscontinuityThresLin", g.s_remappingDepthDiscontinuityThresLin);
     if (auto* s = r.find("s_numSolveFramesBeforeExit")) g.s_numSolveFramesBeforeExit = (uint32_t)strtol(s->c_str(), nullptr, 10);   // may be -1
     if (auto* s = r.find("s_binaryDumpSensorFile")) {                                    // a quoted string
         std::string v = *s;
@@ -149,6 +150,7 @@ int bf_global_app_state_default(bf_global_app_state* g) {           // zParamete
     g->s_numSolveFramesBeforeExit = 30;
     g->s_rayCastWidth = 320; g->s_rayCastHeight = 240;
     g->s_SDFRayIncrementFactor = 0.8f; g->s_SDFRayThresSampleDistFactor = 50.5f; g->s_SDFRayThresDistFactor = 50.0f; g->s_SDFUseGradients = 0;
+    g->s_remappingDepthDiscontinuityThresOffset = 0.012f; g->s_remappingDepthDiscontinuityThresLin = 0.01f;
     snprintf(g->s_binaryDumpSensorFile, sizeof g->s_binaryDumpSensorFile, "%s", "../data/sequence.sens");
     return BF_OK;
 }

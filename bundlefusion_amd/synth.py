@@ -169,13 +169,13 @@ def _ray_aabb(o, d, lo, hi):
     return tnear, tfar, axis_n, axis_f
 
 
-def scene_room(k, width=640, height=480, frames_per_loop=1800, bob=0.0):
-    """S2 frame k: depth f32 [H,W], colour u8 [H,W,4], camera-to-world 4x4 f32, intrinsics."""
+def scene_room_at(T, K, width=640, height=480):
+    """S2 seen from camera-to-world matrix T through the pinhole K (a dict as intrinsics() returns): depth f32 [H,W],
+    colour u8 [H,W,4], T as 4x4 f32, K.  The camera need not lie on the trajectory (a second camera of a sensor rig)."""
     global _BOXES
     if _BOXES is None:
         _BOXES = _clutter_boxes()
-    K = intrinsics(width, height)
-    T = trajectory_pose(k, frames_per_loop, bob=bob).astype(np.float64)
+    T = np.asarray(T).astype(np.float64)
     xs, ys = np.meshgrid(np.arange(width, dtype=np.float64), np.arange(height, dtype=np.float64))
     dc = np.stack([(xs - K["mx"]) / K["fx"], (ys - K["my"]) / K["fy"], np.ones_like(xs)], axis=-1)
     d = dc @ T[:3, :3].T
@@ -203,6 +203,11 @@ def scene_room(k, width=640, height=480, frames_per_loop=1800, bob=0.0):
         color[m] = _rgbx(u[m], v[m], int(s))
     depth = best_t          # camera-space z == t because dc.z == 1
     return _finish_depth(depth), color, T.astype(np.float32), K
+
+
+def scene_room(k, width=640, height=480, frames_per_loop=1800, bob=0.0):
+    """S2 frame k: depth f32 [H,W], colour u8 [H,W,4], camera-to-world 4x4 f32, intrinsics."""
+    return scene_room_at(trajectory_pose(k, frames_per_loop, bob=bob), intrinsics(width, height), width, height)
 
 
 # ---------------------------------------------------------------- parallel rendering of a stream

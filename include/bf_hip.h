@@ -609,6 +609,28 @@ typedef struct bf_jpeg_info {
 BF_API int bf_jpeg_reconstruct_device(const bf_jpeg_info* info, const int16_t* d_coefficients, uint8_t* d_planes, uint8_t* d_rgbxOut, void* hip_stream);
 
 /* ------------------------------------------------------------------------- */
+/* CUDAImageCalibrator:  CUDAImageCalibrator.h:1-40, .cpp:8-64                */
+/* (csrc/calibrator.hip) - registers a depth image to the colour camera       */
+/* ------------------------------------------------------------------------- */
+/* The reference renders the depth image as a triangle mesh into the colour camera with Direct3D (DX11RGBDRenderer::RenderDepthMap,
+ * Shaders/RGBDRenderer.hlsl).  Here the same stages - one quad per pixel with the shader's discontinuity test, the shader's vertex transform
+ * in binary32, a top-left-rule rasteriser at 1/256 pixel - are two kernels on the caller's stream; DESIGN.md "Depth registration" is the definition,
+ * with its three departures (pixel centres at integer coordinates, the value written is the depth in the COLOUR camera, triangles that cross the
+ * near / far plane 0.1 m / 20 m are dropped whole).  Where several triangles cover a pixel the smallest depth wins; uncovered pixels are -inf. */
+typedef struct bf_image_calibrator bf_image_calibrator;
+/* OnD3D11CreateDevice(device, width, height)  .cpp:16-37.  width x height: the depth image's (and the result's) size */
+BF_API int bf_image_calibrator_create(uint32_t width, uint32_t height, bf_image_calibrator** out);
+/* OnD3D11DestroyDevice()  .cpp:8-14 */
+BF_API int bf_image_calibrator_destroy(bf_image_calibrator* c);
+BF_API int bf_image_calibrator_set_stream(bf_image_calibrator* c, void* hip_stream);
+/* process(context, d_depth, colorIntrinsics, depthIntrinsicsInv, depthExtrinsics)  .cpp:39-64, minus the D3D context.  d_depth (width * height floats,
+ * metres, -inf invalid) is replaced in place.  colorIntrinsics: the colour camera's at the DEPTH image's size; depthExtrinsics: depth camera -> colour
+ * camera; the matrices are row-major host arrays.  threshOffset / threshLin: s_remappingDepthDiscontinuityThresOffset / ...Lin (the reference reads them
+ * from GlobalAppState, :56).  Asynchronous: two launches, no host synchronisation. */
+BF_API int bf_image_calibrator_process(bf_image_calibrator* c, float* d_depth, const float colorIntrinsics[16], const float depthIntrinsicsInv[16],
+                                       const float depthExtrinsics[16], float threshOffset, float threshLin);
+
+/* ------------------------------------------------------------------------- */
 /* Marching cubes over the voxel hash:                                        */
 /* DepthSensing/CUDAMarchingCubesHashSDF.h:8-58, .cpp, CUDAMarchingCubesSDF.cu, */
 /* MarchingCubesSDFUtil.h:9-287 (a consumer of getHashData(): it reads the raw  */

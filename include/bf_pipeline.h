@@ -48,6 +48,8 @@ typedef struct bf_global_app_state {
     uint32_t s_rayCastWidth, s_rayCastHeight;
     float s_SDFRayIncrementFactor, s_SDFRayThresSampleDistFactor, s_SDFRayThresDistFactor;
     int32_t s_SDFUseGradients;
+    /* depth registration (CUDAImageCalibrator.cpp:56): a quad of the depth mesh is dropped when its depths spread more than Offset + Lin * mid-depth */
+    float s_remappingDepthDiscontinuityThresOffset, s_remappingDepthDiscontinuityThresLin;
 } bf_global_app_state;
 
 typedef struct bf_global_bundling_state {
@@ -118,6 +120,13 @@ BF_API int bf_image_manager_set_input_guard(bf_image_manager* im, uint32_t set, 
  * made once at ingest instead of once per operator on the frame.  Before the first frame; needs storeFramesOnGPU.  _get_..._texels returns null when off. */
 BF_API int bf_image_manager_set_store_texels(bf_image_manager* im, int enable);
 BF_API int bf_image_manager_get_integrate_frame_texels(bf_image_manager* im, uint32_t frame, const void** d_texels);
+/* s_bUseCameraCalibration (CUDAImageManager.cpp:74-90): register every frame's depth to the colour camera (bf_image_calibrator_process, bf_hip.h) on the
+ * ingest stream, in place on the frame's raw depth, before the first erosion - in all five forms of process().  Before the first frame.  As in
+ * RGBDSensor::initializeDepthExtrinsics (RGBDSensor.cpp:126-131) a sensor whose depthExtrinsics are the identity has nothing to register: *active stays 0
+ * whatever was asked, and the ingest is the one without this call.  While active, _get_sift_depth reports the colour intrinsics scaled to the depth size
+ * (CUDAImageManager.h:184-190) and bf_pipeline integrates with the colour intrinsics scaled to the integration size (DepthSensing.cpp:285-288). */
+BF_API int bf_image_manager_set_camera_calibration(bf_image_manager* im, int enable, float threshOffset, float threshLin);
+BF_API int bf_image_manager_get_camera_calibration(bf_image_manager* im, int* active);
 BF_API int bf_image_manager_reset(bf_image_manager* im);
 /* process()  .cpp:22-158.  h_depth = sensor->getDepthFloat() (metres, -inf invalid), h_colorRGBX = getColorRGBX().
  * *gotFrame = 0 when the frame capacity (s_maxNumImages * s_submapSize) is reached.

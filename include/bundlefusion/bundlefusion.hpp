@@ -482,6 +482,26 @@ private:
     bf_rgbd_sensor_desc m_desc;
 };
 
+// ---- CUDAImageCalibrator (CUDAImageCalibrator.h:1-40): re-renders a depth image into the colour camera (bf_image_calibrator, bf_hip.h).  No D3D device or context:
+// the reference's OnD3D11CreateDevice(device, w, h) / process(context, ...) lose their first argument.  The thresholds are GlobalAppState's, as in .cpp:56.
+class CUDAImageCalibrator {
+public:
+    CUDAImageCalibrator() {}
+    ~CUDAImageCalibrator() { OnD3D11DestroyDevice(); }
+    CUDAImageCalibrator(const CUDAImageCalibrator&) = delete;
+    void OnD3D11CreateDevice(unsigned int width, unsigned int height) { OnD3D11DestroyDevice(); check(bf_image_calibrator_create(width, height, &m_h)); }
+    void OnD3D11DestroyDevice() { if (m_h) bf_image_calibrator_destroy(m_h); m_h = nullptr; }
+    void process(float* d_depth, const mat4f& colorIntrinsics, const mat4f& depthIntrinsicsInv, const mat4f& depthExtrinsics) {
+        if (!m_h) throw std::runtime_error("CUDAImageCalibrator::process before OnD3D11CreateDevice");
+        check(bf_image_calibrator_process(m_h, d_depth, colorIntrinsics.m, depthIntrinsicsInv.m, depthExtrinsics.m,
+                                          GlobalAppState::get().s_remappingDepthDiscontinuityThresOffset, GlobalAppState::get().s_remappingDepthDiscontinuityThresLin));
+    }
+    void setStream(void* hipStream) { check(bf_image_calibrator_set_stream(m_h, hipStream)); }
+    bf_image_calibrator* handle() const { return m_h; }
+private:
+    bf_image_calibrator* m_h = nullptr;
+};
+
 // ---- CUDAImageManager (CUDAImageManager.h:10-337)
 class CUDAImageManager {
 public:
@@ -509,7 +529,11 @@ public:
     CUDAImageManager(unsigned int widthIntegration, unsigned int heightIntegration, unsigned int widthSIFT, unsigned int heightSIFT, RGBDSensor* sensor,
                      bool storeFramesOnGPU = false) : m_sensor(sensor) {      // default as CUDAImageManager.h:140; pass true to keep every frame resident in HBM (what bf_pipeline does)
         check(bf_image_manager_create(widthIntegration, heightIntegration, widthSIFT, heightSIFT, &sensor->desc(), &GlobalBundlingState::get(), storeFramesOnGPU, &m_h));
+        const GlobalAppState& gas = GlobalAppState::get();          // CUDAImageManager.cpp:74: the flag is read from the singleton
+        if (gas.s_bUseCameraCalibration)
+            check(bf_image_manager_set_camera_calibration(m_h, 1, gas.s_remappingDepthDiscontinuityThresOffset, gas.s_remappingDepthDiscontinuityThresLin));
     }
+    bool usesCameraCalibration() const { int a = 0; check(bf_image_manager_get_camera_calibration(m_h, &a)); return a != 0; }
     ~CUDAImageManager() { bf_image_manager_destroy(m_h); }
     CUDAImageManager(const CUDAImageManager&) = delete;
     void reset() { check(bf_image_manager_reset(m_h)); }

@@ -2,7 +2,9 @@
 optimised trajectory against the poses stored in the file (SensorDataReader::evaluateTrajectory).
 
 usage: python tools/run_sens.py sequence.sens [--voxel 0.01] [--app zParametersDefault.txt] [--bundling zParametersBundlingDefault.txt]
-                                [--ingest host|device] [--decode-threads N]
+                                [--ingest host|device] [--decode-threads N] [--camera-calibration]
+--camera-calibration: s_bUseCameraCalibration = true - register every frame's depth to the colour camera with the extrinsics and intrinsics of the file's
+header (a file whose depth extrinsics are the identity has nothing to register; the line below says whether it is active).
 --ingest host (default): frames are decoded on the host and handed over as host buffers (the PCIe path of bf_pipeline_process_frame).
 --ingest device: sensordata.SensPlayer - N threads (default 4, at most 12) read, inflate and entropy-decode ahead, the u16 depth and the RGB8 / JPEG
 coefficients go up the bus and are converted / reconstructed on the device (bf_pipeline_process_frame_raw_decoded).  Same results, bit for bit.
@@ -32,6 +34,7 @@ def main():
     ap.add_argument("--ingest", choices=("host", "device"), default="host", help="where frames are converted to float depth / RGBX")
     ap.add_argument("--decode-threads", type=int, default=4, help="decode-ahead threads of --ingest device (1 .. 12)")
     ap.add_argument("--decoder", choices=("auto", "builtin"), default="auto", help="--ingest host: auto decodes JPEG / PNG with Pillow where it is installed, builtin with the library's decoder")
+    ap.add_argument("--camera-calibration", action="store_true", help="s_bUseCameraCalibration = true (a parameter file given with --app may set it as well)")
     ap.add_argument("--save", default=None, help="write a copy of the file with the optimised trajectory (SensorDataReader::saveToFile)")
     a = ap.parse_args()
     sd = sdm.SensorData(a.sens, use_pillow=a.ingest == "host" and a.decoder == "auto")        # (the player's workers decode with the library's own decoder)
@@ -45,9 +48,12 @@ def main():
     if a.voxel: gas.s_SDFVoxelSize = a.voxel
     if a.buckets: gas.s_hashNumBuckets = a.buckets
     if a.blocks: gas.s_hashNumSDFBlocks = a.blocks
+    if a.camera_calibration: gas.s_bUseCameraCalibration = 1
     if n > gbs.s_maxNumImages * gbs.s_submapSize:          # SensorDataReader.cpp:65-67
         raise SystemExit("sens file #frames = %d, please change param file to accommodate" % n)
     p = bf.capi.Pipeline(gas, gbs, desc)
+    print("camera calibration: %s" % ("registering depth to the colour camera" if p.camera_calibration() else
+                                      "asked for, but the depth extrinsics are the identity: off" if gas.s_bUseCameraCalibration else "off"))
     t0 = time.time()
     keep = []                                               # the last few host frames stay alive while their upload may be in flight
     if a.ingest == "device":
