@@ -68,6 +68,7 @@ class DepthCameraData(C.Structure):
 
 
 SCENE_BATCH_MAX = 12
+SCENE_OP_INTEGRATE, SCENE_OP_DEINTEGRATE, SCENE_OP_REINTEGRATE = 0, 1, 2      # BF_SCENE_OP_* (bf_hip.h)
 
 
 class SceneBatchOp(C.Structure):
@@ -248,7 +249,7 @@ class SceneRepHashSDF:
         assert 1 <= len(ops) <= SCENE_BATCH_MAX
         arr = (SceneBatchOp * len(ops))()
         for o, (kind, T0, T1, depth, color) in zip(arr, ops):
-            o.kind = {"in": 0, "de": 1, "re": 2}.get(kind, kind)
+            o.kind = {"in": SCENE_OP_INTEGRATE, "de": SCENE_OP_DEINTEGRATE, "re": SCENE_OP_REINTEGRATE}.get(kind, kind)
             o.T0[:] = np.asarray(T0, np.float32).reshape(16).tolist()
             o.T1[:] = np.asarray(T1 if T1 is not None else T0, np.float32).reshape(16).tolist()
             o.data = self._data(depth, color)

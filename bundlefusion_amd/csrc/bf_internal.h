@@ -53,6 +53,8 @@ void set_error(const char* fmt, ...);
         }                                                          \
     } while (0)
 
+#define BF_TRY(expr) do { int _rc = (expr); if (_rc != BF_OK) return _rc; } while (0)
+
 inline unsigned div_up(unsigned a, unsigned b) { return (a + b - 1) / b; }
 
 bool jpeg_on_device(const bf_jpeg_info& info);      // the sampling layouts bf_jpeg_reconstruct_device takes (sensoringest.hip)

@@ -32,8 +32,6 @@
 
 using namespace bf;
 
-#define BF_TRY(expr) do { int _rc = (expr); if (_rc != BF_OK) return _rc; } while (0)
-
 namespace {
 
 const float NINF = -std::numeric_limits<float>::infinity();

@@ -11,13 +11,11 @@
 #include <algorithm>
 #include <atomic>
 #include <cmath>
-#include <condition_variable>
 #include <cstring>
 #include <deque>
 #include <fstream>
 #include <limits>
 #include <list>
-#include <mutex>
 #include <thread>
 #include <chrono>
 #include <vector>
@@ -28,10 +26,9 @@
 #include "bf_device.h"
 #include "bf_internal.h"
 #include "bf_se3.h"
+#include "volume_queue.h"
 
 using namespace bf;
-
-#define BF_TRY(expr) do { int _rc = (expr); if (_rc != BF_OK) return _rc; } while (0)
 
 namespace {
 
@@ -2123,26 +2120,8 @@ struct bf_pipeline {
     hipStream_t sPair[2] = {nullptr, nullptr};      // pair stages of consecutive frames side by side (bf_online_bundler_set_pair_streams)
     static const int NEV = 8;
     hipEvent_t evIngest[NEV] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // ring, indexed by frame
-    // The volume stream is fed by its own host thread: the main thread decides WHAT to integrate (TrajectoryManager lists, poses)
-    // and posts commands; the worker issues the launches (three per operator + the event operations: 13 us of HIP calls per operator,
-    // 12 % of the wall time), so they do not serialize with the ~60 launches of the detect and bundling streams on one CPU thread.
-    struct VolCmd { int kind; bf_depth_camera_data data; const void* texels; float T0[16], T1[16]; int waitEv; };   // kind: 0 integrate, 1 de-integrate, 2 fused re-integrate, 3 GC, 4 flush
-    // Batched volume operators (round 5, bf_scene_run_batch): the volume thread collects a frame's operators - the integration of the previous frame, which
-    // arrives last in that frame's body, and this frame's re-integrations - and issues them as ONE batch when the frame's garbage collection arrives
-    // (DepthSensing.cpp:854-902 order kept: ..., integrate(k-1), fixes(k), GC(k), integrate(k), ...); a flush command (every accessor, bf_pipeline_synchronize)
-    // issues what is pending.  Per batch: four launches and one pass over the touched blocks instead of 3 launches and one pass per operator.
-    bool volBatching = true;
-    std::vector<VolCmd> volPending;                // worker-thread only
-    static const size_t MAX_QUEUE = 48;          // back-pressure: the volume thread may lag the bundling thread by a few frames at most
-    std::thread worker;
-    std::mutex mu;
-    std::condition_variable cvWork, cvIdle;
-    std::deque<VolCmd> queue;
-    bool stop = false, busy = false;
-    int workerError = BF_OK;
-    std::string workerMessage;
+    VolumeQueue vol;      // the volume stream is fed by its own host thread (volume_queue.h): plIntegrate / plReintegrate post typed commands, every accessor drains
     uint32_t numIntegrate = 0, numDeIntegrate = 0;
-    double volBusy = 0.0, volCommands = 0.0;      // the volume thread: seconds spent issuing operators (HIP API calls), operators issued (bf_pipeline_get_volume_thread_profile)
     // wall time the calling thread spent in each part of plFrame, accumulated (bf_pipeline_get_host_profile): where the frame loop's
     // critical path lies without a profiler.  [0] enqueue of the previous frame's matching chain, [1] ingest + detection enqueue,
     // [2] re-integration commands, [3] wait for the matching result + host logic, [4] integration command, [5] solves, [6] ingest wait, [7] frames
@@ -2159,101 +2138,22 @@ struct bf_pipeline {
 
 namespace {
 
-int volExecute(bf_pipeline* p, const bf_pipeline::VolCmd& c) {                                     // DepthSensing.cpp:723-762
-    if (c.kind == 3) return bf_scene_garbage_collect(p->scene);
-    if (c.waitEv >= 0) BF_TRY(bf_scene_wait_event(p->scene, p->evIngest[c.waitEv]));
-    if (c.texels) BF_TRY(bf_scene_set_frame_texels(p->scene, c.texels));
-    if (c.kind == 0) return bf_scene_integrate(p->scene, c.T0, &c.data, &p->cam, nullptr);
-    if (c.kind == 1) return bf_scene_deintegrate(p->scene, c.T0, &c.data, &p->cam, nullptr);
-    return bf_scene_reintegrate(p->scene, c.T0, c.T1, &c.data, &p->cam);
-}
-
-int volSubmitPending(bf_pipeline* p) {
-    std::vector<bf_pipeline::VolCmd>& q = p->volPending;
-    if (q.empty()) return BF_OK;
-    bf_scene_batch_op ops[BF_SCENE_BATCH_MAX];
-    const uint32_t n = (uint32_t)q.size();
-    for (uint32_t k = 0; k < n; ++k) {
-        const bf_pipeline::VolCmd& c = q[k];
-        ops[k].kind = c.kind; ops[k].reserved = 0;
-        memcpy(ops[k].T0, c.T0, 64); memcpy(ops[k].T1, c.kind == 2 ? c.T1 : c.T0, 64);
-        ops[k].data = c.data; ops[k].d_texels = c.texels;
-        ops[k].wait_event = c.waitEv >= 0 ? (void*)p->evIngest[c.waitEv] : nullptr;
-    }
-    q.clear();
-    return bf_scene_run_batch(p->scene, ops, n, &p->cam);
-}
-
-// the volume thread's handling of one command (see bf_pipeline::volBatching)
-int volHandle(bf_pipeline* p, const bf_pipeline::VolCmd& c) {
-    if (!p->volBatching) return c.kind == 4 ? BF_OK : volExecute(p, c);
-    if (c.kind <= 2) {
-        p->volPending.push_back(c);
-        return p->volPending.size() == BF_SCENE_BATCH_MAX ? volSubmitPending(p) : BF_OK;
-    }
-    BF_TRY(volSubmitPending(p));
-    return c.kind == 3 ? bf_scene_garbage_collect(p->scene) : BF_OK;
-}
-
-void volWorker(bf_pipeline* p) {
-    for (;;) {
-        bf_pipeline::VolCmd c;
-        {
-            std::unique_lock<std::mutex> lk(p->mu);
-            p->cvWork.wait(lk, [p] { return p->stop || !p->queue.empty(); });
-            if (p->queue.empty()) return;             // stop requested and drained
-            c = p->queue.front(); p->queue.pop_front();
-            p->busy = true;
-        }
-        const double tv = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-        const int rc = volHandle(p, c);
-        const double dv = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - tv;
-        {
-            std::lock_guard<std::mutex> lk(p->mu);
-            p->volBusy += dv; p->volCommands += 1.0;
-            if (rc != BF_OK && p->workerError == BF_OK) { p->workerError = rc; p->workerMessage = bf_last_error(); }
-            p->busy = false;
-            p->cvIdle.notify_all();
-        }
-    }
-}
-
-int volPost(bf_pipeline* p, int kind, uint32_t frame, const float* T0, const float* T1, int waitEv) {
-    bf_pipeline::VolCmd c;
-    c.kind = kind; c.waitEv = waitEv;
-    c.data.d_depthData = nullptr; c.data.d_colorData = nullptr;
-    c.texels = nullptr;
-    if (kind < 3) {
-        BF_TRY(bf_image_manager_get_integrate_frame_gpu(p->im, frame, &c.data.d_depthData, &c.data.d_colorData));   // resolved on the calling thread
-        BF_TRY(bf_image_manager_get_integrate_frame_texels(p->im, frame, &c.texels));
-    }
-    if (T0) memcpy(c.T0, T0, 64);
+// a volume operator on frame `frame`: its pointers, texels and event are resolved here, on the calling thread
+int volPost(bf_pipeline* p, VolumeQueue::Op op, uint32_t frame, const float* T0, const float* T1, int waitEv) {
+    VolumeQueue::Cmd c;
+    c.op = op;
+    BF_TRY(bf_image_manager_get_integrate_frame_gpu(p->im, frame, &c.data.d_depthData, &c.data.d_colorData));
+    BF_TRY(bf_image_manager_get_integrate_frame_texels(p->im, frame, &c.texels));
+    memcpy(c.T0, T0, 64);
     if (T1) memcpy(c.T1, T1, 64);
-    if (p->timings) return volExecute(p, c);        // stage timings are taken with everything issued from the calling thread
-    std::unique_lock<std::mutex> lk(p->mu);
-    p->cvIdle.wait(lk, [p] { return p->queue.size() < bf_pipeline::MAX_QUEUE || p->workerError != BF_OK; });
-    if (p->workerError != BF_OK) { set_error("volume worker: %s", p->workerMessage.c_str()); return p->workerError; }
-    p->queue.push_back(c);
-    p->cvWork.notify_one();
-    return BF_OK;
-}
-
-int volDrain(bf_pipeline* p) {
-    std::unique_lock<std::mutex> lk(p->mu);
-    if (p->worker.joinable() && p->workerError == BF_OK) {      // what the volume thread holds back for the next batch is issued now
-        bf_pipeline::VolCmd f; memset(&f, 0, sizeof f); f.kind = 4; f.waitEv = -1;
-        p->queue.push_back(f);
-        p->cvWork.notify_one();
-    }
-    p->cvIdle.wait(lk, [p] { return p->queue.empty() && !p->busy; });
-    if (p->workerError != BF_OK) { set_error("volume worker: %s", p->workerMessage.c_str()); return p->workerError; }
-    return BF_OK;
+    if (waitEv >= 0) c.waitEvent = p->evIngest[waitEv];
+    return p->vol.post(c);
 }
 
 int plIntegrate(bf_pipeline* p, uint32_t frameIdx, const float* T, bool de, int waitEv = -1) {
     if (!p->gas.s_integrationEnabled) return BF_OK;
     if (de) p->numDeIntegrate++; else p->numIntegrate++;
-    return volPost(p, de ? 1 : 0, frameIdx, T, nullptr, waitEv);
+    return volPost(p, de ? VolumeQueue::Op::Deintegrate : VolumeQueue::Op::Integrate, frameIdx, T, nullptr, waitEv);
 }
 
 int plReintegrate(bf_pipeline* p) {                                                                 // :854-902
@@ -2272,7 +2172,7 @@ int plReintegrate(bf_pipeline* p) {                                             
         if (found) {
             if (newT[0] == NINF) continue;          // every candidate was invalidated meanwhile: no volume operation now; get_top re-typed them Integrated, so the next list update de-integrates them at their old poses
             if (p->gas.s_integrationEnabled) {          // deIntegrate(old) + integrate(new) (:885-886) as one fused pass over the volume
-                BF_TRY(volPost(p, 2, frameIdx, oldT, newT, -1));
+                BF_TRY(volPost(p, VolumeQueue::Op::Reintegrate, frameIdx, oldT, newT, -1));
                 p->numDeIntegrate++; p->numIntegrate++;
             }
             BF_TRY(bf_trajectory_manager_confirm_integration(tm, frameIdx));
@@ -2282,8 +2182,9 @@ int plReintegrate(bf_pipeline* p) {                                             
     }
     // the frame boundary closes the volume thread's batch: the garbage collection does, or (collection disabled) a flush command - a batch is one frame's operators
     // whatever the settings, and nothing stays pending across frames
-    BF_TRY(volPost(p, p->gas.s_garbageCollectionEnabled ? 3 : 4, 0, nullptr, nullptr, -1));
-    return BF_OK;
+    VolumeQueue::Cmd boundary;
+    boundary.op = p->gas.s_garbageCollectionEnabled ? VolumeQueue::Op::Collect : VolumeQueue::Op::Flush;
+    return p->vol.post(boundary);
 }
 
 // everything of the frame loop after the ingest, for frame `frame` (got: a new frame, as opposed to an iteration after the
@@ -2530,18 +2431,14 @@ int bf_pipeline_create(const bf_global_app_state* gas, const bf_global_bundling_
     if (const char* e = getenv("BF_PIPELINE_TRACE")) p->tracePath = e;
     int dev = 0;
     BF_HIP_TRY(hipGetDevice(&dev));
-    p->worker = std::thread([p, dev] { (void)hipSetDevice(dev); volWorker(p); });
+    p->vol.start(p->scene, p->cam, dev);
     *out = p;
     return BF_OK;
 }
 
 int bf_pipeline_destroy(bf_pipeline* p) {
     if (!p) return BF_OK;
-    if (p->worker.joinable()) {
-        { std::lock_guard<std::mutex> lk(p->mu); p->stop = true; }
-        p->cvWork.notify_all();
-        p->worker.join();
-    }
+    p->vol.stop();
     (void)hipDeviceSynchronize();
     if (!p->tracePath.empty() && !p->trace.empty()) {
         if (FILE* f = fopen(p->tracePath.c_str(), "a")) {
@@ -2596,17 +2493,17 @@ int bf_pipeline_get_solve_lag(bf_pipeline* p, uint32_t* lag) { BF_REQUIRE(p && l
 int bf_pipeline_set_comm(bf_pipeline* p, bf_comm* comm, uint32_t capacity_keys) {
     BF_REQUIRE(p, "null pipeline");
     BF_TRY(plFlush(p));
-    BF_TRY(volDrain(p));
+    BF_TRY(p->vol.drain());
     return bf_scene_set_alloc_comm(p->scene, comm, capacity_keys);
 }
 
-// Batched volume operators on / off (on by default; see bf_pipeline::volBatching).  Off: every operator is issued on its own (bf_scene_integrate / _deintegrate /
+// Batched volume operators on / off (on by default; see bf::VolumeQueue).  Off: every operator is issued on its own (bf_scene_integrate / _deintegrate /
 // _reintegrate), as before round 5 - same volume either way.
 int bf_pipeline_set_volume_batching(bf_pipeline* p, int enable) {
     BF_REQUIRE(p, "null pipeline");
     BF_TRY(plFlush(p));
-    BF_TRY(volDrain(p));
-    p->volBatching = enable != 0;
+    BF_TRY(p->vol.drain());
+    p->vol.setBatching(enable != 0);
     return BF_OK;
 }
 
@@ -2647,7 +2544,7 @@ int bf_pipeline_process_end_of_sequence(bf_pipeline* p, uint32_t* numActiveOpera
 int bf_pipeline_synchronize(bf_pipeline* p) {
     BF_REQUIRE(p, "null pipeline");
     BF_TRY(plFlush(p));
-    BF_TRY(volDrain(p));
+    BF_TRY(p->vol.drain());
     BF_HIP_TRY(hipStreamSynchronize(p->sIngest));
     BF_HIP_TRY(hipStreamSynchronize(p->sDetect));
     for (auto st : p->sPair) if (st) BF_HIP_TRY(hipStreamSynchronize(st));
@@ -2659,7 +2556,7 @@ int bf_pipeline_synchronize(bf_pipeline* p) {
 int bf_pipeline_get_scene(bf_pipeline* p, bf_scene** out) {         // the volume thread is drained first: the caller may use the scene directly
     BF_REQUIRE(p && out, "null argument");
     BF_TRY(plFlush(p));
-    BF_TRY(volDrain(p));
+    BF_TRY(p->vol.drain());
     *out = p->scene;
     return BF_OK;
 }
@@ -2705,18 +2602,16 @@ int bf_pipeline_get_host_profile(bf_pipeline* p, double out[8], int reset) {
 int bf_pipeline_get_volume_thread_profile(bf_pipeline* p, double* busySeconds, double* commands, int reset) {
     BF_REQUIRE(p, "null pipeline");
     BF_TRY(plFlush(p));
-    BF_TRY(volDrain(p));
-    std::lock_guard<std::mutex> lk(p->mu);
-    if (busySeconds) *busySeconds = p->volBusy;
-    if (commands) *commands = p->volCommands;
-    if (reset) { p->volBusy = 0.0; p->volCommands = 0.0; }
+    BF_TRY(p->vol.drain());
+    p->vol.profile(busySeconds, commands, reset != 0);
     return BF_OK;
 }
 int bf_pipeline_enable_timings(bf_pipeline* p, int enable) {
     BF_REQUIRE(p, "null pipeline");
     BF_TRY(plFlush(p));
-    BF_TRY(volDrain(p));
+    BF_TRY(p->vol.drain());
     p->timings = enable != 0;
+    p->vol.setInline(p->timings);      // stage timings are taken with everything issued from the calling thread
     return BF_OK;
 }
 int bf_pipeline_get_last_timing(bf_pipeline* p, bf_frame_timing* out) { BF_REQUIRE(p && out, "null argument"); *out = p->last; return BF_OK; }

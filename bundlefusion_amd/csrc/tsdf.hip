@@ -1964,16 +1964,54 @@ int prepWaits(bf_scene* s, hipStream_t ps) {
     return BF_OK;
 }
 
-// One operator = preparation (allocation + block list) -> voxel update.  kind 0 integrate(f), 1 de-integrate(f), 2 fused: de-integrate(fo) +
+// The slot protocol of a single operator and of a batch alike.  A slot is list buffer b (with its texel set), the stream `ps` its preparation is issued on and
+// the scene's device view `dv` with that buffer's list; with overlap enabled the preparation goes to the prep stream into the NEXT buffer.
+struct OpSlot { int b; hipStream_t ps; Dev dv; };
+OpSlot openSlot(const bf_scene* s) {
+    const int b = s->overlap ? (s->cur + 1) % s->NB : s->cur;
+    return {b, s->overlap ? s->prep : s->stream, devBuf(s, b)};
+}
+// the preparation is complete on `ps`: the voxel update on the main stream follows it
+int publishPrep(bf_scene* s, int b, hipStream_t ps) {
+    if (s->overlap) {
+        BF_HIP_TRY(hipEventRecord(s->evPrep[b], ps));
+        BF_HIP_TRY(hipStreamWaitEvent(s->stream, s->evPrep[b], 0));
+    }
+    return BF_OK;
+}
+// the timed launches begin (bf_scene_set_timing): they cover `ops` integrate / de-integrate operations sampling `images` frames
+int beginTimed(bf_scene* s, uint32_t ops, uint32_t images, std::pair<hipEvent_t, hipEvent_t>*& ev) {
+    if (!s->timing) return BF_OK;
+    if (s->eventsUsed == s->events.size()) {
+        hipEvent_t e0, e1;
+        BF_HIP_TRY(hipEventCreate(&e0));
+        BF_HIP_TRY(hipEventCreate(&e1));
+        s->events.push_back({e0, e1});
+    }
+    ev = &s->events[s->eventsUsed++];
+    s->opsTimed += ops;
+    s->imagesTimed += images;
+    BF_HIP_TRY(hipEventRecord(ev->first, s->stream));
+    return BF_OK;
+}
+// the update is issued: the timed launches end, list buffer b is busy until evUpd[b], and the scene's own view moves to that buffer
+int closeSlot(bf_scene* s, int b, std::pair<hipEvent_t, hipEvent_t>* ev) {
+    if (ev) BF_HIP_TRY(hipEventRecord(ev->second, s->stream));
+    if (s->overlap) { BF_HIP_TRY(hipEventRecord(s->evUpd[b], s->stream)); s->updRecorded[b] = true; }
+    BF_HIP_TRY(hipGetLastError());
+    useBuf(s, b);
+    return BF_OK;
+}
+
+// One operator = preparation (allocation + block list) -> voxel update.  kind BF_SCENE_OP_INTEGRATE integrate(f), _DEINTEGRATE de-integrate(f), _REINTEGRATE fused: de-integrate(fo) +
 // integrate(f).  With overlap enabled the preparation goes to the prep stream and only the update to the main stream.  The preparation of an operator that
 // allocates is two launches - the march (which also writes the frame's texels for the fast contract) and the placement, which builds the list on the way;
 // an operator that does not allocate takes its snapshot and filters the allocated-block list.
 int runOperator(bf_scene* s, int kind, const Frame& f, const Frame& fo, const bf_depth_camera_data* data) {
-    const int b = s->overlap ? (s->cur + 1) % s->NB : s->cur;
-    hipStream_t ps = s->overlap ? s->prep : s->stream;
+    const auto [b, ps, dv] = openSlot(s);
+    const bool fused = kind == BF_SCENE_OP_REINTEGRATE;
     const bool useTexel = s->arith == BF_TSDF_ARITH_FAST && data->d_colorData != nullptr;
     BF_TRY_RC(prepWaits(s, ps));                   // incl. the frame's ingest (bf_scene_wait_event)
-    const Dev dv = devBuf(s, b);
     const uint2* opTexels = s->frameTexels;        // the caller's per-frame texel image (consumed by this operator), or the one made here
     s->frameTexels = nullptr;
     const size_t npx = (size_t)s->cam.m_imageWidth * s->cam.m_imageHeight;
@@ -1985,7 +2023,7 @@ int runOperator(bf_scene* s, int kind, const Frame& f, const Frame& fo, const bf
     // The preparation writes the operator's snapshot and list into buffer b (and, fast contract, the frame's texels into texel buffer b): not before the update
     // that used buffer b NB operators ago has finished - which also keeps the preparation at most NB operators ahead of the updates
     if (s->overlap && s->updRecorded[b]) BF_HIP_TRY(hipStreamWaitEvent(ps, s->evUpd[b], 0));
-    const bool marches = kind != 1 && !s->externalAlloc;                       // de-integration neither allocates nor frees
+    const bool marches = kind != BF_SCENE_OP_DEINTEGRATE && !s->externalAlloc;      // de-integration neither allocates nor frees
     const bool texelsFromMarch = marches && !s->allocComm && useTexel && !opTexels;      // (the divided march covers a band of the image only)
     if (useTexel && !opTexels && !texelsFromMarch) {
         hipLaunchKernelGGL(k_interleave, dim3(std::min<uint32_t>(div_up((uint32_t)npx, 256u), 2048u)), dim3(256), 0, ps, data->d_depthData, reinterpret_cast<const uint32_t*>(data->d_colorData), s->texel[b], (uint32_t)npx);
@@ -1994,52 +2032,35 @@ int runOperator(bf_scene* s, int kind, const Frame& f, const Frame& fo, const bf
     if (marches) {
         TexelOut tx{nullptr, nullptr};
         if (texelsFromMarch) { tx.color = reinterpret_cast<const uint32_t*>(data->d_colorData); tx.texel = s->texel[b]; opTexels = s->texel[b]; }
-        BF_TRY_RC(launchAllocOn(s, ps, dv, f, fo, kind == 2, data->d_depthData, tx));
+        BF_TRY_RC(launchAllocOn(s, ps, dv, f, fo, fused, data->d_depthData, tx));
     } else {
         hipLaunchKernelGGL(k_alloc_snapshot, dim3(1), dim3(1), 0, ps, dv);
-        if (kind == 2) hipLaunchKernelGGL(k_compact_append<2>, dim3(s->gridCompact), dim3(256), 0, ps, dv, f, fo);
+        if (fused) hipLaunchKernelGGL(k_compact_append<2>, dim3(s->gridCompact), dim3(256), 0, ps, dv, f, fo);
         else hipLaunchKernelGGL(k_compact_append<0>, dim3(s->gridCompact), dim3(256), 0, ps, dv, f, f);
     }
-    if (s->overlap) {
-        BF_HIP_TRY(hipEventRecord(s->evPrep[b], ps));
-        BF_HIP_TRY(hipStreamWaitEvent(s->stream, s->evPrep[b], 0));
-    }
+    BF_TRY_RC(publishPrep(s, b, ps));
     std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
-    if (s->timing) {
-        if (s->eventsUsed == s->events.size()) {
-            hipEvent_t e0, e1;
-            BF_HIP_TRY(hipEventCreate(&e0));
-            BF_HIP_TRY(hipEventCreate(&e1));
-            s->events.push_back({e0, e1});
-        }
-        ev = &s->events[s->eventsUsed++];
-        s->opsTimed += kind == 2 ? 2 : 1;
-        s->imagesTimed += 1;
-        BF_HIP_TRY(hipEventRecord(ev->first, s->stream));
-    }
+    BF_TRY_RC(beginTimed(s, fused ? 2 : 1, 1, ev));
     const uchar4* color = reinterpret_cast<const uchar4*>(data->d_colorData);
     const int acc = s->timing ? 1 : 0;
     if (s->arith == BF_TSDF_ARITH_FAST) {
         const ApxCam ac = makeApxCam(f);
-        const ApxPose pin = makeApxPose(f), pde = makeApxPose(kind == 2 ? fo : f);
+        const ApxPose pin = makeApxPose(f), pde = makeApxPose(fused ? fo : f);
         const int hasColor = useTexel ? 1 : 0;
-        if (kind == 0) launchApx<0>(s, s->gridUpdateColPlain, dv, ac, pin, pde, opTexels, hasColor, acc);
-        else if (kind == 1) launchApx<1>(s, s->gridUpdateColPlain, dv, ac, pin, pde, opTexels, hasColor, acc);
+        if (kind == BF_SCENE_OP_INTEGRATE) launchApx<0>(s, s->gridUpdateColPlain, dv, ac, pin, pde, opTexels, hasColor, acc);
+        else if (kind == BF_SCENE_OP_DEINTEGRATE) launchApx<1>(s, s->gridUpdateColPlain, dv, ac, pin, pde, opTexels, hasColor, acc);
         else launchApx<2>(s, s->gridUpdateCol, dv, ac, pin, pde, opTexels, hasColor, acc);
     } else {
         const UpdCam uc = makeUpdCam(f);
-        const UpdPose pin = makeUpdPose(f), pde = makeUpdPose(kind == 2 ? fo : f);
+        const UpdPose pin = makeUpdPose(f), pde = makeUpdPose(fused ? fo : f);
         const int fe = s->forceExactDiv ? 1 : 0;
-        if (kind == 0) hipLaunchKernelGGL(k_update_col<0>, dim3(s->gridUpdateColPlain), dim3(256), 0, s->stream, dv, uc, pin, pde, data->d_depthData, color, acc, fe);
-        else if (kind == 1) hipLaunchKernelGGL(k_update_col<1>, dim3(s->gridUpdateColPlain), dim3(256), 0, s->stream, dv, uc, pin, pde, data->d_depthData, color, acc, fe);
+        if (kind == BF_SCENE_OP_INTEGRATE) hipLaunchKernelGGL(k_update_col<0>, dim3(s->gridUpdateColPlain), dim3(256), 0, s->stream, dv, uc, pin, pde, data->d_depthData, color, acc, fe);
+        else if (kind == BF_SCENE_OP_DEINTEGRATE) hipLaunchKernelGGL(k_update_col<1>, dim3(s->gridUpdateColPlain), dim3(256), 0, s->stream, dv, uc, pin, pde, data->d_depthData, color, acc, fe);
         else hipLaunchKernelGGL(k_update_col<2>, dim3(s->gridUpdateCol), dim3(256), 0, s->stream, dv, uc, pin, pde, data->d_depthData, color, acc, fe);
     }
-    if (ev) BF_HIP_TRY(hipEventRecord(ev->second, s->stream));
-    if (s->overlap) { BF_HIP_TRY(hipEventRecord(s->evUpd[b], s->stream)); s->updRecorded[b] = true; }
-    BF_HIP_TRY(hipGetLastError());
-    useBuf(s, b);
-    s->compactStale = kind == 2;
-    s->gcMask = kind == 2 ? 1u : 0u;      // bit 0 of a union list's flags: the block lies in the frustum of the new pose (keepRec<2>)
+    BF_TRY_RC(closeSlot(s, b, ev));
+    s->compactStale = fused;
+    s->gcMask = fused ? 1u : 0u;      // bit 0 of a union list's flags: the block lies in the frustum of the new pose (keepRec<2>)
     return BF_OK;
 }
 
@@ -2091,9 +2112,7 @@ void verifyDump(bf_scene* s) {          // (streams drained by the caller) appen
 // A batch of operators in the serial order ops[0], ops[1], ...: one march, one binning, one placement + union list (preparation stream), one voxel update.
 int runBatch(bf_scene* s, const bf_scene_batch_op* ops, uint32_t n) {
     BF_TRY_RC(ensureBatch(s));
-    const int b = s->overlap ? (s->cur + 1) % s->NB : s->cur;
-    hipStream_t ps = s->overlap ? s->prep : s->stream;
-    const Dev dv = devBuf(s, b);
+    const auto [b, ps, dv] = openSlot(s);
     const bool fast = s->arith == BF_TSDF_ARITH_FAST;
     const size_t npx = (size_t)s->cam.m_imageWidth * s->cam.m_imageHeight;
     if (fast && s->btexelPixels < npx) {
@@ -2114,7 +2133,7 @@ int runBatch(bf_scene* s, const bf_scene_batch_op* ops, uint32_t n) {
     if (s->pendingEv) { BF_HIP_TRY(hipStreamWaitEvent(ms, s->pendingEv, 0)); s->pendingEv = nullptr; }
     if (s->overlap && s->updRecorded[b]) BF_HIP_TRY(hipStreamWaitEvent(ps, s->evUpd[b], 0));      // the update that read list buffer b and its texel set NB batches ago
     s->frameTexels = nullptr;
-    // per-operator frames: integration pose (kinds 0, 2), de-integration pose (kinds 1, 2)
+    // per-operator frames: integration pose (integrate, re-integrate), de-integration pose (de-integrate, re-integrate)
     Frame fin[BMAX], fde[BMAX];
     BatchCommon bc;
     BatchMarchArgs ma;
@@ -2126,17 +2145,18 @@ int runBatch(bf_scene* s, const bf_scene_batch_op* ops, uint32_t n) {
         setLastRigidTransform(s, o.T0);
         const Frame f0 = makeFrame(s);
         Frame f1 = f0;
-        if (o.kind == 2) { setLastRigidTransform(s, o.T1); f1 = makeFrame(s); }
-        fin[k] = o.kind == 2 ? f1 : f0;          // kind 0: integrate at T0; kind 2: integrate at T1
-        fde[k] = f0;                             // kind 1: de-integrate at T0; kind 2: de-integrate at T0
+        const bool fused = o.kind == BF_SCENE_OP_REINTEGRATE;
+        if (fused) { setLastRigidTransform(s, o.T1); f1 = makeFrame(s); }
+        fin[k] = fused ? f1 : f0;                // integrate at T0; re-integrate: integrate at T1
+        fde[k] = f0;                             // de-integrate and re-integrate: de-integrate at T0
         fr.TinvIn[k] = fin[k].Tinv; fr.TinvDe[k] = fde[k].Tinv;
-        fr.bits[k] = o.kind == 0 ? 1u : o.kind == 1 ? 2u : 3u;
+        fr.bits[k] = o.kind == BF_SCENE_OP_INTEGRATE ? 1u : o.kind == BF_SCENE_OP_DEINTEGRATE ? 2u : 3u;
         BatchMarchOp& m = ma.op[k];
         m.T = fin[k].T; m.Tinv = fin[k].Tinv;
         m.depth = o.data.d_depthData; m.color = reinterpret_cast<const uint32_t*>(o.data.d_colorData);
-        m.marches = (o.kind != 1 && !s->externalAlloc) ? 1u : 0u;      // a de-integration neither allocates nor frees
+        m.marches = (o.kind != BF_SCENE_OP_DEINTEGRATE && !s->externalAlloc) ? 1u : 0u;      // a de-integration neither allocates nor frees
         m.texel = (fast && o.data.d_colorData && !o.d_texels) ? s->btexel[b][k] : nullptr;
-        opsCount += o.kind == 2 ? 2u : 1u;
+        opsCount += fused ? 2u : 1u;
     }
     const uint32_t tiles = div_up(s->cam.m_imageWidth, 8) * div_up(s->cam.m_imageHeight, 8);
     uint32_t world = 1, rank = 0;
@@ -2170,23 +2190,9 @@ int runBatch(bf_scene* s, const bf_scene_batch_op* ops, uint32_t n) {
     if (s->overlap && s->barrierPending) { BF_HIP_TRY(hipStreamWaitEvent(ps, s->evBarrier, 0)); s->barrierPending = false; }
     hipLaunchKernelGGL(k_batch_bin, dim3(1024), dim3(256), 0, ps, dv, s->bd, bc);
     hipLaunchKernelGGL(k_batch_place, dim3(PLACE_WGS), dim3(256), 0, ps, dv, s->bd, bc, fr);
-    if (s->overlap) {
-        BF_HIP_TRY(hipEventRecord(s->evPrep[b], ps));
-        BF_HIP_TRY(hipStreamWaitEvent(s->stream, s->evPrep[b], 0));
-    }
+    BF_TRY_RC(publishPrep(s, b, ps));
     std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
-    if (s->timing) {
-        if (s->eventsUsed == s->events.size()) {
-            hipEvent_t e0, e1;
-            BF_HIP_TRY(hipEventCreate(&e0));
-            BF_HIP_TRY(hipEventCreate(&e1));
-            s->events.push_back({e0, e1});
-        }
-        ev = &s->events[s->eventsUsed++];
-        s->opsTimed += opsCount;
-        s->imagesTimed += n;
-        BF_HIP_TRY(hipEventRecord(ev->first, s->stream));
-    }
+    BF_TRY_RC(beginTimed(s, opsCount, n, ev));
     const int acc = s->timing ? 1 : 0;
     if (fast) {
         BatchUpdApxArgs ua;
@@ -2221,14 +2227,11 @@ int runBatch(bf_scene* s, const bf_scene_batch_op* ops, uint32_t n) {
         }
         hipLaunchKernelGGL(k_update_batch_col, dim3(s->gridUpdateCol), dim3(256), 0, s->stream, dv, makeUpdCam(fl), ua, acc, s->forceExactDiv ? 1 : 0);
     }
-    if (ev) BF_HIP_TRY(hipEventRecord(ev->second, s->stream));
-    if (s->overlap) { BF_HIP_TRY(hipEventRecord(s->evUpd[b], s->stream)); s->updRecorded[b] = true; }
-    BF_HIP_TRY(hipGetLastError());
-    useBuf(s, b);
+    BF_TRY_RC(closeSlot(s, b, ev));
     s->compactStale = true;
     // the frustum list of the LAST pose inside the union list: the blocks with the last operator's bit (integration pose, or the pose of a de-integration)
-    s->gcMask = (ops[n - 1].kind == 1 ? 2u : 1u) << (2u * (n - 1));
-    for (uint32_t k = 0; k < n; ++k) s->numIntegrated += ops[k].kind == 0 ? 1u : ops[k].kind == 1 ? (uint32_t)-1 : 0u;
+    s->gcMask = (ops[n - 1].kind == BF_SCENE_OP_DEINTEGRATE ? 2u : 1u) << (2u * (n - 1));
+    for (uint32_t k = 0; k < n; ++k) s->numIntegrated += ops[k].kind == BF_SCENE_OP_INTEGRATE ? 1u : ops[k].kind == BF_SCENE_OP_DEINTEGRATE ? (uint32_t)-1 : 0u;
     return BF_OK;
 }
 
@@ -2238,6 +2241,20 @@ int checkCall(bf_scene* s, const float* T, const bf_depth_camera_data* data, con
     BF_REQUIRE(data->d_depthData, "d_depthData is null");
     BF_REQUIRE(d_bitMask == nullptr, "chunk streaming (d_bitMask) is not supported: it is disabled for BundleFusion");
     BF_REQUIRE(cam->m_imageWidth > 0 && cam->m_imageHeight > 0, "empty image");
+    return BF_OK;
+}
+
+// what bf_scene_integrate / _deintegrate / _reintegrate do behind their argument checks: the operator at pose T (a re-integration: from oldT to T; else oldT = T,
+// whose frame is then made twice - two 4x4 inverses on the host, fo = f bit for bit); the scene's last rigid transform is T afterwards
+int singleOperator(bf_scene* s, int kind, const float* T, const float* oldT, const bf_depth_camera_data* data, const bf_depth_camera_params* cam) {
+    s->cam = *cam; s->haveCam = true;
+    setLastRigidTransform(s, oldT);
+    const Frame fo = makeFrame(s);
+    setLastRigidTransform(s, T);
+    const Frame f = makeFrame(s);
+    const int rc = runOperator(s, kind, f, fo, data);          // (oldT = T: fo is f)
+    if (rc) return rc;
+    s->numIntegrated += kind == BF_SCENE_OP_INTEGRATE ? 1u : kind == BF_SCENE_OP_DEINTEGRATE ? (uint32_t)-1 : 0u;
     return BF_OK;
 }
 
@@ -2500,26 +2517,14 @@ int bf_scene_reset(bf_scene* s) {                                  // CUDASceneR
 
 int bf_scene_integrate(bf_scene* s, const float T[16], const bf_depth_camera_data* data,
                        const bf_depth_camera_params* cam, const uint32_t* d_bitMask) {
-    int rc = checkCall(s, T, data, cam, d_bitMask);
-    if (rc) return rc;
-    s->cam = *cam; s->haveCam = true;
-    setLastRigidTransform(s, T);
-    const Frame f = makeFrame(s);
-    if ((rc = runOperator(s, 0, f, f, data))) return rc;
-    s->numIntegrated++;
-    return BF_OK;
+    const int rc = checkCall(s, T, data, cam, d_bitMask);
+    return rc ? rc : singleOperator(s, BF_SCENE_OP_INTEGRATE, T, T, data, cam);
 }
 
 int bf_scene_deintegrate(bf_scene* s, const float T[16], const bf_depth_camera_data* data,
                          const bf_depth_camera_params* cam, const uint32_t* d_bitMask) {
-    int rc = checkCall(s, T, data, cam, d_bitMask);
-    if (rc) return rc;
-    s->cam = *cam; s->haveCam = true;
-    setLastRigidTransform(s, T);
-    const Frame f = makeFrame(s);
-    if ((rc = runOperator(s, 1, f, f, data))) return rc;
-    s->numIntegrated--;
-    return BF_OK;
+    const int rc = checkCall(s, T, data, cam, d_bitMask);
+    return rc ? rc : singleOperator(s, BF_SCENE_OP_DEINTEGRATE, T, T, data, cam);
 }
 
 // Hash-bucket sharding: this volume keeps only blocks whose home bucket lies in
@@ -2542,12 +2547,7 @@ int bf_scene_reintegrate(bf_scene* s, const float oldT[16], const float newT[16]
     int rc = checkCall(s, newT, data, cam, nullptr);
     if (rc) return rc;
     BF_REQUIRE(oldT, "null argument");
-    s->cam = *cam; s->haveCam = true;
-    setLastRigidTransform(s, oldT);
-    const Frame fo = makeFrame(s);
-    setLastRigidTransform(s, newT);
-    const Frame f = makeFrame(s);
-    return runOperator(s, 2, f, fo, data);
+    return singleOperator(s, BF_SCENE_OP_REINTEGRATE, newT, oldT, data, cam);
 }
 
 // A batch of operators in the serial order ops[0] .. ops[n - 1] (MI355X addition; DepthSensing.cpp:854-902 issues them one by one): the same table, heap and
@@ -2557,7 +2557,7 @@ int bf_scene_run_batch(bf_scene* s, const bf_scene_batch_op* ops, uint32_t n, co
     BF_REQUIRE(n >= 1 && n <= BF_SCENE_BATCH_MAX, "1 .. BF_SCENE_BATCH_MAX operators per batch");
     BF_REQUIRE(cam->m_imageWidth > 0 && cam->m_imageHeight > 0, "empty image");
     for (uint32_t k = 0; k < n; ++k) {
-        BF_REQUIRE(ops[k].kind >= 0 && ops[k].kind <= 2, "unknown operator kind");
+        BF_REQUIRE(ops[k].kind == BF_SCENE_OP_INTEGRATE || ops[k].kind == BF_SCENE_OP_DEINTEGRATE || ops[k].kind == BF_SCENE_OP_REINTEGRATE, "unknown operator kind");
         BF_REQUIRE(ops[k].data.d_depthData, "d_depthData is null");
     }
     s->cam = *cam; s->haveCam = true;

@@ -211,8 +211,11 @@ BF_API int bf_scene_reintegrate(bf_scene* s, const float old_cam_to_world[16], c
  * every touched block is loaded once, updated by the batch's operators in order and stored once.  `wait_event` (optional hipEvent_t): the operator's frame is
  * complete when the event is; `d_texels` (optional): the frame as interleaved texels (bf_image_interleave_texels).  cam as in bf_scene_integrate. */
 #define BF_SCENE_BATCH_MAX 12
+#define BF_SCENE_OP_INTEGRATE 0        /* integrate(T0)                                   */
+#define BF_SCENE_OP_DEINTEGRATE 1      /* deIntegrate(T0)                                 */
+#define BF_SCENE_OP_REINTEGRATE 2      /* deIntegrate(T0) + integrate(T1), the same frame */
 typedef struct bf_scene_batch_op {
-    int32_t kind;
+    int32_t kind;                      /* BF_SCENE_OP_*                                   */
     int32_t reserved;
     float T0[16], T1[16];
     bf_depth_camera_data data;

@@ -730,14 +730,14 @@ public:
     void integrate(const mat4f& lastRigidTransform, const DepthCameraData& data, const DepthCameraParams& params, unsigned int* d_bitMask) {
         if (!m_deferred || d_bitMask) { flush(); check(bf_scene_integrate(m_h, lastRigidTransform.m, &data.d, &params, d_bitMask)); return; }
         // deIntegrate(old) directly followed by integrate(new) of the same frame (DepthSensing.cpp:885-886) is one fused re-integration
-        if (!m_pending.empty() && m_pending.back().kind == 1 && m_pending.back().data.d_depthData == data.d.d_depthData && m_pending.back().data.d_colorData == data.d.d_colorData && m_lastWasDe) {
-            m_pending.back().kind = 2; std::memcpy(m_pending.back().T1, lastRigidTransform.m, 64); m_lastWasDe = false;
-        } else push(0, lastRigidTransform, data);
+        if (!m_pending.empty() && m_pending.back().kind == BF_SCENE_OP_DEINTEGRATE && m_pending.back().data.d_depthData == data.d.d_depthData && m_pending.back().data.d_colorData == data.d.d_colorData && m_lastWasDe) {
+            m_pending.back().kind = BF_SCENE_OP_REINTEGRATE; std::memcpy(m_pending.back().T1, lastRigidTransform.m, 64); m_lastWasDe = false;
+        } else push(BF_SCENE_OP_INTEGRATE, lastRigidTransform, data);
         m_cam = params;
     }
     void deIntegrate(const mat4f& lastRigidTransform, const DepthCameraData& data, const DepthCameraParams& params, unsigned int* d_bitMask) {
         if (!m_deferred || d_bitMask) { flush(); check(bf_scene_deintegrate(m_h, lastRigidTransform.m, &data.d, &params, d_bitMask)); return; }
-        push(1, lastRigidTransform, data); m_lastWasDe = true;
+        push(BF_SCENE_OP_DEINTEGRATE, lastRigidTransform, data); m_lastWasDe = true;
         m_cam = params;
     }
     void garbageCollect() { flush(); check(bf_scene_garbage_collect(m_h)); }

@@ -221,6 +221,19 @@ def test_gloo_chunk_parallel_schedule(tmp_path, world):
         assert r[4] == str(rounds) and r[5] == str(rounds * world * 10 + 1)  # one collective per round; the stream is extended to complete the last round
 
 
+@pytest.mark.parametrize("sanitizer", ["thread", "address,undefined"])
+def test_volume_queue_harness_under_sanitizers(tmp_path, sanitizer):
+    """bf::VolumeQueue (csrc/volume_queue.cpp) against a fake scene, as a stand-alone program (tests/volume_queue_harness.cpp: batching, one-by-one and inline
+    dispatch, back-pressure, error hand-over, stop protocol, profile), built with plain g++ under the thread and the address + undefined-behaviour sanitizers."""
+    exe = str(tmp_path / "volume_queue_harness")
+    r = subprocess.run(["g++", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-g", "-O1", "-fsanitize=" + sanitizer, "-fno-sanitize-recover=all",
+                        os.path.join(ROOT, "tests", "volume_queue_harness.cpp"), os.path.join(ROOT, "bundlefusion_amd", "csrc", "volume_queue.cpp"), "-pthread", "-o", exe],
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert r.returncode == 0, r.stdout
+    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120)
+    assert r.returncode == 0 and "8 cases passed" in r.stdout, r.stdout
+
+
 def test_cpp_header_classes_compile_and_link(built, tmp_path):
     """include/bundlefusion/bundlefusion.hpp (reference class names over the C ABI) builds with plain g++ — no HIP headers
     needed on the integrator's side — and every forwarded symbol resolves against libbf_hip.so."""

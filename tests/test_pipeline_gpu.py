@@ -208,37 +208,75 @@ def test_lagged_solve_mode_vs_oracle_loop_with_the_same_lag(gpu, oracle, lag):
     assert dbg["duplicate_keys"] == 0 and dbg["leaked"] == 0 and dbg["free_and_allocated"] == 0
 
 
-@pytest.mark.gpu
-def test_frame_loop_depths_give_identical_results(gpu, monkeypatch):
-    """BF_PIPELINE_DEPTH = 2, 3, 4 (frames the loop may be behind its input): the schedule of every operation is the serial one, so trajectories, counters, hash table,
-    heap and every voxel byte are the same bit for bit (33 frames: three chunks, three global solves, re-integrations)."""
+def _loop_frames():
     import torch
     frames = synth.render_frames(range(33))
     Kd = frames[0][3]
     K = intrinsics_matrix(Kd["fx"], Kd["fy"], Kd["mx"], Kd["my"])
-    dev = [(torch.from_numpy(d).cuda(), torch.from_numpy(c).cuda()) for d, c, _, _ in frames]
+    return K, [(torch.from_numpy(d).cuda(), torch.from_numpy(c).cuda()) for d, c, _, _ in frames]
+
+
+def _loop_run(gpu, K, dev, mode="batched", collect=True):
+    """The 33 frames through a fresh pipeline; mode: how the volume's operators are issued - "batched" (the default), "unbatched" (set_volume_batching(False)) or
+    "timings" (enable_timings: from the calling thread, one by one)."""
+    gas, gbs = _params()
+    gas.s_garbageCollectionEnabled = 1 if collect else 0
+    gp = gpu.capi.Pipeline(gas, gbs, sensor_desc(W, H, K))
+    if mode == "unbatched":
+        gp.set_volume_batching(False)
+    elif mode == "timings":
+        gp.enable_timings(True)
+    else:
+        assert mode == "batched"
+    for d, c in dev:
+        assert gp.process_frame(d, c)
+    for _ in range(4):
+        gp.process_end_of_sequence()
+    gp.synchronize()
+    h, heap, cnt, vox = gp.scene().download()
+    return gp.integrated_trajectory(), gp.optimized_trajectory(), gp.counters(), h, heap, cnt, vox
+
+
+def _assert_same_volume(got, ref, what):
+    assert np.array_equal(got[3]["pos"], ref[3]["pos"]) and np.array_equal(got[3]["ptr"], ref[3]["ptr"]) and got[5] == ref[5], what
+    assert np.array_equal(got[4][:got[5] + 1], ref[4][:ref[5] + 1]), what
+    assert np.array_equal(got[6].view(np.uint8), ref[6].view(np.uint8)), what
+
+
+def _assert_same_loop_result(got, ref, what):
+    assert np.array_equal(got[0].view(np.uint32), ref[0].view(np.uint32)) and np.array_equal(got[1].view(np.uint32), ref[1].view(np.uint32)), what
+    assert got[2] == ref[2], what
+    _assert_same_volume(got, ref, what)
+
+
+@pytest.mark.gpu
+def test_frame_loop_depths_give_identical_results(gpu, monkeypatch):
+    """BF_PIPELINE_DEPTH = 2, 3, 4 (frames the loop may be behind its input): the schedule of every operation is the serial one, so trajectories, counters, hash table,
+    heap and every voxel byte are the same bit for bit (33 frames: three chunks, three global solves, re-integrations)."""
+    K, dev = _loop_frames()
 
     def run(depth):
         monkeypatch.setenv("BF_PIPELINE_DEPTH", str(depth))
-        gas, gbs = _params()
-        gp = gpu.capi.Pipeline(gas, gbs, sensor_desc(W, H, K))
-        for d, c in dev:
-            assert gp.process_frame(d, c)
-        for _ in range(4):
-            gp.process_end_of_sequence()
-        gp.synchronize()
-        h, heap, cnt, vox = gp.scene().download()
-        return gp.integrated_trajectory(), gp.optimized_trajectory(), gp.counters(), h, heap, cnt, vox
+        return _loop_run(gpu, K, dev)
 
     ref = run(2)
     assert ref[2]["deintegrate"] > 20 and ref[2]["global_solves"] >= 3
     for depth in (3, 4):
-        got = run(depth)
-        assert np.array_equal(got[0].view(np.uint32), ref[0].view(np.uint32)) and np.array_equal(got[1].view(np.uint32), ref[1].view(np.uint32)), depth
-        assert got[2] == ref[2], depth
-        assert np.array_equal(got[3]["pos"], ref[3]["pos"]) and np.array_equal(got[3]["ptr"], ref[3]["ptr"]) and got[5] == ref[5], depth
-        assert np.array_equal(got[4][:got[5] + 1], ref[4][:ref[5] + 1]), depth
-        assert np.array_equal(got[6].view(np.uint8), ref[6].view(np.uint8)), depth
+        _assert_same_loop_result(run(depth), ref, depth)
+
+
+@pytest.mark.gpu
+def test_volume_queue_modes_give_identical_results(gpu):
+    """The three ways a voxel operator reaches the volume (bf::VolumeQueue) - batched by the volume thread (default), one by one by the volume thread
+    (set_volume_batching(False)), one by one from the calling thread (enable_timings) - give the same trajectories, counters, hash table, heap and voxel bytes
+    on the 33 frames (fused re-integrations, integrations and collections pass through the queue).  With the garbage collection disabled a frame's boundary is a
+    flush command: the timings mode once answered it with a re-integration of nothing ("d_depthData is null")."""
+    K, dev = _loop_frames()
+    ref = _loop_run(gpu, K, dev)
+    assert ref[2]["deintegrate"] > 20 and ref[2]["global_solves"] >= 3
+    for mode in ("unbatched", "timings"):
+        _assert_same_loop_result(_loop_run(gpu, K, dev, mode), ref, mode)
+    _assert_same_volume(_loop_run(gpu, K, dev, "timings", collect=False), _loop_run(gpu, K, dev, "batched", collect=False), "no collection")
 
 
 def test_frame_loop_is_deterministic(gpu):
