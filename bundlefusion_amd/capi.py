@@ -792,6 +792,36 @@ class SiftManager:
                                               T.ctypes.data_as(C.c_void_p), Ti.ctypes.data_as(C.c_void_p)))
         return n.value, idx, dist, T, Ti
 
+    def set_raw_matches(self, pair, n, idx=None, dist=None):
+        """Overwrite the raw match list of one previous image: the count and (where given) the 128 index pairs / distances; shorter arrays are
+        zero-padded.  No index is checked: the caller keeps every key index below num_images * max_keys."""
+        i = d = None
+        if idx is not None:
+            idx = np.asarray(idx, np.uint32).reshape(-1, 2)
+            i = np.zeros((self.MAX_RAW, 2), np.uint32); i[:len(idx)] = idx
+        if dist is not None:
+            dist = np.asarray(dist, np.float32).reshape(-1)
+            d = np.zeros(self.MAX_RAW, np.float32); d[:len(dist)] = dist
+        check(lib.bf_siftmgr_set_raw_matches(self._h, pair, int(n), None if i is None else i.ctypes.data_as(C.c_void_p),
+                                             None if d is None else d.ctypes.data_as(C.c_void_p)))
+
+    def set_filt_matches(self, pair, n, idx=None, dist=None, T=None, Tinv=None):
+        """Overwrite the filtered match list of one previous image: the count and (where given) the 25 index pairs / distances and the two 4x4
+        transforms; shorter arrays are zero-padded.  No index is checked."""
+        i = d = t = ti = None
+        if idx is not None:
+            idx = np.asarray(idx, np.uint32).reshape(-1, 2)
+            i = np.zeros((self.MAX_FILT, 2), np.uint32); i[:len(idx)] = idx
+        if dist is not None:
+            dist = np.asarray(dist, np.float32).reshape(-1)
+            d = np.zeros(self.MAX_FILT, np.float32); d[:len(dist)] = dist
+        if T is not None:
+            t = np.ascontiguousarray(T, np.float32).reshape(16)
+        if Tinv is not None:
+            ti = np.ascontiguousarray(Tinv, np.float32).reshape(16)
+        p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        check(lib.bf_siftmgr_set_filt_matches(self._h, pair, int(n), p(i), p(d), p(t), p(ti)))
+
     def fuse_to_global(self, glob, K, d_transforms, Kinv, host=False):
         """fuseToGlobal on the device (default) or in the reference's host form (host=True); same results bit for bit"""
         fn = lib.bf_siftmgr_fuse_to_global_host if host else lib.bf_siftmgr_fuse_to_global

@@ -1534,6 +1534,25 @@ int bf_siftmgr_get_filt_matches(bf_siftmgr* m, uint32_t imagePairIndex, int32_t*
     BF_HIP_TRY(hipStreamSynchronize(m->stream));
     return BF_OK;
 }
+int bf_siftmgr_set_raw_matches(bf_siftmgr* m, uint32_t imagePairIndex, int32_t numMatches, const uint32_t* h_keyPointIndices, const float* h_distances) {
+    BF_REQUIRE(m && imagePairIndex < m->maxImages, "bad argument");
+    BF_HIP_TRY(hipMemcpyAsync(m->d_numMatches + imagePairIndex, &numMatches, sizeof(int), hipMemcpyHostToDevice, m->stream));
+    if (h_keyPointIndices) BF_HIP_TRY(hipMemcpyAsync(m->d_idx + (size_t)imagePairIndex * MAX_RAW, h_keyPointIndices, sizeof(uint2) * MAX_RAW, hipMemcpyHostToDevice, m->stream));
+    if (h_distances) BF_HIP_TRY(hipMemcpyAsync(m->d_dist + (size_t)imagePairIndex * MAX_RAW, h_distances, sizeof(float) * MAX_RAW, hipMemcpyHostToDevice, m->stream));
+    BF_HIP_TRY(hipStreamSynchronize(m->stream));
+    return BF_OK;
+}
+int bf_siftmgr_set_filt_matches(bf_siftmgr* m, uint32_t imagePairIndex, int32_t numMatches, const uint32_t* h_keyPointIndices, const float* h_distances,
+                                const float* h_transform, const float* h_transformInv) {
+    BF_REQUIRE(m && imagePairIndex < m->maxImages, "bad argument");
+    BF_HIP_TRY(hipMemcpyAsync(m->d_numFilt + imagePairIndex, &numMatches, sizeof(int), hipMemcpyHostToDevice, m->stream));
+    if (h_keyPointIndices) BF_HIP_TRY(hipMemcpyAsync(m->d_fidx + (size_t)imagePairIndex * MAX_FILT, h_keyPointIndices, sizeof(uint2) * MAX_FILT, hipMemcpyHostToDevice, m->stream));
+    if (h_distances) BF_HIP_TRY(hipMemcpyAsync(m->d_fdist + (size_t)imagePairIndex * MAX_FILT, h_distances, sizeof(float) * MAX_FILT, hipMemcpyHostToDevice, m->stream));
+    if (h_transform) BF_HIP_TRY(hipMemcpyAsync(m->d_T + imagePairIndex, h_transform, 64, hipMemcpyHostToDevice, m->stream));
+    if (h_transformInv) BF_HIP_TRY(hipMemcpyAsync(m->d_Tinv + imagePairIndex, h_transformInv, 64, hipMemcpyHostToDevice, m->stream));
+    BF_HIP_TRY(hipStreamSynchronize(m->stream));
+    return BF_OK;
+}
 
 int bf_siftmgr_add_to_retry_list(bf_siftmgr* m, uint32_t idx) { BF_REQUIRE(m, "null manager"); m->retry.push_front(idx); return BF_OK; }
 int bf_siftmgr_get_top_retry_image(bf_siftmgr* m, uint32_t* idx, int* found) {

@@ -529,6 +529,13 @@ BF_API int bf_siftmgr_get_raw_matches(bf_siftmgr* m, uint32_t imagePairIndex, in
 BF_API int bf_siftmgr_get_filt_matches(bf_siftmgr* m, uint32_t imagePairIndex, int32_t* numMatches,
                                        uint32_t* h_keyPointIndices, float* h_distances, float* h_transform,
                                        float* h_transformInv);
+/* The inverse of the two getters, for tests that hand the filters a match list of their own: the count and the 128 (raw) / 25 (filtered) slots of
+ * one previous image of the selected pair set are overwritten from host memory.  Null pointers are skipped; no index is checked. */
+BF_API int bf_siftmgr_set_raw_matches(bf_siftmgr* m, uint32_t imagePairIndex, int32_t numMatches,
+                                      const uint32_t* h_keyPointIndices, const float* h_distances);
+BF_API int bf_siftmgr_set_filt_matches(bf_siftmgr* m, uint32_t imagePairIndex, int32_t numMatches,
+                                       const uint32_t* h_keyPointIndices, const float* h_distances, const float* h_transform,
+                                       const float* h_transformInv);
 /* addToRetryList / getTopRetryImage                            .h:263-271 */
 BF_API int bf_siftmgr_add_to_retry_list(bf_siftmgr* m, uint32_t idx);
 BF_API int bf_siftmgr_get_top_retry_image(bf_siftmgr* m, uint32_t* idx, int* found);
