@@ -1390,6 +1390,30 @@ class Pipeline:
         check(lib.bf_pipeline_get_last_timing(self._h, C.byref(t)))
         return {n: getattr(t, n) for n, _ in FrameTiming._fields_}
 
+    def set_render_state(self, state):
+        check(lib.bf_pipeline_set_render_state(self._h, C.byref(state)))
+
+    def render_size(self, mode=1):
+        w, h = C.c_uint32(), C.c_uint32()
+        check(lib.bf_pipeline_get_render_size(self._h, int(mode), C.byref(w), C.byref(h)))
+        return w.value, h.value
+
+    def render(self, mode=1, camera_to_world=None, tracking_lost=None):
+        """bf_pipeline_render: the picture of s_RenderMode `mode` as uint8 (h, w, 4).  camera_to_world None: the pose of the last frame handed to the volume;
+        tracking_lost None: from that frame's validity."""
+        w, h = self.render_size(mode)
+        out = np.zeros((h, w, 4), np.uint8)
+        T = None if camera_to_world is None else _f16(camera_to_world)
+        check(lib.bf_pipeline_render(self._h, int(mode), T, -1 if tracking_lost is None else int(bool(tracking_lost)), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def render_top_down(self):
+        """bf_pipeline_render_top_down: renderTopDown's reconstruction picture (pose and depth range from the render state's s_topVideo* keys)"""
+        w, h = self.render_size(1)
+        out = np.zeros((h, w, 4), np.uint8)
+        check(lib.bf_pipeline_render_top_down(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
     def scene(self):
         """Borrowed SceneRepHashSDF view of the pipeline's voxel-hash volume."""
         h = C.c_void_p()
@@ -1677,3 +1701,86 @@ class RayCastSDF:
         f4 = lambda ptr: _d2h(ptr, n * 16).view("<f4").reshape(p.m_height, p.m_width, 4).copy()
         return dict(depth=f1(d.d_depth), depth4=f4(d.d_depth4), normals=f4(d.d_normals), colors=f4(d.d_colors),
                     ray_min=f1(d.d_rayIntervalSplatMin), ray_max=f1(d.d_rayIntervalSplatMax))
+
+
+# --------------------------------------------------------------------------- frame rendering (include/bf_render.h, csrc/render.hip)
+class RenderState(C.Structure):
+    """bf_render_state: the rendering keys of zParametersDefault.txt"""
+    _fields_ = [("s_materialShininess", C.c_float),
+                ("s_materialAmbient", C.c_float * 4), ("s_materialDiffuse", C.c_float * 4), ("s_materialSpecular", C.c_float * 4),
+                ("s_lightAmbient", C.c_float * 4), ("s_lightDiffuse", C.c_float * 4), ("s_lightSpecular", C.c_float * 4),
+                ("s_lightDirection", C.c_float * 3),
+                ("s_RenderMode", C.c_uint32),
+                ("s_renderingDepthDiscontinuityThresOffset", C.c_float), ("s_renderingDepthDiscontinuityThresLin", C.c_float),
+                ("s_generateVideo", C.c_int32), ("s_generateVideoDir", C.c_char * 256),
+                ("s_topVideoTransformWorld", C.c_float * 16), ("s_topVideoCameraPose", C.c_float * 4), ("s_topVideoMinMax", C.c_float * 2)]
+
+
+def default_render_state(path=None, with_missing=False):
+    """bf_render_state_default, or bf_render_state_read of a parameter file (with_missing: also the number of fields the file does not name)"""
+    g = RenderState(); n = C.c_uint32()
+    if path is None:
+        check(lib.bf_render_state_default(C.byref(g)))
+    else:
+        check(lib.bf_render_state_read(str(path).encode(), C.byref(g), C.byref(n)))
+    return (g, n.value) if with_missing else g
+
+
+def ray_cast_intrinsics_inv(params):
+    out = (C.c_float * 16)()
+    check(lib.bf_ray_cast_intrinsics_inv(C.byref(params), out))
+    return np.array(list(out), np.float32).reshape(4, 4)
+
+
+def write_png_rgba8(path, rgba):
+    a = np.ascontiguousarray(rgba, np.uint8)
+    assert a.ndim == 3 and a.shape[2] == 4
+    check(lib.bf_write_png_rgba8(str(path).encode(), a.ctypes.data_as(C.c_void_p), a.shape[1], a.shape[0]))
+
+
+class FrameRenderer:
+    """Python view of `bf_frame_renderer`: DX11RGBDRenderer::RenderDepthMap + DX11PhongLighting::render + DX11QuadDrawer::RenderQuad on a width x height image."""
+
+    def __init__(self, width, height, stream=0):
+        self._h = C.c_void_p()
+        self.w, self.h = int(width), int(height)
+        check(lib.bf_frame_renderer_create(self.w, self.h, C.byref(self._h)))
+        if stream:
+            check(lib.bf_frame_renderer_set_stream(self._h, C.c_void_p(stream)))
+
+    def close(self):
+        if self._h:
+            lib.bf_frame_renderer_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def shade(self, depth, colors, intrinsics_inv, state=None, use_material=False, tracking_lost=False, thresh_offset=None, thresh_lin=None):
+        """depth: float32 device tensor (h, w) or a device pointer; colors: float32 (h, w, 4) likewise.  The thresholds default to the state's."""
+        st = state if state is not None else default_render_state()
+        off = st.s_renderingDepthDiscontinuityThresOffset if thresh_offset is None else thresh_offset
+        lin = st.s_renderingDepthDiscontinuityThresLin if thresh_lin is None else thresh_lin
+        dp = C.c_void_p(depth) if isinstance(depth, int) else _p(depth)
+        cp = C.c_void_p(colors) if isinstance(colors, int) else _p(colors)
+        check(lib.bf_frame_renderer_shade(self._h, dp, cp, _f16(intrinsics_inv), C.byref(st), int(bool(use_material)), int(bool(tracking_lost)), C.c_float(off), C.c_float(lin)))
+
+    def depth_hsv(self, depth, dmin, dmax):
+        check(lib.bf_frame_renderer_depth_hsv(self._h, _p(depth), C.c_float(dmin), C.c_float(dmax)))
+
+    def rgbx(self, img):
+        check(lib.bf_frame_renderer_rgbx(self._h, _p(img)))
+
+    def download_rgba8(self):
+        out = np.zeros((self.h, self.w, 4), np.uint8)
+        check(lib.bf_frame_renderer_download_rgba8(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def download_target(self):
+        """the float4 target (GetColorsSRV) as float32 (h, w, 4); call after download_rgba8 or a synchronisation of the stream"""
+        t = C.c_void_p(); r = C.c_void_p()
+        check(lib.bf_frame_renderer_get_images(self._h, C.byref(t), C.byref(r)))
+        return _d2h(t.value, self.w * self.h * 16).view("<f4").reshape(self.h, self.w, 4).copy()

@@ -22,6 +22,7 @@
 
 #include "../../include/bf_pipeline.h"
 #include "../../include/bf_comm.h"
+#include "../../include/bf_render.h"
 #include "../../include/bf_sensordata.h"
 #include "bf_device.h"
 #include "bf_internal.h"
@@ -2131,6 +2132,11 @@ struct bf_pipeline {
     struct TraceRec { uint32_t frame; double hEnq0, hEnq1, hDet0, hDet1, hWait0, hWait1, hBody1; hipEvent_t gDet, gChain0, gChain1; };
     std::string tracePath; std::vector<TraceRec> trace; hipEvent_t traceBase = nullptr; double traceBaseHost = 0.0;
     TraceRec* traceOf(uint32_t frame) { for (size_t i = trace.size(); i-- > 0;) if (trace[i].frame == frame) return &trace[i]; return nullptr; }
+    // Pictures (bf_render.h): the ray caster and the renderers are created by the first render; a render is a command of the volume thread's queue.  The last frame
+    // handed to the volume (plBodyRest) gives the default view: its pose while it was valid, and whether tracking was lost
+    bf_ray_cast* rayCast = nullptr; bf_frame_renderer* renderer = nullptr; bf_frame_renderer* inputRenderer = nullptr;
+    bf_render_state renderState; bool haveRenderState = false;
+    bool haveVolFrame = false, lastVolLost = false; uint32_t lastVolFrame = 0; float lastVolT[16] = {};
     bool timings = false;
     hipEvent_t ev[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     bf_frame_timing last;
@@ -2229,7 +2235,10 @@ int plBodyRest(bf_pipeline* p, uint32_t frame, bool got) {
         if (valid && p->gas.s_reconstructionEnabled) {
             BF_TRY(plIntegrate(p, frameIdx, T, false, evSlot));
             BF_TRY(bf_trajectory_manager_add_frame(p->ob->tm, BF_TF_INTEGRATED, T, frame));
+            if (p->gas.s_integrationEnabled) { p->haveVolFrame = true; p->lastVolFrame = frameIdx; memcpy(p->lastVolT, T, 64); }
+            p->lastVolLost = lost != 0;
         } else {
+            p->lastVolLost = true;
             const m44 inv = minfM();
             BF_TRY(bf_trajectory_manager_add_frame(p->ob->tm, BF_TF_NOT_INTEGRATED_NO_TRANSFORM, inv.e, frame));
         }
@@ -2436,10 +2445,120 @@ int bf_pipeline_create(const bf_global_app_state* gas, const bf_global_bundling_
     return BF_OK;
 }
 
+// ---- pictures (bf_render.h): visualizeFrame's render modes, DepthSensing.cpp:766-850, and renderTopDown's reconstruction picture, :1262-1349
+namespace {
+
+struct PlRenderJob {
+    bf_pipeline* p; int mode; float T[16]; int lost; float threshOffset, threshLin; bool topDown; uint8_t* out;
+    const float* d_depth; const uint8_t* d_color;      // modes 3 / 4: the frame, resolved on the calling thread
+};
+
+int plRenderEnsure(bf_pipeline* p, bool input) {
+    if (!p->haveRenderState) { BF_TRY(bf_render_state_default(&p->renderState)); p->haveRenderState = true; }
+    if (input) {
+        if (!p->inputRenderer) {
+            BF_TRY(bf_frame_renderer_create(p->gas.s_integrationWidth, p->gas.s_integrationHeight, &p->inputRenderer));
+            BF_TRY(bf_frame_renderer_set_stream(p->inputRenderer, p->sVolume));
+        }
+        return BF_OK;
+    }
+    if (!p->rayCast) {
+        const float K[16] = {p->cam.fx, 0, p->cam.mx, 0, 0, p->cam.fy, p->cam.my, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+        bf_ray_cast_params rp;
+        BF_TRY(bf_ray_cast_params_from_global_app_state(&p->gas, K, &rp));
+        BF_TRY(bf_ray_cast_create(&rp, &p->rayCast));
+        BF_TRY(bf_ray_cast_set_stream(p->rayCast, p->sVolume));
+    }
+    if (!p->renderer) {
+        BF_TRY(bf_frame_renderer_create(p->gas.s_rayCastWidth, p->gas.s_rayCastHeight, &p->renderer));
+        BF_TRY(bf_frame_renderer_set_stream(p->renderer, p->sVolume));
+    }
+    return BF_OK;
+}
+
+// on the volume thread (timings: on the calling thread), between two batches: everything on the volume stream, and finished when it returns
+int plRenderExec(void* ctx) {
+    const PlRenderJob& j = *static_cast<const PlRenderJob*>(ctx);
+    bf_pipeline* p = j.p;
+    if (j.mode == 3) { BF_TRY(bf_frame_renderer_rgbx(p->inputRenderer, j.d_color)); return bf_frame_renderer_download_rgba8(p->inputRenderer, j.out); }
+    if (j.mode == 4) {
+        BF_TRY(bf_frame_renderer_depth_hsv(p->inputRenderer, j.d_depth, p->gas.s_sensorDepthMin, p->gas.s_sensorDepthMax));
+        return bf_frame_renderer_download_rgba8(p->inputRenderer, j.out);
+    }
+    bf_hash_data hd; bf_hash_params hp;
+    BF_TRY(bf_scene_begin_view(p->scene, j.T, &p->cam, &hd, &hp));
+    int rc = BF_OK;
+    if (j.topDown) rc = bf_ray_cast_update_min_max(p->rayCast, p->renderState.s_topVideoMinMax[0], p->renderState.s_topVideoMinMax[1]);
+    if (rc == BF_OK) rc = bf_ray_cast_render(p->rayCast, &hd, &hp, &p->cam, j.T);
+    bf_ray_cast_data rd; bf_ray_cast_params rp; float Kinv[16];
+    if (rc == BF_OK) rc = bf_ray_cast_get_data(p->rayCast, &rd);
+    if (rc == BF_OK) rc = bf_ray_cast_get_params(p->rayCast, &rp);
+    if (rc == BF_OK) rc = bf_ray_cast_intrinsics_inv(&rp, Kinv);
+    if (rc == BF_OK) rc = bf_frame_renderer_shade(p->renderer, rd.d_depth, rd.d_colors, Kinv, &p->renderState, j.mode == 2 ? 1 : 0, j.lost, j.threshOffset, j.threshLin);
+    if (rc == BF_OK) rc = bf_frame_renderer_download_rgba8(p->renderer, j.out);          // waits for the volume stream
+    if (j.topDown) (void)bf_ray_cast_update_min_max(p->rayCast, p->gas.s_renderDepthMin, p->gas.s_renderDepthMax);
+    const int rc2 = bf_scene_end_view(p->scene);
+    return rc != BF_OK ? rc : rc2;
+}
+
+int plRender(bf_pipeline* p, PlRenderJob& j) {
+    VolumeQueue::Cmd c;
+    c.op = VolumeQueue::Op::Render; c.render = plRenderExec; c.renderCtx = &j;
+    return p->vol.postAndWait(c);
+}
+
+}  // namespace
+
+int bf_pipeline_set_render_state(bf_pipeline* p, const bf_render_state* state) {
+    BF_REQUIRE(p && state, "null argument");
+    p->renderState = *state; p->haveRenderState = true;
+    return BF_OK;
+}
+
+int bf_pipeline_get_render_size(bf_pipeline* p, int mode, uint32_t* width, uint32_t* height) {
+    BF_REQUIRE(p && width && height, "null argument");
+    BF_REQUIRE(mode >= 1 && mode <= 4, "render mode 1 .. 4");
+    *width = mode <= 2 ? p->gas.s_rayCastWidth : p->gas.s_integrationWidth; *height = mode <= 2 ? p->gas.s_rayCastHeight : p->gas.s_integrationHeight;
+    return BF_OK;
+}
+
+int bf_pipeline_render(bf_pipeline* p, int mode, const float* cameraToWorld, int trackingLost, uint8_t* h_out) {
+    BF_REQUIRE(p && h_out, "null argument");
+    BF_REQUIRE(mode >= 1 && mode <= 4, "render mode 1 .. 4");
+    uint32_t w = 0, h = 0;
+    BF_TRY(bf_pipeline_get_render_size(p, mode, &w, &h));
+    PlRenderJob j = {};
+    j.p = p; j.mode = mode; j.out = h_out; j.topDown = false;
+    const bool needFrame = mode >= 3 || !cameraToWorld;
+    if (needFrame && !p->haveVolFrame) { memset(h_out, 0, (size_t)w * h * 4); return BF_OK; }      // nothing has reached the volume yet: the empty picture
+    BF_TRY(plRenderEnsure(p, mode >= 3));
+    if (mode >= 3) BF_TRY(bf_image_manager_get_integrate_frame_gpu(p->im, p->lastVolFrame, &j.d_depth, &j.d_color));
+    memcpy(j.T, cameraToWorld ? cameraToWorld : p->lastVolT, 64);
+    j.lost = trackingLost < 0 ? (p->lastVolLost ? 1 : 0) : (trackingLost ? 1 : 0);
+    j.threshOffset = p->renderState.s_renderingDepthDiscontinuityThresOffset; j.threshLin = p->renderState.s_renderingDepthDiscontinuityThresLin;
+    return plRender(p, j);
+}
+
+int bf_pipeline_render_top_down(bf_pipeline* p, uint8_t* h_out) {
+    BF_REQUIRE(p && h_out, "null argument");
+    BF_TRY(plRenderEnsure(p, false));
+    PlRenderJob j = {};
+    j.p = p; j.mode = 1; j.out = h_out; j.topDown = true; j.lost = 0;
+    j.threshOffset = 0.02f; j.threshLin = 0.01f;                           // DepthSensing.cpp:1321
+    // mat4f::translation(pose[1], pose[2], pose[3]) * mat4f::rotationZ(pose[0])  :1280 (degrees)
+    const float* pose = p->renderState.s_topVideoCameraPose;
+    const double a = (double)pose[0] * 3.14159265358979323846 / 180.0;
+    const float c = (float)std::cos(a), s = (float)std::sin(a);
+    const float T[16] = {c, -s, 0, pose[1], s, c, 0, pose[2], 0, 0, 1, pose[3], 0, 0, 0, 1};
+    memcpy(j.T, T, 64);
+    return plRender(p, j);
+}
+
 int bf_pipeline_destroy(bf_pipeline* p) {
     if (!p) return BF_OK;
     p->vol.stop();
     (void)hipDeviceSynchronize();
+    bf_ray_cast_destroy(p->rayCast); bf_frame_renderer_destroy(p->renderer); bf_frame_renderer_destroy(p->inputRenderer);
     if (!p->tracePath.empty() && !p->trace.empty()) {
         if (FILE* f = fopen(p->tracePath.c_str(), "a")) {
             fprintf(f, "# frame | host: detect enqueue (begin end) chain enqueue (begin end) wait for the result (begin end) body end | GPU: detection end, chain begin, chain end   [ms since the first traced frame]\n");

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/bf_pipeline.h"
+#include "../../include/bf_render.h"
 #include "bf_internal.h"
 
 namespace {
@@ -126,9 +127,54 @@ void readBundling(Reader& r, bf_global_bundling_state& g) {
     r.u("s_denseOverlapCheckSubsampleFactor", g.s_denseOverlapCheckSubsampleFactor);
 }
 
+// the rendering keys (GlobalAppState.h); one call per field of bf_render_state
+void readRender(Reader& r, bf_render_state& g) {
+    r.f("s_materialShininess", g.s_materialShininess);
+    r.fv("s_materialAmbient", g.s_materialAmbient, 4); r.fv("s_materialDiffuse", g.s_materialDiffuse, 4); r.fv("s_materialSpecular", g.s_materialSpecular, 4);
+    r.fv("s_lightAmbient", g.s_lightAmbient, 4); r.fv("s_lightDiffuse", g.s_lightDiffuse, 4); r.fv("s_lightSpecular", g.s_lightSpecular, 4);
+    r.fv("s_lightDirection", g.s_lightDirection, 3);
+    r.u("s_RenderMode", g.s_RenderMode);
+    r.f("s_renderingDepthDiscontinuityThresOffset", g.s_renderingDepthDiscontinuityThresOffset); r.f("s_renderingDepthDiscontinuityThresLin", g.s_renderingDepthDiscontinuityThresLin);
+    r.b("s_generateVideo", g.s_generateVideo);
+    if (auto* s = r.find("s_generateVideoDir")) {                                        // a quoted string
+        std::string v = *s;
+        if (v.size() >= 2 && v.front() == '"' && v.back() == '"') v = v.substr(1, v.size() - 2);
+        snprintf(g.s_generateVideoDir, sizeof g.s_generateVideoDir, "%s", v.c_str());
+    }
+    r.fv("s_topVideoTransformWorld", g.s_topVideoTransformWorld, 16); r.fv("s_topVideoCameraPose", g.s_topVideoCameraPose, 4); r.fv("s_topVideoMinMax", g.s_topVideoMinMax, 2);
+}
+
 }  // namespace
 
 extern "C" {
+
+int bf_render_state_default(bf_render_state* g) {                   // zParametersDefault.txt
+    BF_REQUIRE(g, "null argument");
+    memset(g, 0, sizeof *g);
+    g->s_materialShininess = 16.0f;
+    const float ma[4] = {0.75f, 0.65f, 0.5f, 1.0f}, md[4] = {1.0f, 0.9f, 0.7f, 1.0f}, ms[4] = {1.0f, 1.0f, 1.0f, 1.0f};
+    const float la[4] = {0.4f, 0.4f, 0.4f, 1.0f}, ld[4] = {0.6f, 0.52944f, 0.4566f, 0.6f}, ls[4] = {0.3f, 0.3f, 0.3f, 1.0f};
+    memcpy(g->s_materialAmbient, ma, 16); memcpy(g->s_materialDiffuse, md, 16); memcpy(g->s_materialSpecular, ms, 16);
+    memcpy(g->s_lightAmbient, la, 16); memcpy(g->s_lightDiffuse, ld, 16); memcpy(g->s_lightSpecular, ls, 16);
+    g->s_lightDirection[0] = 0.0f; g->s_lightDirection[1] = -1.0f; g->s_lightDirection[2] = 2.0f;
+    g->s_RenderMode = 1;
+    g->s_renderingDepthDiscontinuityThresOffset = 0.012f; g->s_renderingDepthDiscontinuityThresLin = 0.001f;
+    g->s_generateVideo = 0;
+    snprintf(g->s_generateVideoDir, sizeof g->s_generateVideoDir, "%s", "output/");
+    for (int i = 0; i < 16; ++i) g->s_topVideoTransformWorld[i] = (i % 5 == 0) ? 1.0f : 0.0f;
+    return BF_OK;
+}
+
+int bf_render_state_read(const char* filename, bf_render_state* out, uint32_t* numMissing) {
+    BF_REQUIRE(filename && out, "null argument");
+    KV kv;
+    if (!parseFile(filename, kv)) { bf::set_error("cannot open parameter file %s", filename); return BF_ERR_INVALID_ARG; }
+    bf_render_state_default(out);
+    Reader r(kv);
+    readRender(r, *out);
+    if (numMissing) *numMissing = r.missing;
+    return BF_OK;
+}
 
 int bf_global_app_state_default(bf_global_app_state* g) {           // zParametersDefault.txt
     BF_REQUIRE(g, "null argument");

@@ -2573,6 +2573,40 @@ int bf_scene_set_last_rigid_transform_and_compactify(bf_scene* s, const float T[
     return endExclusive(s);
 }
 
+// The frustum list of somebody else's view, in the list buffer the next operator would take: nothing the scene itself looks at (params, d.compact, compactStale,
+// gcMask, cur) changes.  Exclusive section: the preparation stream has finished what was issued, and starts nothing new before bf_scene_end_view.
+static int buildView(bf_scene* s, const float T[16], const bf_depth_camera_params* cam, bf_hash_data* hd, bf_hash_params* hp) {
+    const int b = (s->cur + 1) % s->NB;
+    const Dev dv = devBuf(s, b);
+    Frame f = makeFrame(s);
+    memcpy(f.T.e, T, 64);
+    f.Tinv = inverse44(f.T);
+    f.cam = *cam;
+    hipLaunchKernelGGL(k_alloc_snapshot, dim3(1), dim3(1), 0, s->stream, dv);
+    hipLaunchKernelGGL(k_compact_append<0>, dim3(s->gridCompact), dim3(256), 0, s->stream, dv, f, f);
+    BF_HIP_TRY(hipGetLastError());
+    int32_t n = 0;
+    BF_HIP_TRY(hipMemcpyAsync(&n, dv.compactCount, 4, hipMemcpyDeviceToHost, s->stream));
+    BF_HIP_TRY(hipStreamSynchronize(s->stream));
+    *hp = s->params;
+    memcpy(hp->m_rigidTransform, f.T.e, 64); memcpy(hp->m_rigidTransformInverse, f.Tinv.e, 64);
+    hp->m_numOccupiedBlocks = (uint32_t)n;
+    hd->d_heap = s->d.heap; hd->d_heapCounter = s->d.heapCounter; hd->d_hashDecision = s->d_hashDecision; hd->d_hashDecisionPrefix = nullptr;
+    hd->d_hash = s->d.hash; hd->d_hashCompactified = dv.compact; hd->d_hashCompactifiedCounter = dv.compactCount; hd->d_SDFBlocks = s->d.vox; hd->d_hashBucketMutex = nullptr;
+    return BF_OK;
+}
+int bf_scene_begin_view(bf_scene* s, const float T[16], const bf_depth_camera_params* cam, bf_hash_data* hd, bf_hash_params* hp) {
+    BF_REQUIRE(s && T && cam && hd && hp, "null argument");
+    BF_TRY_RC(beginExclusive(s));
+    const int rc = buildView(s, T, cam, hd, hp);
+    if (rc != BF_OK) (void)endExclusive(s);      // a view that failed closes its own exclusive section: the next operator's preparation waits for that barrier
+    return rc;
+}
+int bf_scene_end_view(bf_scene* s) {
+    BF_REQUIRE(s, "null scene");
+    return endExclusive(s);
+}
+
 int bf_scene_garbage_collect(bf_scene* s) {                          // :110-126
     BF_REQUIRE(s, "null scene");
     if (!s->haveCam) return BF_OK;                                  // nothing was ever compactified

@@ -42,6 +42,12 @@ int VolumeQueue::dispatch(const Cmd& c, bool batch) {
         return bf_scene_garbage_collect(scene_);
     case Op::Flush:
         return submitPending();
+    case Op::Render: {
+        BF_TRY(submitPending());
+        const int rc = c.render ? c.render(c.renderCtx) : BF_ERR_INVALID_ARG;
+        if (c.reply) { c.reply->rc = rc; if (rc != BF_OK) c.reply->message = bf_last_error(); }
+        return BF_OK;               // a picture that failed is its poster's business, not the volume's
+    }
     }
     return BF_ERR_INVALID_ARG;      // (not an Op)
 }
@@ -63,6 +69,7 @@ void VolumeQueue::work() {
             std::lock_guard<std::mutex> lk(mu_);
             busySeconds_ += dv; commands_ += 1.0;
             if (rc != BF_OK && workerError_ == BF_OK) { workerError_ = rc; workerMessage_ = bf_last_error(); }
+            if (c.reply) { if (rc != BF_OK) { c.reply->rc = rc; c.reply->message = bf_last_error(); } c.reply->done = true; }
             busy_ = false;
             cvIdle_.notify_all();
         }
@@ -89,6 +96,21 @@ int VolumeQueue::post(const Cmd& c) {
     queue_.push_back(c);
     cvWork_.notify_one();
     return BF_OK;
+}
+
+int VolumeQueue::postAndWait(Cmd c) {
+    Reply reply;
+    c.reply = &reply;
+    if (inline_) {
+        const int rc = dispatch(c, false);
+        if (rc != BF_OK) return rc;
+    } else {
+        BF_TRY(post(c));
+        std::unique_lock<std::mutex> lk(mu_);
+        cvIdle_.wait(lk, [&reply] { return reply.done; });
+    }
+    if (reply.rc != BF_OK) set_error("%s", reply.message.c_str());
+    return reply.rc;
 }
 
 int VolumeQueue::drain() {

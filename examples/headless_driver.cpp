@@ -1,11 +1,17 @@
 // Headless driver written against the reference's class names (include/bundlefusion/bundlefusion.hpp):
 // the serial body of DepthSensing.cpp's OnD3D11FrameRender without DirectX.  Build:
 //   g++ -std=c++17 -I include examples/headless_driver.cpp -L bundlefusion_amd/lib -lbf_hip -Wl,-rpath,$PWD/bundlefusion_amd/lib -o headless_driver
-// Run:  ./headless_driver zParametersDefault.txt zParametersBundlingDefault.txt
+// Run:  ./headless_driver zParametersDefault.txt zParametersBundlingDefault.txt [--video DIR]
+// --video DIR (or s_generateVideo = true with s_generateVideoDir): after every frame the PNG sequences of renderToFile (DepthSensing.cpp:1131-1260:
+// DIR/self_reconstruction/, DIR/self_reconstruction_color/) and of renderTopDown (:1262-1390: DIR/reconstruction/, DIR/reconstruction_color/, DIR/input_color/,
+// DIR/input_depth/), six-digit frame numbers.  The frustum overlay of renderTopDown is not drawn.
 // With s_sensorIdx = 8 the file named by s_binaryDumpSensorFile is played (SensorDataReader, FriedLiver.cpp:89-94) and the
 // optimised trajectory is evaluated against the poses stored in it; any other sensor index feeds a constant-depth dummy sensor.
 #include <cstdio>
 #include <limits>
+#include <memory>
+#include <string>
+#include <sys/stat.h>
 
 #include "bundlefusion/bundlefusion.hpp"
 
@@ -28,11 +34,62 @@ struct DummySensor : RGBDSensor {           // RGBDSensor contract: host float d
     const unsigned char* getColorRGBX() const override { return color.data(); }
 };
 
+// the PNG sequences of s_generateVideo: renderToFile and renderTopDown restated over CUDARayCastSDF + FrameRenderer
+struct VideoWriter {
+    std::string base; unsigned int frameNumber = 0;
+    CUDARayCastSDF rayCast; FrameRenderer target, input; DepthCameraParams cam;
+    VideoWriter(const std::string& dir, const GlobalAppState& gas, const mat4f& K, const DepthCameraParams& c)
+        : base(dir.empty() || dir.back() == '/' ? dir : dir + "/"), rayCast(CUDARayCastSDF::parametersFromGlobalAppState(gas, K, K.getInverse())),
+          target(gas.s_rayCastWidth, gas.s_rayCastHeight), input(gas.s_integrationWidth, gas.s_integrationHeight), cam(c) {
+        ::mkdir(base.c_str(), 0777);
+        for (const char* sub : {"self_reconstruction/", "self_reconstruction_color/", "input_color/", "input_depth/", "reconstruction/", "reconstruction_color/"}) ::mkdir((base + sub).c_str(), 0777);
+    }
+    std::string name(const char* sub) const { char n[16]; std::snprintf(n, sizeof n, "%06u", frameNumber); return base + sub + n + ".png"; }
+    void castAt(CUDASceneRepHashSDF& sceneRep, const mat4f& T) {
+        sceneRep.setLastRigidTransformAndCompactify(T, cam);
+        rayCast.render(sceneRep.getHashData(), sceneRep.getHashParams(), cam, T);
+    }
+    // renderToFile(context, lastRigidTransform, trackingLost)  :1131-1260
+    void renderToFile(CUDASceneRepHashSDF& sceneRep, const mat4f& lastRigidTransform, bool trackingLost) {
+        const GlobalRenderState& rs = GlobalRenderState::get();
+        castAt(sceneRep, lastRigidTransform);
+        target.render(rayCast, false, trackingLost, rs.s_renderingDepthDiscontinuityThresOffset, rs.s_renderingDepthDiscontinuityThresLin);
+        target.saveToFile(name("self_reconstruction/"));
+        target.render(rayCast, true, false, rs.s_renderingDepthDiscontinuityThresOffset, rs.s_renderingDepthDiscontinuityThresLin);
+        target.saveToFile(name("self_reconstruction_color/"));
+    }
+    // renderTopDown(context, lastRigidTransform, trackingLost)  :1262-1390, without the frustum; input_color / input_depth are render modes 3 and 4 of visualizeFrame
+    void renderTopDown(CUDASceneRepHashSDF& sceneRep, const float* d_depth, const unsigned char* d_color) {
+        const GlobalRenderState& rs = GlobalRenderState::get();
+        const GlobalAppState& gas = GlobalAppState::get();
+        const float* pose = rs.s_topVideoCameraPose;
+        const float a = pose[0] * 3.14159265358979323846f / 180.0f;
+        mat4f T = mat4f::identity();                             // mat4f::translation(pose[1], pose[2], pose[3]) * mat4f::rotationZ(pose[0])
+        T(0, 0) = std::cos(a); T(0, 1) = -std::sin(a); T(1, 0) = std::sin(a); T(1, 1) = std::cos(a); T(0, 3) = pose[1]; T(1, 3) = pose[2]; T(2, 3) = pose[3];
+        rayCast.updateRayCastMinMax(rs.s_topVideoMinMax[0], rs.s_topVideoMinMax[1]);
+        castAt(sceneRep, T);
+        // Departure: the reference leaves the top-video range in force (its reset is commented out, DepthSensing.cpp:1291), so from the second frame on its
+        // self_reconstruction pictures are cast with s_topVideoMinMax.  Here each sequence keeps its own range.
+        rayCast.updateRayCastMinMax(gas.s_renderDepthMin, gas.s_renderDepthMax);
+        target.render(rayCast, false, false, 0.02f, 0.01f);
+        target.saveToFile(name("reconstruction/"));
+        target.render(rayCast, true, false, 0.02f, 0.01f);
+        target.saveToFile(name("reconstruction_color/"));
+        input.RenderQuadDynamicUCHAR4(d_color);
+        input.saveToFile(name("input_color/"));
+        input.RenderQuadDynamicDEPTHasHSV(d_depth, gas.s_sensorDepthMin, gas.s_sensorDepthMax);
+        input.saveToFile(name("input_depth/"));
+    }
+};
+
 int main(int argc, char** argv) {
-    if (argc < 3) { std::printf("usage: %s zParametersDefault.txt zParametersBundlingDefault.txt\n", argv[0]); return 0; }
+    if (argc < 3) { std::printf("usage: %s zParametersDefault.txt zParametersBundlingDefault.txt [--video DIR]\n", argv[0]); return 0; }
     try {
         GlobalAppState::get().readMembers(argv[1]);
         GlobalBundlingState::get().readMembers(argv[2]);
+        GlobalRenderState::get().readMembers(argv[1]);
+        std::string videoDir = GlobalRenderState::get().s_generateVideo ? GlobalRenderState::get().s_generateVideoDir : "";
+        for (int i = 3; i + 1 < argc; ++i) if (std::string(argv[i]) == "--video") videoDir = argv[i + 1];
         const GlobalAppState& gas = GlobalAppState::get();
         const GlobalBundlingState& gbs = GlobalBundlingState::get();
         DummySensor dummy(640, 480, 30);
@@ -49,6 +106,9 @@ int main(int argc, char** argv) {
         cam.m_sensorDepthWorldMin = gas.s_renderDepthMin; cam.m_sensorDepthWorldMax = gas.s_renderDepthMax;
         cam.m_imageWidth = imageManager.getIntegrationWidth(); cam.m_imageHeight = imageManager.getIntegrationHeight();
         TrajectoryManager* tm = bundler.getTrajectoryManager();
+        std::unique_ptr<VideoWriter> video;
+        if (!videoDir.empty()) video.reset(new VideoWriter(videoDir, gas, K, cam));
+        mat4f lastRigidTransform = mat4f::identity();
         for (;;) {
             const bool bGotDepth = imageManager.process();
             if (!bGotDepth) break;
@@ -74,7 +134,8 @@ int main(int argc, char** argv) {
             }
             sceneRep.garbageCollect();
             mat4f T; unsigned int frameIdx; bool bGlobalTrackingLost;
-            if (bundler.getCurrentIntegrationFrame(T, frameIdx, bGlobalTrackingLost)) {
+            const bool validFrame = bundler.getCurrentIntegrationFrame(T, frameIdx, bGlobalTrackingLost);
+            if (validFrame) {
                 auto f = imageManager.getIntegrateFrame(frameIdx);
                 sceneRep.integrate(T, DepthCameraData(f.getDepthFrameGPU(), f.getColorFrameGPU()), cam, nullptr);
                 tm->addFrame(TrajectoryManager::TrajectoryFrame::Integrated, T, imageManager.getCurrFrameNumber());
@@ -82,13 +143,20 @@ int main(int argc, char** argv) {
                 mat4f inv; for (int i = 0; i < 16; ++i) inv.m[i] = -std::numeric_limits<float>::infinity();
                 tm->addFrame(TrajectoryManager::TrajectoryFrame::NotIntegrated_NoTransform, inv, imageManager.getCurrFrameNumber());
             }
+            if (video && sceneRep.getNumIntegratedFrames() > 0) {             // DepthSensing.cpp:1097-1101: s_generateVideo replaces visualizeFrame
+                if (validFrame) lastRigidTransform = T;
+                auto f = imageManager.getIntegrateFrame(imageManager.getCurrFrameNumber());
+                video->renderToFile(sceneRep, lastRigidTransform, bGlobalTrackingLost || !validFrame);
+                video->renderTopDown(sceneRep, f.getDepthFrameGPU(), f.getColorFrameGPU());
+                video->frameNumber++;
+            }
             bundler.process(gbs.s_numLocalNonLinIterations, gbs.s_numLocalLinIterations, gbs.s_numGlobalNonLinIterations, gbs.s_numGlobalLinIterations);
             std::printf("<<< [Frame: %u ] %u >>>\n", imageManager.getCurrFrameNumber(), sceneRep.getHeapFreeCount());
         }
         if (useFile) {                                          // DepthSensing.cpp:905-910 (StopScanningAndExit): evaluate against the recorded trajectory
             std::vector<mat4f> trajectory;
             tm->getOptimizedTransforms(trajectory);
-            reader.evaluateTrajectory(trajectory);
+            if (!trajectory.empty()) reader.evaluateTrajectory(trajectory);      // (not part of --video: a stream too short for an optimised trajectory has nothing to evaluate, and the call rejects an empty one)
         }
     } catch (const std::exception& e) {
         std::printf("error: %s\n", e.what());

@@ -1,7 +1,7 @@
 /*
  * bf_detmath.h — deterministic single-precision elementary functions.
  *
- * The SIFT front end needs exp, atan2, sin/cos and acos.  libm results differ between a host CPU
+ * The SIFT front end needs exp, atan2, sin/cos and acos, the frame renderer's Phong shading (bf_render.h) log and pow.  libm results differ between a host CPU
  * and the GPU's device library in the last bit, which would make keypoint orientations (floor() of
  * an angle), descriptor bytes and ratio-test decisions platform dependent.  These versions are part
  * of the arithmetic contract of this ABI: fixed sequences of IEEE-754 binary32 +,-,*,/ and sqrt only
@@ -50,6 +50,34 @@ BF_DM_FN float bf_dm_exp(float x) {
     const int ki = (int)k;
     return p * bf_dm_from_bits((uint32_t)(ki + 127) << 23);   /* exact scaling by 2^k, k in [-126,126] */
 }
+
+/* ln(x) for finite x > 0, denormals included.  x <= 0 and NaN return -inf.  +inf is not special-cased: its bits read as 2^128, so the
+ * sequence gives 128 ln 2 = 88.72.  x = 2^e m with m in (sqrt(1/2), sqrt(2)], s = (m-1)/(m+1), ln m = 2 atanh(s) as an odd series to s^9
+ * (|s| <= 0.1716: the first dropped term is below 2^-27 of the sum), ln2 split as in bf_dm_exp so that e * hi is exact. */
+BF_DM_FN float bf_dm_log(float x) {
+    if (!(x > 0.0f)) return bf_dm_from_bits(0xff800000u);
+    int e = 0;
+    if (x < 1.17549435e-38f) { x = x * 8388608.0f; e = -23; }     /* denormal: exact scaling by 2^23 */
+    const uint32_t u = bf_dm_bits(x);
+    e += (int)(u >> 23) - 127;
+    float m = bf_dm_from_bits((u & 0x007fffffu) | 0x3f800000u);   /* [1, 2) */
+    if (m > 1.41421356237f) { m = m * 0.5f; e += 1; }
+    const float f = m - 1.0f;                                     /* exact */
+    const float s = f / (2.0f + f);
+    const float z = s * s;
+    float p = 2.2222222e-1f;                                      /* 2/9, 2/7, 2/5, 2/3 */
+    p = p * z + 2.8571430e-1f;
+    p = p * z + 4.0000001e-1f;
+    p = p * z + 6.6666669e-1f;
+    const float lm = 2.0f * s + (s * z) * p;
+    const float ef = (float)e;
+    return ef * 0.693145751953125f + (ef * 1.42860682030941723212e-6f + lm);
+}
+
+/* x^y = exp(y ln x) for x > 0; 0 for x <= 0 and for NaN (the shaders raise clamped, non-negative values only).  The result is clamped as
+ * bf_dm_exp clamps: y ln x > 87 gives e^87, below -87 gives 0; x = +inf therefore gives exp(min(88.72 y, 87)) for y > 0.  The relative
+ * error is about |y ln x| 2^-23 + 2 ulp. */
+BF_DM_FN float bf_dm_pow(float x, float y) { return x > 0.0f ? bf_dm_exp(y * bf_dm_log(x)) : 0.0f; }
 
 /* atan(a) for a in [0,1] */
 BF_DM_FN float bf_dm_atan01(float a) {

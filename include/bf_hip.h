@@ -230,6 +230,12 @@ BF_API int bf_scene_set_last_rigid_transform_and_compactify(
     bf_scene* s, const float cam_to_world[16], const bf_depth_camera_params* cam);
 /* setLastRigidTransform(T)                                 :128-134 (host state only: m_rigidTransform and its inverse) */
 BF_API int bf_scene_set_last_rigid_transform(bf_scene* s, const float cam_to_world[16]);
+/* A frustum list for a view that is not the reconstruction's (the frame renderer, bf_render.h): setLastRigidTransformAndCompactify(T) + getHashData() +
+ * getHashParams() into a list buffer of its own.  The scene's last rigid transform, its block list and whatever a later operator or garbage collection reads
+ * stay as they are.  *hashData / *hashParams (m_rigidTransform = T, m_numOccupiedBlocks read back: the call waits for the stream) are valid until
+ * bf_scene_end_view, which the caller issues after its last launch that reads them, on the scene's stream; no other scene call in between. */
+BF_API int bf_scene_begin_view(bf_scene* s, const float cam_to_world[16], const bf_depth_camera_params* cam, bf_hash_data* hashData, bf_hash_params* hashParams);
+BF_API int bf_scene_end_view(bf_scene* s);
 /* getHashData() / getHashParams()                          :158-164
  * get_hash_params synchronises and refreshes m_numOccupiedBlocks.               */
 BF_API int bf_scene_get_hash_data(bf_scene* s, bf_hash_data* out);

@@ -23,7 +23,8 @@ extern "C" {
 /* (name = value; lines, // comments; parsed like ml::ParameterFile)          */
 /* ------------------------------------------------------------------------- */
 
-/* the GlobalAppState fields the hot path reads (rendering / recording / streaming keys are accepted and ignored) */
+/* the GlobalAppState fields the hot path reads (recording / streaming keys are accepted and ignored; the rendering keys - s_material*, s_light*, s_RenderMode,
+ * s_renderingDepthDiscontinuityThres*, s_generateVideo*, s_topVideo* - are ignored HERE and read from the same file into bf_render_state, bf_render.h) */
 typedef struct bf_global_app_state {
     uint32_t s_sensorIdx;
     uint32_t s_integrationWidth, s_integrationHeight;

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../bf_pipeline.h"
+#include "../bf_render.h"
 #include "../bf_sensordata.h"
 
 namespace bundlefusion {
@@ -844,6 +845,52 @@ private:
     bf_ray_cast* m_h = nullptr;
     RayCastData m_data;
     RayCastParams m_params;
+};
+
+// ---- GlobalRenderState: the rendering keys of GlobalAppState (s_material*, s_light*, s_RenderMode, s_renderingDepthDiscontinuityThres*, s_generateVideo*,
+// s_topVideo*), read from the same parameter file; a struct of its own so that GlobalAppState stays what the hot path reads (bf_render.h)
+class GlobalRenderState : public bf_render_state {
+public:
+    static GlobalRenderState& get() { static GlobalRenderState s; return s; }
+    void readMembers(const std::string& parameterFile) { check(bf_render_state_read(parameterFile.c_str(), this, nullptr)); }
+private:
+    GlobalRenderState() { bf_render_state_default(this); }
+};
+
+// ---- FrameRenderer: DX11RGBDRenderer::RenderDepthMap (DX11RGBDRenderer.h) into the four-target g_CustomRenderTarget, DX11PhongLighting::render / GetColorsSRV
+// (DX11PhongLighting.h) and DX11QuadDrawer::RenderQuad / RenderQuadDynamicUCHAR4 / RenderQuadDynamicDEPTHasHSV (DX11QuadDrawer.h) as one object over
+// bf_frame_renderer: no D3D device or context, the view matrix is the identity as in visualizeFrame, the output has the input image's size.
+class FrameRenderer {
+public:
+    FrameRenderer(unsigned int width, unsigned int height) : m_width(width), m_height(height) { check(bf_frame_renderer_create(width, height, &m_h)); }
+    ~FrameRenderer() { bf_frame_renderer_destroy(m_h); }
+    FrameRenderer(const FrameRenderer&) = delete;
+    // RenderDepthMap(context, d_depth, d_colors, width, height, intrinsicsInv, view = I, ..., threshOffset, threshLin) + DX11PhongLighting::render(context,
+    // positions, normals, colors, useMaterial, width, height, overlayColor) + RenderQuad(GetColorsSRV()): overlayColor.x == -1 is `trackingLost`
+    void render(const float* d_depth, const float* d_colors, const mat4f& intrinsicsInv, bool useMaterial, bool trackingLost, float threshOffset, float threshLin,
+                const bf_render_state& state = GlobalRenderState::get()) {
+        check(bf_frame_renderer_shade(m_h, d_depth, d_colors, intrinsicsInv.m, &state, useMaterial ? 1 : 0, trackingLost ? 1 : 0, threshOffset, threshLin));
+    }
+    void render(CUDARayCastSDF& rayCast, bool useMaterial, bool trackingLost, float threshOffset, float threshLin, const bf_render_state& state = GlobalRenderState::get()) {
+        mat4f Kinv; check(bf_ray_cast_intrinsics_inv(&rayCast.getRayCastParams(), Kinv.m));
+        const RayCastData& d = rayCast.getRayCastData();
+        render(d.d_depth, d.d_colors, Kinv, useMaterial, trackingLost, threshOffset, threshLin, state);
+    }
+    void RenderQuadDynamicUCHAR4(const unsigned char* d_color) { check(bf_frame_renderer_rgbx(m_h, d_color)); }
+    void RenderQuadDynamicDEPTHasHSV(const float* d_depth, float minDepth, float maxDepth) { check(bf_frame_renderer_depth_hsv(m_h, d_depth, minDepth, maxDepth)); }
+    const float* GetColors() const { const float* t; const uint8_t* r; check(bf_frame_renderer_get_images(m_h, &t, &r)); return t; }      // GetColorsSRV: float4, device
+    const unsigned char* getImageGPU() const { const float* t; const uint8_t* r; check(bf_frame_renderer_get_images(m_h, &t, &r)); return r; }
+    // g_RenderToFileTarget.copyToHost + the alpha rule of renderToFile: RGBA8, width * height * 4 bytes
+    const std::vector<unsigned char>& copyToHost() { m_host.resize((size_t)m_width * m_height * 4); check(bf_frame_renderer_download_rgba8(m_h, m_host.data())); return m_host; }
+    void saveToFile(const std::string& filename) { const std::vector<unsigned char>& img = copyToHost(); check(bf_write_png_rgba8(filename.c_str(), img.data(), m_width, m_height)); }      // LodePNG::save
+    void setStream(void* hipStream) { check(bf_frame_renderer_set_stream(m_h, hipStream)); }
+    unsigned int getWidth() const { return m_width; }
+    unsigned int getHeight() const { return m_height; }
+    bf_frame_renderer* handle() const { return m_h; }
+private:
+    bf_frame_renderer* m_h = nullptr;
+    unsigned int m_width, m_height;
+    std::vector<unsigned char> m_host;
 };
 
 // ---- CorrespondenceEvaluator (CorrespondenceEvaluator.h:10-141)
