@@ -956,12 +956,30 @@ __global__ __launch_bounds__(256) void k_compact_scatter(Dev d) {
         __syncthreads();
         uint32_t woff = 0;
         for (uint32_t w = 0; w < wave; ++w) woff += wscan[w];
-        const uint32_t tileTotal = wscan[0] + wscan[1] + wscan[2] + wscan[3];
         uint32_t pos = base + woff + incl - c;
 #pragma unroll
         for (uint32_t k = 0; k < 4; ++k) if (keep[k]) d.allocListAlt[pos++] = recs[k];
-        if (tile == numTiles - 1 && threadIdx.x == 0) d.tileCounts[numTiles] = base + tileTotal;      // new list length, committed by k_list_commit
         __syncthreads();
+    }
+    // The workgroup that arrives last commits the new list length (the former k_list_commit): the sum of k_compact_count's tile counts, nothing a workgroup of this
+    // launch wrote.  Every workgroup - the ones without a tile too - has read allocCount (n, above) before it takes its ticket.
+    __shared__ uint32_t lastFlag;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint32_t ticket = atomicAdd(&d.stats[ST_TICKET], 1u);
+        lastFlag = ticket == gridDim.x - 1 ? 1u : 0u;
+    }
+    __syncthreads();
+    if (!lastFlag) return;
+    uint32_t v = 0;
+    for (uint32_t t = threadIdx.x; t < numTiles; t += blockDim.x) v += d.tileCounts[t];
+    v = (uint32_t)wave_sum_i((int)v);
+    if (lane == 0) wsum[wave] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (numTiles > 0) d.allocCount[0] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        d.stats[ST_TICKET] = 0;
     }
 }
 
@@ -976,12 +994,6 @@ __global__ __launch_bounds__(256) void k_compact_append(Dev d, Frame f, Frame fo
 }
 
 __global__ void k_alloc_snapshot(Dev d) { d.allocSnap[0] = d.allocCount[0]; d.compactCount[0] = 0; d.compactCount[1] = 0; }      // an operator without an allocation of its own
-
-__global__ void k_list_commit(Dev d) {
-    const uint32_t n = d.allocCount[0];
-    const uint32_t numTiles = (n + TILE - 1) / TILE;
-    if (numTiles > 0) d.allocCount[0] = d.tileCounts[numTiles];
-}
 
 // ---------------------------------------------------------------------------------------
 // voxel update: integrate / de-integrate (CUDASceneRepHashSDF.cu:420-521)
@@ -1599,34 +1611,34 @@ __global__ void k_probe_cvt(uint32_t* out) {
 // ---------------------------------------------------------------------------------------
 // needMask != 0: d.compact is a union list (fused re-integration, batch) whose entries with (flags & needMask) != 0 are exactly the frustum list of the last
 // pose - the list the reference's garbageCollect walks (its last compactify) - so the union list is filtered here instead of being re-compacted first
+//
+// ONE WAVE per block, slice by slice (64 voxels, one per lane), and the wave leaves the block at the first slice with a weight that does not truncate to zero: the
+// maximum is only ever compared with 0.  A block the camera has seen answers in its first slice nearly always (profiles/volume_chain.md: 1.5 of 8 slices read on
+// average); only the blocks that are deleted - and the few whose surface crosses them late - are read whole.  No LDS, no workgroup barrier.
 __global__ __launch_bounds__(256) void k_gc_identify(Dev d, Frame f, uint32_t needMask) {
-    __shared__ uint32_t wmax[4];
     const uint32_t n = (uint32_t)d.compactCount[0];
-    for (uint32_t blk = blockIdx.x; blk < n; blk += gridDim.x) {
-        if (needMask != 0u && (reinterpret_cast<const uint32_t*>(d.compact)[(size_t)blk * 8 + 4] & needMask) == 0u) continue;      // block-uniform
+    const uint32_t lane = threadIdx.x & 63;
+    for (uint32_t blk = blockIdx.x * 4 + (threadIdx.x >> 6); blk < n; blk += gridDim.x * 4) {
+        if (needMask != 0u && (reinterpret_cast<const uint32_t*>(d.compact)[(size_t)blk * 8 + 4] & needMask) == 0u) continue;      // wave-uniform
         const int4 e = reinterpret_cast<const int4*>(d.compact)[(size_t)blk * 2];
         const bf_voxel* v = d.vox + (size_t)(uint32_t)e.w;
-        const uint32_t w0 = (uint32_t)f2i(v[2 * threadIdx.x + 0].weight);      // uint shared_MaxWeight, .cu:581,606
-        const uint32_t w1 = (uint32_t)f2i(v[2 * threadIdx.x + 1].weight);
-        uint32_t m = wave_max_u(max(w0, w1));
-        if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = m;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            m = max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3]));
-            if (m == 0) {
-                i3 b; b.x = e.x; b.y = e.y; b.z = e.z;
-                const uint32_t h = hashPos(f.numBuckets, b);
-                const uint32_t bin = (uint32_t)(((uint64_t)h * NBINS) / f.numBuckets);
-                const uint32_t pos = atomicAdd(&d.binCount[bin], 1u);
-                if (pos < BINCAP) {
-                    BinRec r; r.key = packKey(b); r.bucket = h; r.aux = d.compactSrc[blk];
-                    d.bins[(size_t)bin * BINCAP + pos] = r;
-                } else {
-                    atomicOr(&d.stats[ST_ERROR], (uint32_t)ERR_BIN_OVERFLOW);
-                }
+        bool zero = true;
+        for (uint32_t sl = 0; sl < (uint32_t)VOX / 64u; ++sl) {
+            const uint32_t w = (uint32_t)f2i(v[sl * 64u + lane].weight);      // uint shared_MaxWeight, .cu:581,606
+            if (__ballot(w != 0u) != 0ull) { zero = false; break; }            // wave-uniform
+        }
+        if (zero && lane == 0) {
+            i3 b; b.x = e.x; b.y = e.y; b.z = e.z;
+            const uint32_t h = hashPos(f.numBuckets, b);
+            const uint32_t bin = (uint32_t)(((uint64_t)h * NBINS) / f.numBuckets);
+            const uint32_t pos = atomicAdd(&d.binCount[bin], 1u);
+            if (pos < BINCAP) {
+                BinRec r; r.key = packKey(b); r.bucket = h; r.aux = d.compactSrc[blk];
+                d.bins[(size_t)bin * BINCAP + pos] = r;
+            } else {
+                atomicOr(&d.stats[ST_ERROR], (uint32_t)ERR_BIN_OVERFLOW);
             }
         }
-        __syncthreads();
     }
 }
 
@@ -1671,12 +1683,30 @@ BF_DEV int32_t deleteEntry(const Dev& d, const Frame& f, i3 b, uint32_t h) {
     return BF_FREE_ENTRY;
 }
 
+// The workgroup that arrives last closes the collection (the former k_gc_finish): heap counter forward by the number of deleted blocks, bin counts back to zero for
+// the next allocation.  It consumes nothing another workgroup of this launch wrote - the bin counts are k_gc_identify's - so the ticket only has to say that every
+// workgroup, the ones of empty bins included, has READ the bin counts and the heap counter: each takes it behind its last such load.
+BF_DEV void gcFinishIfLast(const Dev& d, uint32_t* scratch) {
+    __shared__ uint32_t lastFlag;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint32_t ticket = atomicAdd(&d.stats[ST_TICKET], 1u);
+        lastFlag = ticket == gridDim.x - 1 ? 1u : 0u;
+    }
+    __syncthreads();
+    if (!lastFlag) return;
+    const uint32_t D = binPrefix(d.binCount, NBINS, scratch);
+    if (threadIdx.x == 0) { d.heapCounter[0] += D; d.stats[ST_TICKET] = 0; }
+    for (uint32_t b = threadIdx.x; b < NBINS; b += blockDim.x) d.binCount[b] = 0;
+}
+
 __global__ __launch_bounds__(1024) void k_gc_delete(Dev d, Frame f) {
     __shared__ SortLds s;
     __shared__ uint32_t scratch[16];
     const uint32_t bin = blockIdx.x;
     const uint32_t n = min(d.binCount[bin], BINCAP);
-    if (n == 0) return;
+    if (n == 0) { gcFinishIfLast(d, scratch); return; }      // block-uniform
     loadBinSorted(s, d.bins + (size_t)bin * BINCAP, n);
     const uint32_t base = binPrefix(d.binCount, bin, scratch);
     const uint32_t heapC = d.heapCounter[0];
@@ -1699,14 +1729,7 @@ __global__ __launch_bounds__(1024) void k_gc_delete(Dev d, Frame f) {
         uint4* v4 = reinterpret_cast<uint4*>(d.vox + (size_t)ptr);
         for (uint32_t t = threadIdx.x; t < (uint32_t)(VOX * 12 / 16); t += blockDim.x) v4[t] = make_uint4(0, 0, 0, 0);
     }
-}
-
-__global__ __launch_bounds__(256) void k_gc_finish(Dev d) {
-    __shared__ uint32_t scratch[16];
-    const uint32_t D = binPrefix(d.binCount, NBINS, scratch);
-    if (threadIdx.x == 0) d.heapCounter[0] += D;
-    __syncthreads();
-    for (uint32_t b = threadIdx.x; b < NBINS; b += blockDim.x) d.binCount[b] = 0;
+    gcFinishIfLast(d, scratch);
 }
 
 }  // namespace
@@ -1751,9 +1774,10 @@ struct bf_scene {
     int NB = 4;                     // list buffers in use (2 .. NBMAX)
     bf_hash_entry* cbuf[NBMAX] = {}; uint32_t* csrc[NBMAX] = {}; int32_t* ccnt[NBMAX] = {};
     int cur = 0;                    // buffer that holds the latest list (== d.compact / d.compactSrc / d.compactCount)
-    hipEvent_t evPrep[NBMAX] = {}, evUpd[NBMAX] = {}, evBarrier = nullptr, evTmp = nullptr;
+    hipEvent_t evPrep[NBMAX] = {}, evUpd[NBMAX] = {}, evBarrier = nullptr, evTmp = nullptr, evPlace = nullptr;
     bool updRecorded[NBMAX] = {};
     bool barrierPending = false;    // the last exclusive section of the main stream has not been waited for by the preparation stream yet
+    bool placePending = false;      // a batch's placement on the main stream (evPlace, runBatch) has not been waited for by the preparation stream yet
     hipEvent_t pendingEv = nullptr; // bf_scene_wait_event: the next operator's first kernel waits for it
     const uint2* frameTexels = nullptr;   // bf_scene_set_frame_texels: the next operator's frame as interleaved texels, made once when the frame was ingested
     bool compactStale = false;      // d.compact holds a union list (fused re-integration, batch) or nothing usable (behind a garbage collection), not the frustum list of the last pose
@@ -1961,6 +1985,7 @@ int launchAllocOn(bf_scene* s, hipStream_t st, const Dev& dv, const Frame& f, co
 int prepWaits(bf_scene* s, hipStream_t ps) {
     if (s->pendingEv) { BF_HIP_TRY(hipStreamWaitEvent(ps, s->pendingEv, 0)); s->pendingEv = nullptr; }
     if (s->overlap && s->barrierPending) { BF_HIP_TRY(hipStreamWaitEvent(ps, s->evBarrier, 0)); s->barrierPending = false; }
+    if (s->overlap && s->placePending) { BF_HIP_TRY(hipStreamWaitEvent(ps, s->evPlace, 0)); s->placePending = false; }
     return BF_OK;
 }
 
@@ -2131,6 +2156,7 @@ int runBatch(bf_scene* s, const bf_scene_batch_op* ops, uint32_t n) {
     hipStream_t ms = ps;
     for (uint32_t k = 0; k < n; ++k) if (ops[k].wait_event) BF_HIP_TRY(hipStreamWaitEvent(ms, (hipEvent_t)ops[k].wait_event, 0));
     if (s->pendingEv) { BF_HIP_TRY(hipStreamWaitEvent(ms, s->pendingEv, 0)); s->pendingEv = nullptr; }
+    if (s->overlap && s->placePending) { BF_HIP_TRY(hipStreamWaitEvent(ps, s->evPlace, 0)); s->placePending = false; }      // the last batch's binning emptied the key set this march claims in
     if (s->overlap && s->updRecorded[b]) BF_HIP_TRY(hipStreamWaitEvent(ps, s->evUpd[b], 0));      // the update that read list buffer b and its texel set NB batches ago
     s->frameTexels = nullptr;
     // per-operator frames: integration pose (integrate, re-integrate), de-integration pose (de-integrate, re-integrate)
@@ -2187,10 +2213,23 @@ int runBatch(bf_scene* s, const bf_scene_batch_op* ops, uint32_t n) {
         }
     }
     // the table look-ups wait for whatever frees table entries (the last garbage collection); the march above does not
-    if (s->overlap && s->barrierPending) { BF_HIP_TRY(hipStreamWaitEvent(ps, s->evBarrier, 0)); s->barrierPending = false; }
-    hipLaunchKernelGGL(k_batch_bin, dim3(1024), dim3(256), 0, ps, dv, s->bd, bc);
-    hipLaunchKernelGGL(k_batch_place, dim3(PLACE_WGS), dim3(256), 0, ps, dv, s->bd, bc, fr);
-    BF_TRY_RC(publishPrep(s, b, ps));
+    if (s->overlap && s->barrierPending) {
+        // Binning and placement have to follow the main stream's exclusive section (the frame's garbage collection): issued behind it on that stream they need no
+        // barrier hop, and the update behind them no publish hop - update -> collection -> bin -> place -> update is one queue, and only the march crosses streams
+        // (profiles/volume_chain.md: 1055 -> 1148 frames/s with the rest of this chain, although this stream has no queue priority).  The preparation stream takes
+        // the barrier behind the march, long past when it next matters, and waits for this placement before it touches the key set or the table again (evPlace).
+        BF_HIP_TRY(hipEventRecord(s->evPrep[b], ps));
+        BF_HIP_TRY(hipStreamWaitEvent(s->stream, s->evPrep[b], 0));
+        BF_HIP_TRY(hipStreamWaitEvent(ps, s->evBarrier, 0)); s->barrierPending = false;
+        hipLaunchKernelGGL(k_batch_bin, dim3(1024), dim3(256), 0, s->stream, dv, s->bd, bc);
+        hipLaunchKernelGGL(k_batch_place, dim3(PLACE_WGS), dim3(256), 0, s->stream, dv, s->bd, bc, fr);
+        BF_HIP_TRY(hipEventRecord(s->evPlace, s->stream)); s->placePending = true;
+    } else {
+        if (s->overlap && s->barrierPending) { BF_HIP_TRY(hipStreamWaitEvent(ps, s->evBarrier, 0)); s->barrierPending = false; }
+        hipLaunchKernelGGL(k_batch_bin, dim3(1024), dim3(256), 0, ps, dv, s->bd, bc);
+        hipLaunchKernelGGL(k_batch_place, dim3(PLACE_WGS), dim3(256), 0, ps, dv, s->bd, bc, fr);
+        BF_TRY_RC(publishPrep(s, b, ps));
+    }
     std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
     BF_TRY_RC(beginTimed(s, opsCount, n, ev));
     const int acc = s->timing ? 1 : 0;
@@ -2309,7 +2348,7 @@ int bf_scene_create(const bf_hash_params* p, bf_scene** out) {
     }
     for (int b = 0; b < bf_scene::NBMAX; ++b)
         for (hipEvent_t* e : {&s->evPrep[b], &s->evUpd[b]}) BF_HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
-    for (hipEvent_t* e : {&s->evBarrier, &s->evTmp})
+    for (hipEvent_t* e : {&s->evBarrier, &s->evTmp, &s->evPlace})
         BF_HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
     s->gridCompact = std::min<uint32_t>(std::max<uint32_t>(div_up((uint32_t)N, TILE), 1u), 2048u);
     s->gridUpdateCol = s->gridUpdateColPlain = 8192;      // see k_update_col
@@ -2448,7 +2487,7 @@ int bf_scene_destroy(bf_scene* s) {
     if (s->d_batchRecv) hipFree(s->d_batchRecv);
     for (auto& e : s->events) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
     for (int b = 0; b < bf_scene::NBMAX; ++b) for (hipEvent_t e : {s->evPrep[b], s->evUpd[b]}) if (e) hipEventDestroy(e);
-    for (hipEvent_t e : {s->evBarrier, s->evTmp}) if (e) hipEventDestroy(e);
+    for (hipEvent_t e : {s->evBarrier, s->evTmp, s->evPlace}) if (e) hipEventDestroy(e);
     if (s->prep) hipStreamDestroy(s->prep);
     delete s;
     return BF_OK;
@@ -2466,7 +2505,7 @@ int bf_scene_set_overlap(bf_scene* s, int enable) {
     BF_TRY_RC(syncAll(s));
     s->overlap = enable != 0 && !getenv("BF_DEBUG_NO_OVERLAP");      // (diagnostic: the preparation on the main stream, nothing of the volume beside its own update)
     for (bool& u : s->updRecorded) u = false;
-    s->barrierPending = false;
+    s->barrierPending = false; s->placePending = false;
     return BF_OK;
 }
 
@@ -2501,7 +2540,7 @@ int bf_scene_reset(bf_scene* s) {                                  // CUDASceneR
     memcpy(s->params.m_rigidTransformInverse, I.e, 64);
     s->params.m_numOccupiedBlocks = 0;
     BF_TRY_RC(syncAll(s));
-    s->compactStale = false; s->gcMask = 0; s->barrierPending = false; s->pendingEv = nullptr;
+    s->compactStale = false; s->gcMask = 0; s->barrierPending = false; s->placePending = false; s->pendingEv = nullptr;
 
     for (bool& u : s->updRecorded) u = false;
     for (int b = 0; b < bf_scene::NBMAX; ++b) BF_HIP_TRY(hipMemsetAsync(s->ccnt[b], 0, 16, s->stream));
@@ -2615,11 +2654,9 @@ int bf_scene_garbage_collect(bf_scene* s) {                          // :110-126
     if (s->compactStale) { if (s->gcMask) needMask = s->gcMask; else BF_TRY_RC(launchCompactify(s)); }
     const Frame f = makeFrame(s);
     hipLaunchKernelGGL(k_gc_identify, dim3(4096), dim3(256), 0, s->stream, s->d, f, needMask);
-    hipLaunchKernelGGL(k_gc_delete, dim3(NBINS), dim3(1024), 0, s->stream, s->d, f);
-    hipLaunchKernelGGL(k_gc_finish, dim3(1), dim3(256), 0, s->stream, s->d);
+    hipLaunchKernelGGL(k_gc_delete, dim3(NBINS), dim3(1024), 0, s->stream, s->d, f);               // its last workgroup: heap counter, bin counts
     hipLaunchKernelGGL(k_compact_count, dim3(s->gridCompact), dim3(256), 0, s->stream, s->d);
-    hipLaunchKernelGGL(k_compact_scatter, dim3(s->gridCompact), dim3(256), 0, s->stream, s->d);
-    hipLaunchKernelGGL(k_list_commit, dim3(1), dim3(1), 0, s->stream, s->d);
+    hipLaunchKernelGGL(k_compact_scatter, dim3(s->gridCompact), dim3(256), 0, s->stream, s->d);    // its last workgroup: the new list length
     std::swap(s->d.allocList, s->d.allocListAlt);
     BF_HIP_TRY(hipGetLastError());
     // The list in d.compact refers to positions of the allocated-block list before its compaction: nothing usable.  It is rebuilt when somebody needs the
