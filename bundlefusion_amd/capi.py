@@ -1414,6 +1414,14 @@ class Pipeline:
         check(lib.bf_pipeline_render_top_down(self._h, out.ctypes.data_as(C.c_void_p)))
         return out
 
+    def save_mesh(self, filename, transform=None):
+        """bf_pipeline_save_mesh: the mesh of everything handed in so far as a PLY, extracted and welded on the device between two frames' batches.
+        Returns (vertices, faces, triangles)."""
+        nv, nf, nt = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        T = mat16(transform) if transform is not None else None
+        check(lib.bf_pipeline_save_mesh(self._h, str(filename).encode(), T, C.byref(nv), C.byref(nf), C.byref(nt)))
+        return nv.value, nf.value, nt.value
+
     def scene(self):
         """Borrowed SceneRepHashSDF view of the pipeline's voxel-hash volume."""
         h = C.c_void_p()
@@ -1554,6 +1562,73 @@ class MarchingCubesHashSDF:
         T = mat16(transform) if transform is not None else None
         check(lib.bf_marching_cubes_save_mesh(self._h, str(filename).encode(), T, C.byref(nv), C.byref(nf)))
         return nv.value, nf.value
+
+    # ---- MI355X additions: the mesh without the triangles leaving HBM (csrc/meshweld.hip)
+    @classmethod
+    def from_global_app_state(cls, gas, max_triangles=0, thresh_factor=10.0):
+        """parametersFromGlobalAppState: the thresholds are thresh_factor * s_SDFVoxelSize in binary32, as bf_pipeline_save_mesh computes them.  max_triangles 0: every
+        extraction sizes the triangle buffer to the volume."""
+        self = cls.__new__(cls)
+        th = float(np.float32(thresh_factor) * np.float32(gas.s_SDFVoxelSize))
+        self.params = MarchingCubesParams(max_triangles, SDF_BLOCK_SIZE, gas.s_hashNumBuckets, HASH_BUCKET_SIZE, th, th)
+        self._h = C.c_void_p()
+        check(lib.bf_marching_cubes_create(C.byref(self.params), C.byref(self._h)))
+        return self
+
+    def triangles_gpu(self):
+        """(device pointer, triangles written, triangles the volume holds) of the last extraction"""
+        ptr = C.c_void_p(); n = C.c_uint32(); found = C.c_uint32()
+        check(lib.bf_marching_cubes_get_triangles_gpu(self._h, C.byref(ptr), C.byref(n), C.byref(found)))
+        return ptr.value, n.value, found.value
+
+    def extract_gpu(self, scene, box=None):
+        """extract without the host copy (the host mesh buffer keeps what it held): returns (triangles written, triangles the volume holds)"""
+        hd = scene.hash_data(); hp = scene.hash_params()
+        mn = (C.c_float * 3)(*(box[0] if box else (0, 0, 0))); mx = (C.c_float * 3)(*(box[1] if box else (0, 0, 0)))
+        check(lib.bf_marching_cubes_extract_gpu(self._h, C.byref(hd), C.byref(hp), mn, mx, int(box is not None)))
+        _, n, found = self.triangles_gpu()
+        return n, found
+
+    def download_triangles(self):
+        """host copy of the last extraction's device buffer, [n, 3, 6] float32"""
+        ptr, n, _ = self.triangles_gpu()
+        out = np.zeros((n, 3, 6), np.float32)
+        if n:
+            check(lib.bf_memcpy_d2h(out.ctypes.data_as(C.c_void_p), C.c_void_p(ptr), C.c_size_t(out.nbytes)))
+        return out
+
+    def weld(self, triangles=None, transform=None):
+        """bf_marching_cubes_weld + download: (positions [nv,3] float32, colours [nv,3] float32, faces [nf,3] uint32).  triangles: a contiguous float32 torch cuda
+        tensor [T,3,6], or None for the last extraction."""
+        m = IndexedMesh()
+        T = mat16(transform) if transform is not None else None
+        if triangles is None:
+            check(lib.bf_marching_cubes_weld(self._h, None, 0, T, C.byref(m)))
+        else:
+            assert triangles.is_contiguous() and triangles.numel() % 18 == 0
+            check(lib.bf_marching_cubes_weld(self._h, C.c_void_p(triangles.data_ptr()), triangles.numel() // 18, T, C.byref(m)))
+        pos = np.zeros((m.numVertices, 3), np.float32); col = np.zeros((m.numVertices, 3), np.float32); faces = np.zeros((m.numFaces, 3), np.uint32)
+        check(lib.bf_marching_cubes_download_indexed(self._h, pos.ctypes.data_as(C.c_void_p), col.ctypes.data_as(C.c_void_p), faces.ctypes.data_as(C.c_void_p)))
+        return pos, col, faces
+
+    def save_mesh_gpu(self, filename, transform=None):
+        """weld of the last extraction on the device + PLY: (vertices, faces)"""
+        nv = C.c_uint32(); nf = C.c_uint32()
+        T = mat16(transform) if transform is not None else None
+        check(lib.bf_marching_cubes_save_mesh_gpu(self._h, str(filename).encode(), T, C.byref(nv), C.byref(nf)))
+        return nv.value, nf.value
+
+
+class IndexedMesh(C.Structure):
+    _fields_ = [("d_positions", C.c_void_p), ("d_colors", C.c_void_p), ("d_faces", C.c_void_p), ("numVertices", C.c_uint32), ("numFaces", C.c_uint32)]
+
+
+def write_ply_indexed(filename, positions, colors, faces):
+    """bf_write_ply_indexed: the PLY of an indexed mesh (positions / colours [nv,3] float32, faces [nf,3] uint32).  Host-only."""
+    pos = np.ascontiguousarray(positions, np.float32).reshape(-1, 3); col = np.ascontiguousarray(colors, np.float32).reshape(-1, 3)
+    fc = np.ascontiguousarray(faces, np.uint32).reshape(-1, 3)
+    assert len(pos) == len(col)
+    check(lib.bf_write_ply_indexed(str(filename).encode(), pos.ctypes.data_as(C.c_void_p), col.ctypes.data_as(C.c_void_p), fc.ctypes.data_as(C.c_void_p), len(pos), len(fc)))
 
 
 # --------------------------------------------------------------------------- CorrespondenceEvaluator

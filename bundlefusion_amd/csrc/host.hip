@@ -2137,6 +2137,10 @@ struct bf_pipeline {
     bf_ray_cast* rayCast = nullptr; bf_frame_renderer* renderer = nullptr; bf_frame_renderer* inputRenderer = nullptr;
     bf_render_state renderState; bool haveRenderState = false;
     bool haveVolFrame = false, lastVolLost = false; uint32_t lastVolFrame = 0; float lastVolT[16] = {};
+    // The mesh (bf_pipeline_save_mesh): the marching-cubes object is created by the first save, with a triangle buffer sized to the volume; a save is a command of
+    // the volume thread's queue, like a render.  A shard of the volume lacks its neighbours' blocks, so a sharded loop refuses
+    bf_marching_cubes* marchingCubes = nullptr;
+    bool volumeSharded = false, volumeComm = false;
     bool timings = false;
     hipEvent_t ev[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     bf_frame_timing last;
@@ -2554,10 +2558,56 @@ int bf_pipeline_render_top_down(bf_pipeline* p, uint8_t* h_out) {
     return plRender(p, j);
 }
 
+// ---- the mesh: StopScanningAndExtractIsoSurfaceMC (DepthSensing.cpp:335-368) from inside the frame loop, welded on the device
+namespace {
+
+struct PlMeshJob { bf_pipeline* p; const char* filename; const float* transform; uint32_t nv, nf, nt; };
+
+// on the volume thread (timings: on the calling thread), between two batches.  The view's exclusive section is a render's: the preparation stream has finished
+// and starts nothing until the section ends, and the last rigid transform, the block lists and the heap are what they were - marching cubes reads the hash slots
+// themselves, the view's own frustum list is not used.
+int plMeshExec(void* ctx) {
+    PlMeshJob& j = *static_cast<PlMeshJob*>(ctx);
+    bf_pipeline* p = j.p;
+    const float I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    bf_hash_data hd; bf_hash_params hp;
+    BF_TRY(bf_scene_begin_view(p->scene, I, &p->cam, &hd, &hp));
+    int rc = bf_marching_cubes_extract_gpu(p->marchingCubes, &hd, &hp, nullptr, nullptr, 0);
+    if (rc == BF_OK) rc = bf_marching_cubes_get_triangles_gpu(p->marchingCubes, nullptr, nullptr, &j.nt);
+    if (rc == BF_OK) rc = bf_marching_cubes_save_mesh_gpu(p->marchingCubes, j.filename, j.transform, &j.nv, &j.nf);          // waits for the volume stream
+    const int rc2 = bf_scene_end_view(p->scene);
+    return rc != BF_OK ? rc : rc2;
+}
+
+}  // namespace
+
+int bf_pipeline_save_mesh(bf_pipeline* p, const char* filename, const float* transform, uint32_t* numVertices, uint32_t* numFaces, uint32_t* numTriangles) {
+    BF_REQUIRE(p && filename, "null argument");
+    BF_REQUIRE(!p->volumeSharded && !p->volumeComm, "the volume is sharded over ranks (bf_pipeline_set_volume_shard / _set_comm): a shard lacks its neighbours' blocks, meshing across ranks is not supported");
+    BF_TRY(plFlush(p));          // every frame handed in so far reaches the volume before the mesh is taken
+    if (!p->marchingCubes) {
+        bf_marching_cubes_params mp;          // CUDAMarchingCubesHashSDF::parametersFromGlobalAppState (.h:20-29), s_SDFMarchingCubeThreshFactor = 10; capacity 0: sized to the volume
+        mp.m_maxNumTriangles = 0;
+        mp.m_threshMarchingCubes = 10.0f * p->gas.s_SDFVoxelSize; mp.m_threshMarchingCubes2 = 10.0f * p->gas.s_SDFVoxelSize;
+        mp.m_sdfBlockSize = BF_SDF_BLOCK_SIZE; mp.m_hashBucketSize = BF_HASH_BUCKET_SIZE; mp.m_hashNumBuckets = p->gas.s_hashNumBuckets;
+        BF_TRY(bf_marching_cubes_create(&mp, &p->marchingCubes));
+        BF_TRY(bf_marching_cubes_set_stream(p->marchingCubes, p->sVolume));
+    }
+    PlMeshJob j = {p, filename, transform, 0, 0, 0};
+    VolumeQueue::Cmd c;
+    c.op = VolumeQueue::Op::SaveMesh; c.render = plMeshExec; c.renderCtx = &j;
+    BF_TRY(p->vol.postAndWait(c));
+    if (numVertices) *numVertices = j.nv;
+    if (numFaces) *numFaces = j.nf;
+    if (numTriangles) *numTriangles = j.nt;
+    return BF_OK;
+}
+
 int bf_pipeline_destroy(bf_pipeline* p) {
     if (!p) return BF_OK;
     p->vol.stop();
     (void)hipDeviceSynchronize();
+    bf_marching_cubes_destroy(p->marchingCubes);
     bf_ray_cast_destroy(p->rayCast); bf_frame_renderer_destroy(p->renderer); bf_frame_renderer_destroy(p->inputRenderer);
     if (!p->tracePath.empty() && !p->trace.empty()) {
         if (FILE* f = fopen(p->tracePath.c_str(), "a")) {
@@ -2613,7 +2663,9 @@ int bf_pipeline_set_comm(bf_pipeline* p, bf_comm* comm, uint32_t capacity_keys) 
     BF_REQUIRE(p, "null pipeline");
     BF_TRY(plFlush(p));
     BF_TRY(p->vol.drain());
-    return bf_scene_set_alloc_comm(p->scene, comm, capacity_keys);
+    BF_TRY(bf_scene_set_alloc_comm(p->scene, comm, capacity_keys));
+    p->volumeComm = comm != nullptr;
+    return BF_OK;
 }
 
 // Batched volume operators on / off (on by default; see bf::VolumeQueue).  Off: every operator is issued on its own (bf_scene_integrate / _deintegrate /
@@ -2628,7 +2680,9 @@ int bf_pipeline_set_volume_batching(bf_pipeline* p, int enable) {
 
 int bf_pipeline_set_volume_shard(bf_pipeline* p, uint32_t rank, uint32_t world) {
     BF_REQUIRE(p, "null pipeline");
-    return bf_scene_set_shard(p->scene, rank, world);
+    BF_TRY(bf_scene_set_shard(p->scene, rank, world));
+    p->volumeSharded = world > 1;
+    return BF_OK;
 }
 
 int bf_pipeline_process_frame(bf_pipeline* p, const float* h_depth, const uint8_t* h_color, int* gotFrame) {

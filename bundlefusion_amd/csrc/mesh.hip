@@ -31,6 +31,7 @@
 
 #include "bf_device.h"
 #include "bf_internal.h"
+#include "bf_meshweld.h"
 #include "bf_volume.h"
 
 using namespace bf;
@@ -304,11 +305,13 @@ struct bf_marching_cubes {
     hipStream_t stream = nullptr;
     McTables* d_tables = nullptr;
     bf_mc_triangle* d_triangles = nullptr;
+    uint32_t capTriangles = 0;          // of d_triangles: m_maxNumTriangles, or (m_maxNumTriangles == 0) what the largest extraction so far needed
     uint32_t *d_tileCounts = nullptr, *d_slots = nullptr, *d_numBlocks = nullptr, *d_blockCounts = nullptr, *d_total = nullptr;
     uint32_t capSlots = 0;
     uint32_t numTriangles = 0;          // of the last extraction (clamped to m_maxNumTriangles)
     uint32_t numTrianglesFound = 0;     // before clamping
     std::vector<bf_mc_triangle> mesh;   // m_meshData: triangles accumulated by copyTrianglesToCPU
+    MeshWeld weld;                      // the indexed mesh of the last bf_marching_cubes_weld, in HBM (meshweld.hip)
 };
 
 extern "C" {
@@ -322,14 +325,15 @@ int bf_marching_cubes_tables(uint16_t edgeTable[256], int8_t triTable[256 * 16])
 }
 
 int bf_marching_cubes_create(const bf_marching_cubes_params* p, bf_marching_cubes** out) {      // CUDAMarchingCubesHashSDF::create (.cpp:14-20)
-    BF_REQUIRE(p && out && p->m_maxNumTriangles > 0, "bad argument");
+    BF_REQUIRE(p && out, "bad argument");          // m_maxNumTriangles == 0: the triangle buffer is sized to the volume by every extraction
     BF_REQUIRE(p->m_sdfBlockSize == BF_SDF_BLOCK_SIZE && p->m_hashBucketSize == BF_HASH_BUCKET_SIZE, "block size 8 / bucket size 4 expected");
     bf_marching_cubes* m = new bf_marching_cubes;
     m->params = *p;
     McTables t; makeTables(t);
     BF_HIP_TRY(BF_MALLOC((void**)&m->d_tables, sizeof t));
     BF_HIP_TRY(hipMemcpy(m->d_tables, &t, sizeof t, hipMemcpyHostToDevice));
-    BF_HIP_TRY(BF_MALLOC((void**)&m->d_triangles, sizeof(bf_mc_triangle) * (size_t)p->m_maxNumTriangles));
+    if (p->m_maxNumTriangles) BF_HIP_TRY(BF_MALLOC((void**)&m->d_triangles, sizeof(bf_mc_triangle) * (size_t)p->m_maxNumTriangles));
+    m->capTriangles = p->m_maxNumTriangles;
     BF_HIP_TRY(BF_MALLOC((void**)&m->d_numBlocks, 4));
     BF_HIP_TRY(BF_MALLOC((void**)&m->d_total, 4));
     *out = m;
@@ -341,14 +345,17 @@ int bf_marching_cubes_destroy(bf_marching_cubes* m) {
     (void)hipDeviceSynchronize();
     (void)hipFree(m->d_tables); (void)hipFree(m->d_triangles); (void)hipFree(m->d_numBlocks); (void)hipFree(m->d_total);
     (void)hipFree(m->d_tileCounts); (void)hipFree(m->d_slots); (void)hipFree(m->d_blockCounts);
+    meshweld_free(m->weld);
     delete m;
     return BF_OK;
 }
 
 int bf_marching_cubes_set_stream(bf_marching_cubes* m, void* s) { BF_REQUIRE(m, "null argument"); m->stream = (hipStream_t)s; return BF_OK; }
 
-// extractIsoSurface(hashData, hashParams, rayCastData, minCorner, maxCorner, boxEnabled)  .cpp:107-119 (+ copyTrianglesToCPU :27-46)
-int bf_marching_cubes_extract(bf_marching_cubes* m, const bf_hash_data* hd, const bf_hash_params* hp, const float minCorner[3], const float maxCorner[3], int boxEnabled) {
+}  // extern "C"
+
+// extractIsoSurface(hashData, hashParams, rayCastData, minCorner, maxCorner, boxEnabled)  .cpp:107-119; toHost: + copyTrianglesToCPU :27-46
+static int mcExtract(bf_marching_cubes* m, const bf_hash_data* hd, const bf_hash_params* hp, const float minCorner[3], const float maxCorner[3], int boxEnabled, bool toHost) {
     BF_REQUIRE(m && hd && hp && hd->d_hash && hd->d_SDFBlocks, "null argument");
     BF_REQUIRE(hp->m_hashBucketSize == BF_HASH_BUCKET_SIZE && hp->m_SDFBlockSize == BF_SDF_BLOCK_SIZE, "block size 8 / bucket size 4 expected");
     const uint32_t numSlots = hp->m_hashNumBuckets * BF_HASH_BUCKET_SIZE;
@@ -380,6 +387,17 @@ int bf_marching_cubes_extract(bf_marching_cubes* m, const bf_hash_data* hd, cons
     hipLaunchKernelGGL(k_mc_blocks<false>, dim3(grid), dim3(512), 0, st, a, (const McTables*)m->d_tables, (const uint32_t*)m->d_slots, (const uint32_t*)m->d_numBlocks,
                        m->d_blockCounts, (bf_mc_triangle*)nullptr);
     hipLaunchKernelGGL(k_scan_u32, dim3(1), dim3(1024), 0, st, m->d_blockCounts, nb, m->d_total);
+    if (m->params.m_maxNumTriangles == 0) {          // the count is known before anything is written: size the buffer to the volume
+        uint32_t need = 0;
+        BF_HIP_TRY(hipMemcpyAsync(&need, m->d_total, 4, hipMemcpyDeviceToHost, st));
+        BF_HIP_TRY(hipStreamSynchronize(st));
+        if (need > m->capTriangles) {
+            (void)hipFree(m->d_triangles); m->d_triangles = nullptr; m->capTriangles = 0;
+            BF_HIP_TRY(BF_MALLOC((void**)&m->d_triangles, sizeof(bf_mc_triangle) * (size_t)need));
+            m->capTriangles = need;
+        }
+        a.maxTriangles = need;
+    }
     hipLaunchKernelGGL(k_mc_blocks<true>, dim3(grid), dim3(512), 0, st, a, (const McTables*)m->d_tables, (const uint32_t*)m->d_slots, (const uint32_t*)m->d_numBlocks,
                        m->d_blockCounts, m->d_triangles);
     BF_HIP_TRY(hipGetLastError());
@@ -387,11 +405,22 @@ int bf_marching_cubes_extract(bf_marching_cubes* m, const bf_hash_data* hd, cons
     BF_HIP_TRY(hipMemcpyAsync(&total, m->d_total, 4, hipMemcpyDeviceToHost, st));
     BF_HIP_TRY(hipStreamSynchronize(st));
     m->numTrianglesFound = total;
-    m->numTriangles = std::min(total, m->params.m_maxNumTriangles);          // like appendTriangle (:262-284): the buffer's capacity bounds the mesh
+    m->numTriangles = std::min(total, a.maxTriangles);                        // like appendTriangle (:262-284): the buffer's capacity bounds the mesh
+    if (!toHost) return BF_OK;
     const size_t base = m->mesh.size();                                       // copyTrianglesToCPU: append to m_meshData
     m->mesh.resize(base + m->numTriangles);
     if (m->numTriangles) BF_HIP_TRY(hipMemcpy(m->mesh.data() + base, m->d_triangles, sizeof(bf_mc_triangle) * (size_t)m->numTriangles, hipMemcpyDeviceToHost));
     return BF_OK;
+}
+
+extern "C" {
+
+int bf_marching_cubes_extract(bf_marching_cubes* m, const bf_hash_data* hd, const bf_hash_params* hp, const float minCorner[3], const float maxCorner[3], int boxEnabled) {
+    return mcExtract(m, hd, hp, minCorner, maxCorner, boxEnabled, true);
+}
+// the same extraction without the host copy: m_meshData keeps what it held
+int bf_marching_cubes_extract_gpu(bf_marching_cubes* m, const bf_hash_data* hd, const bf_hash_params* hp, const float minCorner[3], const float maxCorner[3], int boxEnabled) {
+    return mcExtract(m, hd, hp, minCorner, maxCorner, boxEnabled, false);
 }
 
 int bf_marching_cubes_get_triangles_gpu(bf_marching_cubes* m, const bf_mc_triangle** d_triangles, uint32_t* numTriangles, uint32_t* numFound) {
@@ -448,23 +477,44 @@ int bf_marching_cubes_save_mesh(bf_marching_cubes* m, const char* filename, cons
         m44 T; memcpy(T.e, transform, 64);
         for (size_t i = 0; i < pos.size(); i += 3) { const f3 q = xform(T, mk3(pos[i], pos[i + 1], pos[i + 2])); pos[i] = q.x; pos[i + 1] = q.y; pos[i + 2] = q.z; }
     }
-    FILE* f = fopen(filename, "wb");
-    if (!f) { set_error("cannot open %s", filename); return BF_ERR_INVALID_ARG; }
     const uint32_t nv = (uint32_t)(pos.size() / 3), nf = (uint32_t)(faces.size() / 3);
-    fprintf(f, "ply\nformat binary_little_endian 1.0\ncomment bundlefusion_amd marching cubes\nelement vertex %u\nproperty float x\nproperty float y\nproperty float z\n"
-               "property uchar red\nproperty uchar green\nproperty uchar blue\nproperty uchar alpha\nelement face %u\nproperty list uchar int vertex_indices\nend_header\n", nv, nf);
-    for (uint32_t i = 0; i < nv; ++i) {
-        fwrite(&pos[3 * i], 4, 3, f);
-        uint8_t c[4];
-        for (int k = 0; k < 3; ++k) c[k] = (uint8_t)std::max(0.0f, std::min(255.0f, col[3 * i + k] * 255.0f + 0.5f));
-        c[3] = 255;
-        fwrite(c, 1, 4, f);
-    }
-    for (uint32_t i = 0; i < nf; ++i) { const uint8_t three = 3; fwrite(&three, 1, 1, f); int32_t idx[3] = {(int32_t)faces[3 * i], (int32_t)faces[3 * i + 1], (int32_t)faces[3 * i + 2]}; fwrite(idx, 4, 3, f); }
-    fclose(f);
+    BF_TRY(bf_write_ply_indexed(filename, pos.data(), col.data(), faces.data(), nv, nf));
     if (numVertices) *numVertices = nv;
     if (numFaces) *numFaces = nf;
     m->mesh.clear();                                                            // clearMeshBuffer() at the end of saveMesh
+    return BF_OK;
+}
+
+// The same mesh from a triangle buffer in HBM (meshweld.hip); d_triangles null: the last extraction.  On the object's stream.
+int bf_marching_cubes_weld(bf_marching_cubes* m, const bf_mc_triangle* d_triangles, uint32_t numTriangles, const float transform[16], bf_indexed_mesh* out) {
+    BF_REQUIRE(m, "null argument");
+    if (!d_triangles) { d_triangles = m->d_triangles; numTriangles = m->numTriangles; }
+    BF_TRY(meshweld_run(m->weld, m->stream, d_triangles, numTriangles, transform));
+    if (out) { out->d_positions = m->weld.d_positions; out->d_colors = m->weld.d_colors; out->d_faces = m->weld.d_faces; out->numVertices = m->weld.numVertices; out->numFaces = m->weld.numFaces; }
+    return BF_OK;
+}
+
+int bf_marching_cubes_download_indexed(bf_marching_cubes* m, float* h_positions, float* h_colors, uint32_t* h_faces) {
+    BF_REQUIRE(m, "null argument");
+    const MeshWeld& w = m->weld;
+    if (h_positions && w.numVertices) BF_HIP_TRY(hipMemcpyAsync(h_positions, w.d_positions, 12 * (size_t)w.numVertices, hipMemcpyDeviceToHost, m->stream));
+    if (h_colors && w.numVertices) BF_HIP_TRY(hipMemcpyAsync(h_colors, w.d_colors, 12 * (size_t)w.numVertices, hipMemcpyDeviceToHost, m->stream));
+    if (h_faces && w.numFaces) BF_HIP_TRY(hipMemcpyAsync(h_faces, w.d_faces, 12 * (size_t)w.numFaces, hipMemcpyDeviceToHost, m->stream));
+    BF_HIP_TRY(hipStreamSynchronize(m->stream));
+    return BF_OK;
+}
+
+// weld of the last extraction + download + the PLY writer; m_meshData is not touched
+int bf_marching_cubes_save_mesh_gpu(bf_marching_cubes* m, const char* filename, const float transform[16], uint32_t* numVertices, uint32_t* numFaces) {
+    BF_REQUIRE(m && filename, "null argument");
+    bf_indexed_mesh im;
+    BF_TRY(bf_marching_cubes_weld(m, nullptr, 0, transform, &im));
+    std::vector<float> pos(3 * (size_t)im.numVertices), col(3 * (size_t)im.numVertices);
+    std::vector<uint32_t> faces(3 * (size_t)im.numFaces);
+    BF_TRY(bf_marching_cubes_download_indexed(m, pos.data(), col.data(), faces.data()));
+    BF_TRY(bf_write_ply_indexed(filename, pos.data(), col.data(), faces.data(), im.numVertices, im.numFaces));
+    if (numVertices) *numVertices = im.numVertices;
+    if (numFaces) *numFaces = im.numFaces;
     return BF_OK;
 }
 

@@ -42,11 +42,11 @@ int VolumeQueue::dispatch(const Cmd& c, bool batch) {
         return bf_scene_garbage_collect(scene_);
     case Op::Flush:
         return submitPending();
-    case Op::Render: {
+    case Op::Render: case Op::SaveMesh: {
         BF_TRY(submitPending());
         const int rc = c.render ? c.render(c.renderCtx) : BF_ERR_INVALID_ARG;
         if (c.reply) { c.reply->rc = rc; if (rc != BF_OK) c.reply->message = bf_last_error(); }
-        return BF_OK;               // a picture that failed is its poster's business, not the volume's
+        return BF_OK;               // a picture or a mesh that failed is its poster's business, not the volume's
     }
     }
     return BF_ERR_INVALID_ARG;      // (not an Op)

@@ -1,9 +1,10 @@
 // Plays a recorded ".sens" file through the whole-loop C entry points (bf_pipeline_*: four streams, volume worker thread,
 // one-frame detection look-ahead) and evaluates the optimised trajectory against the poses stored in the file.
 // Build:  g++ -std=c++17 -I include examples/sens_pipeline.cpp -L bundlefusion_amd/lib -lbf_hip -Wl,-rpath,$PWD/bundlefusion_amd/lib -o sens_pipeline
-// Run:    ./sens_pipeline sequence.sens [--ingest host|device] [--decode-threads N] [zParametersDefault.txt zParametersBundlingDefault.txt]
+// Run:    ./sens_pipeline sequence.sens [--ingest host|device] [--decode-threads N] [zParametersDefault.txt zParametersBundlingDefault.txt] [scan.ply]
 //   --ingest host    (default) frames are decoded to float depth / RGBX on this thread (SensorDataReader) and handed over as host buffers
 //   --ingest device  SensPlayer: N threads (default 4, at most 12) decode ahead; depth conversion and JPEG reconstruction run on the device.  Same results.
+//   scan.ply         (a trailing argument ending in .ply) the scan's mesh after the end of the sequence: bf_pipeline_save_mesh
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -14,7 +15,7 @@
 using namespace bundlefusion;
 
 int main(int argc, char** argv) {
-    if (argc < 2) { std::printf("usage: %s sequence.sens [--ingest host|device] [--decode-threads N] [zParametersDefault.txt zParametersBundlingDefault.txt]\n", argv[0]); return 0; }
+    if (argc < 2) { std::printf("usage: %s sequence.sens [--ingest host|device] [--decode-threads N] [zParametersDefault.txt zParametersBundlingDefault.txt] [scan.ply]\n", argv[0]); return 0; }
     try {
         bool deviceIngest = false;
         unsigned int decodeThreads = 4;
@@ -23,6 +24,11 @@ int main(int argc, char** argv) {
             if (!std::strcmp(argv[i], "--ingest") && i + 1 < argc) { deviceIngest = !std::strcmp(argv[++i], "device"); }
             else if (!std::strcmp(argv[i], "--decode-threads") && i + 1 < argc) decodeThreads = (unsigned int)std::atoi(argv[++i]);
             else files.push_back(argv[i]);
+        }
+        const char* meshPath = nullptr;
+        if (!files.empty()) {
+            const size_t len = std::strlen(files.back());
+            if (len > 4 && !std::strcmp(files.back() + len - 4, ".ply")) { meshPath = files.back(); files.pop_back(); }
         }
         GlobalAppState& gas = GlobalAppState::get();
         GlobalBundlingState& gbs = GlobalBundlingState::get();
@@ -61,6 +67,11 @@ int main(int argc, char** argv) {
         check(bf_pipeline_get_counters(p, &nInt, &nDe, &nLocal, &nGlobal));
         std::printf("%s: %u frames, %u integrations, %u de-integrations, %u local / %u global solves\n", sensor.getSensorName().c_str(), frames, nInt, nDe, nLocal, nGlobal);
         sensor.evaluateTrajectory(trajectory);
+        if (meshPath) {
+            uint32_t nv = 0, nf = 0, nt = 0;
+            check(bf_pipeline_save_mesh(p, meshPath, nullptr, &nv, &nf, &nt));
+            std::printf("%s: %u vertices, %u faces from %u triangles\n", meshPath, nv, nf, nt);
+        }
         check(bf_pipeline_destroy(p));
     } catch (const std::exception& e) {
         std::printf("error: %s\n", e.what());

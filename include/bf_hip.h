@@ -675,6 +675,26 @@ BF_API int bf_marching_cubes_get_mesh(bf_marching_cubes* m, bf_mc_triangle* h_ou
 BF_API int bf_marching_cubes_clear_mesh_buffer(bf_marching_cubes* m);                                                     /* clearMeshBuffer */
 /* saveMesh(filename, transform)  .cpp:48-105: merge vertices closer than 1e-5, drop duplicate / degenerate faces, binary PLY */
 BF_API int bf_marching_cubes_save_mesh(bf_marching_cubes* m, const char* filename, const float transform[16], uint32_t* numVertices, uint32_t* numFaces);
+/* ---- MI355X additions: the mesh without the triangles leaving HBM (csrc/meshweld.hip) ----
+ * bf_marching_cubes_create with m_maxNumTriangles == 0: every extraction sizes the triangle buffer to the volume (the count is known before anything is
+ * written), so nothing is clamped; with a capacity the buffer and its clamping are the reference's. */
+/* extractIsoSurface without copyTrianglesToCPU: m_meshData keeps what it held; bf_marching_cubes_get_triangles_gpu reports the result */
+BF_API int bf_marching_cubes_extract_gpu(bf_marching_cubes* m, const bf_hash_data* hashData, const bf_hash_params* hashParams,
+                                         const float minCorner[3], const float maxCorner[3], int boxEnabled);
+/* the indexed mesh in HBM: positions and colours numVertices x 3 float, faces numFaces x 3 uint32; owned by the object, valid until its next extract, weld or destroy */
+typedef struct bf_indexed_mesh { const float* d_positions; const float* d_colors; const uint32_t* d_faces; uint32_t numVertices, numFaces; } bf_indexed_mesh;
+/* saveMesh's merge on the device, with exactly its result: a corner's key is (int64)floor((double)p * (1.0 / 0.00001) + 0.5) per axis; the vertex of a key is its
+ * first corner in triangle order and vertex ids follow first occurrence; faces with two equal ids are dropped, of faces with the same id set the first is kept,
+ * in triangle order with its winding; transform (row-major, may be NULL) is applied to the welded positions.  d_triangles NULL: the last extraction (then
+ * numTriangles is ignored).  Zero triangles give an empty mesh.  Runs on the object's stream and waits for it. */
+BF_API int bf_marching_cubes_weld(bf_marching_cubes* m, const bf_mc_triangle* d_triangles, uint32_t numTriangles, const float transform[16], bf_indexed_mesh* out);
+/* host copies of the last weld's arrays (any of them may be NULL) */
+BF_API int bf_marching_cubes_download_indexed(bf_marching_cubes* m, float* h_positions, float* h_colors, uint32_t* h_faces);
+/* weld of the last extraction + download + bf_write_ply_indexed: the file bf_marching_cubes_save_mesh writes for the same triangles; m_meshData is not touched */
+BF_API int bf_marching_cubes_save_mesh_gpu(bf_marching_cubes* m, const char* filename, const float transform[16], uint32_t* numVertices, uint32_t* numFaces);
+/* the PLY writer of both routes (host only): binary little-endian, vertex = 3 floats + RGBA bytes ((uint8)max(0, min(255, c * 255.0f + 0.5f)), alpha 255),
+ * face = count byte 3 + 3 int32 */
+BF_API int bf_write_ply_indexed(const char* filename, const float* h_positions, const float* h_colors, const uint32_t* h_faces, uint32_t numVertices, uint32_t numFaces);
 /* the generated case tables (edge mask per case, up to 5 triangles of edge indices, -1 terminated), for inspection / tests */
 BF_API int bf_marching_cubes_tables(uint16_t edgeTable[256], int8_t triTable[256 * 16]);
 

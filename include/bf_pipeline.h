@@ -387,6 +387,13 @@ BF_API int bf_pipeline_process_frame_raw_device(bf_pipeline* p, const uint16_t* 
 /* one iteration after the sensor stopped delivering frames (solve + re-integration continue, :175-196) */
 BF_API int bf_pipeline_process_end_of_sequence(bf_pipeline* p, uint32_t* numActiveOperations);
 BF_API int bf_pipeline_synchronize(bf_pipeline* p);
+/* The scan's mesh from inside the frame loop (StopScanningAndExtractIsoSurfaceMC, DepthSensing.cpp:335-368; MI355X addition): marching cubes over the whole volume,
+ * the weld on the device (bf_marching_cubes_weld), one binary PLY - the file bf_marching_cubes_extract + bf_marching_cubes_save_mesh write for the same volume.
+ * The frames handed in so far are completed first, as by any accessor.  The save is a command of the volume thread's queue, like a render (bf_render.h): executed
+ * between two frames' batches, the caller waits for its own command only; it does not change the reconstruction.  The pipeline creates its marching-cubes object
+ * on first use (thresholds of parametersFromGlobalAppState, factor 10) and sizes the triangle buffer to the volume: *numTriangles is the full count, never clamped.
+ * transform: row-major 4x4 applied to the welded vertices, or NULL; the three counts may be NULL.  With a volume shard or a communicator set it is an error. */
+BF_API int bf_pipeline_save_mesh(bf_pipeline* p, const char* filename, const float* transform, uint32_t* numVertices, uint32_t* numFaces, uint32_t* numTriangles);
 BF_API int bf_pipeline_get_scene(bf_pipeline* p, bf_scene** out);
 BF_API int bf_pipeline_get_image_manager(bf_pipeline* p, bf_image_manager** out);
 BF_API int bf_pipeline_get_online_bundler(bf_pipeline* p, bf_online_bundler** out);

@@ -815,6 +815,20 @@ public:
         uint32_t nv, nf;
         check(bf_marching_cubes_save_mesh(m_h, filename.c_str(), transform ? transform->m : nullptr, &nv, &nf));
     }
+    // MI355X additions (like setDeferredBatching): the mesh without the triangles leaving HBM.  extractIsoSurfaceGPU is extractIsoSurface without copyTrianglesToCPU
+    // (m_meshData keeps what it held); saveMeshGPU merges the last extraction's vertices on the device and writes the file saveMesh writes for the same triangles.
+    // With m_maxNumTriangles == 0 in the parameters every extraction sizes the triangle buffer to the volume.
+    void extractIsoSurfaceGPU(const HashDataStruct& hashData, const HashParams& hashParams, const vec3f& minCorner = vec3f(0.0f, 0.0f, 0.0f),
+                              const vec3f& maxCorner = vec3f(0.0f, 0.0f, 0.0f), bool boxEnabled = false) {
+        const float mn[3] = {minCorner.x, minCorner.y, minCorner.z}, mx[3] = {maxCorner.x, maxCorner.y, maxCorner.z};
+        check(bf_marching_cubes_extract_gpu(m_h, &hashData, &hashParams, mn, mx, boxEnabled ? 1 : 0));
+    }
+    void saveMeshGPU(const std::string& filename, const mat4f* transform = nullptr, unsigned int* numVertices = nullptr, unsigned int* numFaces = nullptr) {
+        uint32_t nv = 0, nf = 0;
+        check(bf_marching_cubes_save_mesh_gpu(m_h, filename.c_str(), transform ? transform->m : nullptr, &nv, &nf));
+        if (numVertices) *numVertices = nv;
+        if (numFaces) *numFaces = nf;
+    }
     bf_marching_cubes* handle() const { return m_h; }
 private:
     MarchingCubesParams m_params;

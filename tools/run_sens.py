@@ -2,7 +2,9 @@
 optimised trajectory against the poses stored in the file (SensorDataReader::evaluateTrajectory).
 
 usage: python tools/run_sens.py sequence.sens [--voxel 0.01] [--app zParametersDefault.txt] [--bundling zParametersBundlingDefault.txt]
-                                [--ingest host|device] [--decode-threads N] [--camera-calibration]
+                                [--ingest host|device] [--decode-threads N] [--camera-calibration] [--mesh scan.ply] [--mesh-host scan_host.ply]
+--mesh: the scan's mesh after the end of the sequence, extracted and welded on the device (bf_pipeline_save_mesh); --mesh-host: the same file by the host route
+(bf_marching_cubes_extract + bf_marching_cubes_save_mesh).  Both print the vertex, face and triangle counts and the seconds spent.
 --camera-calibration: s_bUseCameraCalibration = true - register every frame's depth to the colour camera with the extrinsics and intrinsics of the file's
 header (a file whose depth extrinsics are the identity has nothing to register; the line below says whether it is active).
 --ingest host (default): frames are decoded on the host and handed over as host buffers (the PCIe path of bf_pipeline_process_frame).
@@ -19,6 +21,7 @@ import numpy as np
 
 import bundlefusion_amd as bf
 from bundlefusion_amd import sensordata as sdm
+from tools import mesh_out
 
 
 def main():
@@ -36,6 +39,7 @@ def main():
     ap.add_argument("--decoder", choices=("auto", "builtin"), default="auto", help="--ingest host: auto decodes JPEG / PNG with Pillow where it is installed, builtin with the library's decoder")
     ap.add_argument("--camera-calibration", action="store_true", help="s_bUseCameraCalibration = true (a parameter file given with --app may set it as well)")
     ap.add_argument("--save", default=None, help="write a copy of the file with the optimised trajectory (SensorDataReader::saveToFile)")
+    mesh_out.add_arguments(ap)
     a = ap.parse_args()
     sd = sdm.SensorData(a.sens, use_pillow=a.ingest == "host" and a.decoder == "auto")        # (the player's workers decode with the library's own decoder)
     n = len(sd) if a.frames <= 0 else min(a.frames, len(sd))
@@ -84,6 +88,7 @@ def main():
     if a.save:
         sd.save_with_trajectory(a.save, traj)
         print("wrote", a.save)
+    mesh_out.write(p, a)
 
 
 if __name__ == "__main__":

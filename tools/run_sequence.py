@@ -1,6 +1,6 @@
 """Run the headless BundleFusion frame loop on a synthetic S2 stream and report poses / timings.
 
-usage: python tools/run_sequence.py [--frames N] [--voxel 0.01] [--host] [--timings]
+usage: python tools/run_sequence.py [--frames N] [--voxel 0.01] [--host] [--timings] [--mesh scan.ply] [--mesh-host scan_host.ply]
 """
 import argparse
 import sys
@@ -14,6 +14,7 @@ import torch
 import bundlefusion_amd as bf
 from bundlefusion_amd import synth
 from bundlefusion_amd.capi import intrinsics_matrix
+from tools import mesh_out
 
 
 def main():
@@ -32,6 +33,7 @@ def main():
     ap.add_argument("--timings-from", type=int, default=-1, help="switch the synchronous per-stage timings on at this frame")
     ap.add_argument("--bob", type=float, default=0.0, help="vertical sinusoid amplitude of the trajectory [m] (SURVEY.md 8d config 4: 0.3)")
     ap.add_argument("--maximages", type=int, default=0)
+    mesh_out.add_arguments(ap)
     a = ap.parse_args()
     W, H = a.width, a.height
     idx = [a.first + k * a.stride for k in range(a.frames)]
@@ -92,6 +94,7 @@ def main():
             print("%s: %d frames, none valid" % (name, n))
     sc = p.scene()
     print("allocated blocks", sc.num_allocated_blocks(), "heap free", sc.heap_free_count(), "debug", sc.debug_hash())
+    mesh_out.write(p, a)
     if tl:
         keys = [k for k in tl[0].keys() if k != "frame"]
         for name, sel in (("all frames", lambda f: True), ("chunk-end frames", lambda f: f % 10 == 9), ("other frames", lambda f: f % 10 != 9)):
