@@ -1043,6 +1043,16 @@ def jpeg_reconstruct_device(info, coefficients, planes, rgbx, stream=0):
     return True
 
 
+def image_convert_depth_to_u16(out, inp, depth_shift, stream=0):
+    """float32 metres -> u16, the recording's rule (bf_image_convert_depth_to_u16); torch device tensors, out.numel() == inp.numel()"""
+    check(lib.bf_image_convert_depth_to_u16(_p(out), _p(inp), C.c_float(depth_shift), inp.numel(), C.c_void_p(stream)))
+
+
+def jpeg_forward_device(rgbx, width, height, quality, coefficients, stream=0):
+    """RGBX8 device image -> quantised coefficients, int16 device tensor of ceil(w/8) * ceil(h/8) * 192 values in bf_jpeg_forward_host's layout"""
+    check(lib.bf_jpeg_forward_device(_p(rgbx), int(width), int(height), int(quality), _p(coefficients), C.c_void_p(stream)))
+
+
 def _raw_colour(colour, jpeg):
     """the colour argument of the *_raw_decoded / *_raw_device calls as (pointer, keep-alive)"""
     if isinstance(colour, np.ndarray):
@@ -1422,6 +1432,16 @@ class Pipeline:
         check(lib.bf_pipeline_save_mesh(self._h, str(filename).encode(), T, C.byref(nv), C.byref(nf), C.byref(nt)))
         return nv.value, nf.value, nt.value
 
+    def set_record_state(self, state, threads=0, tmp_prefix=None):
+        """bf_pipeline_set_record_state: before the first frame; with state.s_recordData every accepted frame is recorded (include/bf_record.h)"""
+        check(lib.bf_pipeline_set_record_state(self._h, C.byref(state), int(threads), str(tmp_prefix).encode() if tmp_prefix is not None else None))
+
+    def save_recording(self, filename=None, overwrite=False):
+        """bf_pipeline_save_recording: the recorded frames that have an optimised pose, as a .sens.  filename None: s_recordDataFile.  Returns (name written, frames)."""
+        name = C.create_string_buffer(4096); n = C.c_uint64()
+        check(lib.bf_pipeline_save_recording(self._h, str(filename).encode() if filename is not None else None, int(bool(overwrite)), name, C.c_uint64(len(name)), C.byref(n)))
+        return name.value.decode(), n.value
+
     def scene(self):
         """Borrowed SceneRepHashSDF view of the pipeline's voxel-hash volume."""
         h = C.c_void_p()
@@ -1798,6 +1818,23 @@ def default_render_state(path=None, with_missing=False):
         check(lib.bf_render_state_default(C.byref(g)))
     else:
         check(lib.bf_render_state_read(str(path).encode(), C.byref(g), C.byref(n)))
+    return (g, n.value) if with_missing else g
+
+
+# --------------------------------------------------------------------------- recording (include/bf_record.h)
+class RecordState(C.Structure):
+    """bf_record_state: the recording keys of zParametersDefault.txt"""
+    _fields_ = [("s_recordData", C.c_int32), ("s_recordCompression", C.c_int32), ("s_recordDataWidth", C.c_uint32), ("s_recordDataHeight", C.c_uint32),
+                ("s_recordDataFile", C.c_char * 512)]
+
+
+def default_record_state(path=None, with_missing=False):
+    """bf_record_state_default, or bf_record_state_read of a parameter file (with_missing: also the number of fields the file does not name)"""
+    g = RecordState(); n = C.c_uint32()
+    if path is None:
+        check(lib.bf_record_state_default(C.byref(g)))
+    else:
+        check(lib.bf_record_state_read(str(path).encode(), C.byref(g), C.byref(n)))
     return (g, n.value) if with_missing else g
 
 

@@ -22,6 +22,7 @@
 
 #include "../../include/bf_pipeline.h"
 #include "../../include/bf_comm.h"
+#include "../../include/bf_record.h"
 #include "../../include/bf_render.h"
 #include "../../include/bf_sensordata.h"
 #include "bf_device.h"
@@ -193,6 +194,9 @@ struct bf_image_manager {
     bf_image_calibrator* calib = nullptr;
     float calibThreshOffset = 0.0f, calibThreshLin = 0.0f;
     m44 calibColorIntrinsics, calibDepthIntrinsicsInv;
+    // s_recordData (bf_pipeline_set_record_state): the pipeline's recorder, or null.  Every accepted frame is packed on the ingest stream from the sensor's own
+    // images, before anything registers, erodes or filters them
+    bf_sens_recorder* recorder = nullptr;
     size_t nInt() const { return (size_t)wInt * hInt; }
     // sensor-format ingest (bf_image_manager_process_raw*), allocated at its first use.  Device side: the uploaded u16 / RGB8 / coefficient bytes, the decoder's sample
     // planes and the converted frame - one set: every user is on `stream`, in order.  Host side: NSETS pinned staging slots (frame n copies into slot n % NSETS; the
@@ -354,6 +358,7 @@ static int im_process(bf_image_manager* im, const float* depth, const uint8_t* c
     // images in three launches - erosion 1 straight from the caller's depth with the colour copies riding along, erosion 2, depth filter writing the stored frame too
     if (kind == hipMemcpyDeviceToDevice && im->onGPU && !im->storeTexels && nc == nd && sn.colorWidth == im->wInt && sn.colorHeight == im->hInt && sn.depthWidth == im->wInt &&
         sn.depthHeight == im->hInt && im->gbs.s_erodeSIFTdepth && im->gbs.s_depthFilter) {
+        if (im->recorder) BF_TRY(bf_sens_recorder_record_device(im->recorder, depth, color, st));      // this path never copies the raw depth: pack the caller's
         if (im->calib) {                                    // registration needs the frame in a buffer of the manager's: one copy more, the erosion then reads that
             BF_HIP_TRY(hipMemcpyAsync(im->d_depthInputRaw, depth, nd * 4, kind, st));
             BF_TRY(im_register_depth(im));
@@ -374,6 +379,7 @@ static int im_process(bf_image_manager* im, const float* depth, const uint8_t* c
     else BF_TRY(bf_image_resample_uchar4(colorDst, im->wInt, im->hInt, im->d_colorInput, sn.colorWidth, sn.colorHeight, st));
     // ---- depth  (.cpp:66-112): two 7x7 erosions ping-pong (the twice-eroded map ends in d_depthInputRaw), then the range-gated Gaussian
     BF_HIP_TRY(hipMemcpyAsync(im->d_depthInputRaw, depth, nd * 4, kind, st));
+    if (im->recorder) BF_TRY(bf_sens_recorder_record_device(im->recorder, im->d_depthInputRaw, im->d_colorInput, st));   // the input set as uploaded; overwritten from here on
     if (im->calib) BF_TRY(im_register_depth(im));
     if (im->gbs.s_erodeSIFTdepth) {
         BF_TRY(bf_image_erode_depth_map(im->d_depthInputFiltered, im->d_depthInputRaw, 3, sn.depthWidth, sn.depthHeight, 0.05f, 0.3f, st));
@@ -2141,6 +2147,8 @@ struct bf_pipeline {
     // the volume thread's queue, like a render.  A shard of the volume lacks its neighbours' blocks, so a sharded loop refuses
     bf_marching_cubes* marchingCubes = nullptr;
     bool volumeSharded = false, volumeComm = false;
+    // The recording (bf_record.h): with s_recordData the pipeline owns a recorder, which the image manager feeds at every accepted frame
+    bf_sens_recorder* recorder = nullptr; bf_record_state recordState;
     bool timings = false;
     hipEvent_t ev[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     bf_frame_timing last;
@@ -2603,11 +2611,57 @@ int bf_pipeline_save_mesh(bf_pipeline* p, const char* filename, const float* tra
     return BF_OK;
 }
 
+// ---- the recording (bf_record.h): s_recordData, DepthSensing.cpp:1042-1045 and :475-483
+int bf_pipeline_set_record_state(bf_pipeline* p, const bf_record_state* state, uint32_t numThreads, const char* tmpPrefix) {
+    BF_REQUIRE(p && state, "null argument");
+    BF_REQUIRE(p->im->currFrame == 0 && !p->recorder, "set_record_state after the first frame, or twice");
+    BF_REQUIRE(memchr(state->s_recordDataFile, 0, sizeof state->s_recordDataFile) != nullptr, "s_recordDataFile is not terminated");
+    if (state->s_recordData && !state->s_recordCompression) {
+        set_error("bf_pipeline_set_record_state: s_recordCompression = false asks for the legacy uncompressed .sensor container, which is not written; record with s_recordCompression = true (.sens)");
+        return BF_ERR_INVALID_ARG;
+    }
+    p->recordState = *state;
+    if (!state->s_recordData) return BF_OK;
+    bf_sensor_data_info info;                                                     // RGBDSensor.cpp:269-280
+    memset(&info, 0, sizeof info);
+    info.versionNumber = 4;
+    snprintf(info.sensorName, sizeof info.sensorName, "%s", "RGBDSensor");
+    memcpy(info.colorIntrinsic, p->sensor.colorIntrinsics, 64); memcpy(info.colorExtrinsic, p->sensor.colorExtrinsics, 64);
+    memcpy(info.depthIntrinsic, p->sensor.depthIntrinsics, 64); memcpy(info.depthExtrinsic, p->sensor.depthExtrinsics, 64);
+    info.colorCompressionType = BF_SENS_COLOR_JPEG; info.depthCompressionType = BF_SENS_DEPTH_ZLIB_USHORT;
+    info.colorWidth = p->sensor.colorWidth; info.colorHeight = p->sensor.colorHeight; info.depthWidth = p->sensor.depthWidth; info.depthHeight = p->sensor.depthHeight;
+    info.depthShift = 1000.0f;
+    const std::string tmp = std::string(tmpPrefix ? tmpPrefix : "./bf_") + std::to_string((unsigned long long)(uintptr_t)p) + ".rec.sens";
+    BF_TRY(bf_sens_recorder_create(p, &info, tmp.c_str(), numThreads, 0, &p->recorder));
+    p->im->recorder = p->recorder;
+    return BF_OK;
+}
+
+int bf_pipeline_save_recording(bf_pipeline* p, const char* filename, int overwrite, char* actualName, uint64_t capacity, uint64_t* numFramesWritten) {
+    BF_REQUIRE(p, "null argument");
+    if (numFramesWritten) *numFramesWritten = 0;
+    if (!p->recorder) { set_error("bf_pipeline_save_recording: the pipeline does not record (bf_pipeline_set_record_state with s_recordData)"); return BF_ERR_STATE; }
+    BF_TRY(plFlush(p));
+    bf_trajectory_manager* tm = nullptr;
+    BF_TRY(bf_online_bundler_get_trajectory_manager(p->ob, &tm));
+    uint32_t n = 0;
+    BF_TRY(bf_trajectory_manager_get_num_optimized_frames(tm, &n));
+    uint64_t recorded = 0;
+    BF_TRY(bf_sens_recorder_get_num_recorded(p->recorder, &recorded));
+    std::vector<float> T((size_t)std::max(n, 1u) * 16);
+    uint32_t count = 0;
+    if (n) BF_TRY(bf_trajectory_manager_get_optimized_transforms(tm, T.data(), n, &count));
+    // (a second save without new frames finds nothing recorded and writes nothing, whatever the trajectory holds)
+    return bf_sens_recorder_finish(p->recorder, filename ? filename : p->recordState.s_recordDataFile, T.data(), recorded ? count : 0, overwrite, actualName, capacity, numFramesWritten);
+}
+
 int bf_pipeline_destroy(bf_pipeline* p) {
     if (!p) return BF_OK;
     p->vol.stop();
     (void)hipDeviceSynchronize();
     bf_marching_cubes_destroy(p->marchingCubes);
+    if (p->im) p->im->recorder = nullptr;
+    bf_sens_recorder_destroy(p->recorder);
     bf_ray_cast_destroy(p->rayCast); bf_frame_renderer_destroy(p->renderer); bf_frame_renderer_destroy(p->inputRenderer);
     if (!p->tracePath.empty() && !p->trace.empty()) {
         if (FILE* f = fopen(p->tracePath.c_str(), "a")) {

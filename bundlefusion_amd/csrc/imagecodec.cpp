@@ -20,6 +20,7 @@
 
 #include "../../include/bf_sensordata.h"
 #include "bf_internal.h"
+#include "bf_jpeg_fwd.h"
 #include "bf_jpeg_recon.h"
 
 using namespace bf;
@@ -430,11 +431,6 @@ int decodePng(const uint8_t* data, size_t size, uint32_t width, uint32_t height,
 // Baseline, 4:4:4, quantisation tables of Annex K scaled by `quality` like the IJG code, and Huffman tables optimised for the
 // image (two passes; code lengths limited to 16 bits by the procedure of Annex K.2).  ml::SensorData records colour with
 // stb_image_write's encoder; an encoder's output is not pinned by anything - any baseline decoder reads this one's.
-const uint8_t STD_LUMA_Q[64] = {16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
-                                18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99};
-const uint8_t STD_CHROMA_Q[64] = {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
-                                  99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
-
 struct HuffEnc { uint8_t bits[17]; uint8_t vals[256]; int nvals; uint16_t code[256]; uint8_t len[256]; };
 
 // optimal code lengths from symbol counts (Annex K.2 / jpeg_gen_optimal_table): a reserved pseudo-symbol keeps the all-ones code free
@@ -487,43 +483,44 @@ struct BitWriter {
 
 inline int bitSize(int v) { v = v < 0 ? -v : v; int n = 0; while (v) { ++n; v >>= 1; } return n; }
 
-void fdct8x8(float* d) {                                              // separable DCT-II, orthonormal scaling folded into the output (direct form: 8x8x8x2)
-    static float C[8][8]; static bool init = false;
-    if (!init) { for (int k = 0; k < 8; ++k) for (int n = 0; n < 8; ++n) C[k][n] = (k == 0 ? 0.35355339059327373f : 0.5f) * (float)std::cos((2 * n + 1) * k * 3.14159265358979323846 / 16.0); init = true; }
-    float t[64];
-    for (int r = 0; r < 8; ++r) for (int k = 0; k < 8; ++k) { float s = 0; for (int n = 0; n < 8; ++n) s += C[k][n] * d[r * 8 + n]; t[r * 8 + k] = s; }
-    for (int c = 0; c < 8; ++c) for (int k = 0; k < 8; ++k) { float s = 0; for (int n = 0; n < 8; ++n) s += C[k][n] * t[n * 8 + c]; d[k * 8 + c] = s; }
-}
-
-int encodeJpeg(const uint8_t* rgb, uint32_t W, uint32_t H, int quality, std::vector<uint8_t>& out) {
-    quality = quality < 1 ? 1 : (quality > 100 ? 100 : quality);
-    const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
+// forward stage: colour conversion, edge replication, the two DCT passes, quantisation, zigzag (arithmetic: bf_jpeg_fwd.h).
+// coef: per block y0 * bx + x0: Y, Cb, Cr, 64 values each in zigzag order.  stride: bytes per pixel (3 RGB, 4 RGBX - X ignored)
+void forwardJpeg(const uint8_t* px, int stride, uint32_t W, uint32_t H, int quality, int16_t* coef) {
+    namespace fw = bfjpegfwd;
+    struct Cos { float c[64]; Cos() { bfjpegfwd::cosTable(c); } };
+    static const Cos cosines;                                         // initialised once, by whichever thread comes first
+    const float* C = cosines.c;
     uint8_t q[2][64];
-    for (int i = 0; i < 64; ++i) {
-        int a = ((int)STD_LUMA_Q[i] * scale + 50) / 100, b = ((int)STD_CHROMA_Q[i] * scale + 50) / 100;
-        q[0][i] = (uint8_t)(a < 1 ? 1 : (a > 255 ? 255 : a)); q[1][i] = (uint8_t)(b < 1 ? 1 : (b > 255 ? 255 : b));
-    }
+    fw::quantTables(quality, q);
     const uint32_t bx = (W + 7) / 8, by = (H + 7) / 8;
-    std::vector<int16_t> coef((size_t)bx * by * 3 * 64);              // quantised coefficients in zigzag order, per block: Y, Cb, Cr
-    float blk[3][64];
+    float blk[3][64], t[64], col[8];
     for (uint32_t y0 = 0; y0 < by; ++y0)
         for (uint32_t x0 = 0; x0 < bx; ++x0) {
             for (int yy = 0; yy < 8; ++yy)
                 for (int xx = 0; xx < 8; ++xx) {
                     const uint32_t x = std::min(x0 * 8 + xx, W - 1), y = std::min(y0 * 8 + yy, H - 1);      // edge replication
-                    const uint8_t* p = rgb + ((size_t)y * W + x) * 3;
-                    const float r = p[0], g = p[1], b = p[2];
-                    blk[0][yy * 8 + xx] = 0.299f * r + 0.587f * g + 0.114f * b - 128.0f;
-                    blk[1][yy * 8 + xx] = -0.168736f * r - 0.331264f * g + 0.5f * b;
-                    blk[2][yy * 8 + xx] = 0.5f * r - 0.418688f * g - 0.081312f * b;
+                    const uint8_t* p = px + ((size_t)y * W + x) * stride;
+                    fw::rgbToYcc(p[0], p[1], p[2], blk[0][yy * 8 + xx], blk[1][yy * 8 + xx], blk[2][yy * 8 + xx]);
                 }
             for (int c = 0; c < 3; ++c) {
-                fdct8x8(blk[c]);
-                int16_t* o = coef.data() + (((size_t)y0 * bx + x0) * 3 + c) * 64;
+                float* d = blk[c];
+                for (int r = 0; r < 8; ++r) for (int k = 0; k < 8; ++k) t[r * 8 + k] = fw::dct1(C + k * 8, d + r * 8);
+                for (int cc = 0; cc < 8; ++cc) {
+                    for (int n = 0; n < 8; ++n) col[n] = t[n * 8 + cc];
+                    for (int k = 0; k < 8; ++k) d[k * 8 + cc] = fw::dct1(C + k * 8, col);
+                }
+                int16_t* o = coef + (((size_t)y0 * bx + x0) * 3 + c) * 64;
                 const uint8_t* qt = q[c ? 1 : 0];
-                for (int i = 0; i < 64; ++i) { const float v = blk[c][ZIGZAG[i]] / (float)qt[ZIGZAG[i]]; o[i] = (int16_t)(v < 0 ? -(int)(-v + 0.5f) : (int)(v + 0.5f)); }
+                for (int i = 0; i < 64; ++i) o[i] = fw::quantise(d[ZIGZAG[i]], (float)qt[ZIGZAG[i]]);
             }
         }
+}
+
+// entropy stage: two Huffman passes with image-optimised tables, then headers and scan; needs nothing but the coefficients
+int entropyEncodeJpeg(uint32_t W, uint32_t H, int quality, const int16_t* coefData, std::vector<uint8_t>& out) {
+    uint8_t q[2][64];
+    bfjpegfwd::quantTables(quality, q);
+    const uint32_t bx = (W + 7) / 8, by = (H + 7) / 8;
     // pass 1: symbol statistics; pass 2: emit
     HuffEnc dcT[2], acT[2];
     std::vector<uint8_t> scan;
@@ -534,7 +531,7 @@ int encodeJpeg(const uint8_t* rgb, uint32_t W, uint32_t H, int quality, std::vec
         int pred[3] = {0, 0, 0};
         for (size_t b = 0; b < (size_t)bx * by; ++b)
             for (int c = 0; c < 3; ++c) {
-                const int16_t* o = coef.data() + (b * 3 + c) * 64;
+                const int16_t* o = coefData + (b * 3 + c) * 64;
                 const int t = c ? 1 : 0;
                 const int diff = o[0] - pred[c]; pred[c] = o[0];
                 const int s = bitSize(diff);
@@ -574,6 +571,12 @@ int encodeJpeg(const uint8_t* rgb, uint32_t W, uint32_t H, int quality, std::vec
     out.insert(out.end(), scan.begin(), scan.end());
     out.push_back(0xFF); out.push_back(0xD9);
     return BF_OK;
+}
+
+int encodeJpeg(const uint8_t* rgb, uint32_t W, uint32_t H, int quality, std::vector<uint8_t>& out) {
+    std::vector<int16_t> coef((size_t)((W + 7) / 8) * ((H + 7) / 8) * 3 * 64);
+    forwardJpeg(rgb, 3, W, H, quality, coef.data());
+    return entropyEncodeJpeg(W, H, quality, coef.data(), out);
 }
 
 }  // namespace
@@ -647,6 +650,34 @@ int bf_encode_jpeg_rgb(const uint8_t* rgb, uint32_t width, uint32_t height, int3
     static thread_local std::vector<uint8_t> buf;
     static thread_local const uint8_t* last = nullptr;
     if (!out || last != rgb || buf.empty()) { const int rc = encodeJpeg(rgb, width, height, quality, buf); if (rc) return rc; last = rgb; }
+    *size = buf.size();
+    if (!out) return BF_OK;
+    BF_REQUIRE(capacity >= buf.size(), "buffer too small");
+    memcpy(out, buf.data(), buf.size());
+    last = nullptr;
+    return BF_OK;
+} catch (const std::exception& e) {
+    set_error("jpeg encoder: %s", e.what());
+    return BF_ERR_STATE;
+}
+
+int bf_jpeg_forward_host(const uint8_t* pixels, uint32_t pixelStride, uint32_t width, uint32_t height, int32_t quality, int16_t* coefficients, uint64_t capacity) try {
+    BF_REQUIRE(pixels && coefficients && width > 0 && height > 0 && width < 65536 && height < 65536, "bad argument");
+    BF_REQUIRE(pixelStride == 3 || pixelStride == 4, "pixelStride must be 3 (RGB) or 4 (RGBX)");
+    BF_REQUIRE(capacity >= (uint64_t)((width + 7) / 8) * ((height + 7) / 8) * 192, "coefficient buffer too small");
+    forwardJpeg(pixels, (int)pixelStride, width, height, quality, coefficients);
+    return BF_OK;
+} catch (const std::exception& e) {
+    set_error("jpeg encoder: %s", e.what());
+    return BF_ERR_STATE;
+}
+
+// out == NULL: only *size (the stream is kept for the following call with a buffer, like bf_encode_jpeg_rgb)
+int bf_jpeg_entropy_encode(uint32_t width, uint32_t height, int32_t quality, const int16_t* coefficients, uint8_t* out, uint64_t capacity, uint64_t* size) try {
+    BF_REQUIRE(coefficients && size && width > 0 && height > 0 && width < 65536 && height < 65536, "bad argument");
+    static thread_local std::vector<uint8_t> buf;
+    static thread_local const int16_t* last = nullptr;
+    if (!out || last != coefficients || buf.empty()) { const int rc = entropyEncodeJpeg(width, height, quality, coefficients, buf); if (rc) return rc; last = coefficients; }
     *size = buf.size();
     if (!out) return BF_OK;
     BF_REQUIRE(capacity >= buf.size(), "buffer too small");

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/bf_pipeline.h"
+#include "../../include/bf_record.h"
 #include "../../include/bf_render.h"
 #include "bf_internal.h"
 
@@ -144,9 +145,40 @@ void readRender(Reader& r, bf_render_state& g) {
     r.fv("s_topVideoTransformWorld", g.s_topVideoTransformWorld, 16); r.fv("s_topVideoCameraPose", g.s_topVideoCameraPose, 4); r.fv("s_topVideoMinMax", g.s_topVideoMinMax, 2);
 }
 
+// the recording keys (GlobalAppState.h); one call per field of bf_record_state
+void readRecord(Reader& r, bf_record_state& g) {
+    r.b("s_recordData", g.s_recordData); r.b("s_recordCompression", g.s_recordCompression);
+    r.u("s_recordDataWidth", g.s_recordDataWidth); r.u("s_recordDataHeight", g.s_recordDataHeight);
+    if (auto* s = r.find("s_recordDataFile")) {                                          // a quoted string
+        std::string v = *s;
+        if (v.size() >= 2 && v.front() == '"' && v.back() == '"') v = v.substr(1, v.size() - 2);
+        snprintf(g.s_recordDataFile, sizeof g.s_recordDataFile, "%s", v.c_str());
+    }
+}
+
 }  // namespace
 
 extern "C" {
+
+int bf_record_state_default(bf_record_state* g) {                   // zParametersDefault.txt
+    BF_REQUIRE(g, "null argument");
+    memset(g, 0, sizeof *g);
+    g->s_recordData = 0; g->s_recordCompression = 1;
+    g->s_recordDataWidth = 640; g->s_recordDataHeight = 480;
+    snprintf(g->s_recordDataFile, sizeof g->s_recordDataFile, "%s", "dump/recording.sens");
+    return BF_OK;
+}
+
+int bf_record_state_read(const char* filename, bf_record_state* out, uint32_t* numMissing) {
+    BF_REQUIRE(filename && out, "null argument");
+    KV kv;
+    if (!parseFile(filename, kv)) { bf::set_error("cannot open parameter file %s", filename); return BF_ERR_INVALID_ARG; }
+    bf_record_state_default(out);
+    Reader r(kv);
+    readRecord(r, *out);
+    if (numMissing) *numMissing = r.missing;
+    return BF_OK;
+}
 
 int bf_render_state_default(bf_render_state* g) {                   // zParametersDefault.txt
     BF_REQUIRE(g, "null argument");

@@ -20,6 +20,7 @@
 #include <thread>
 #include <vector>
 
+#include "../../include/bf_record.h"
 #include "../../include/bf_sensordata.h"
 #include "bf_internal.h"
 
@@ -311,6 +312,18 @@ int bf_sensor_data_writer_add_frame(bf_sensor_data_writer* w, const float T[16],
     w->numFrames++;
     return BF_OK;
     });
+}
+
+int bf_sensor_data_writer_add_frame_compressed(bf_sensor_data_writer* w, const float T[16], uint64_t tsColor, uint64_t tsDepth, const uint8_t* colorBytes,
+                                               uint64_t colorSize, const uint8_t* depthBytes, uint64_t depthSize) {
+    BF_REQUIRE(w && T && depthBytes && (colorBytes || colorSize == 0), "null argument");
+    if (w->info.depthCompressionType == BF_SENS_DEPTH_RAW_USHORT) BF_REQUIRE(depthSize == (uint64_t)w->info.depthWidth * w->info.depthHeight * 2, "raw depth has the wrong size");
+    FILE* f = w->f;
+    const bool ok = wr(f, T, 16) && wr(f, &tsColor) && wr(f, &tsDepth) && wr(f, &colorSize) && wr(f, &depthSize) &&
+                    (colorSize == 0 || wr(f, colorBytes, colorSize)) && (depthSize == 0 || wr(f, depthBytes, depthSize));
+    if (!ok) { set_error("sens: write failed at frame %llu", (unsigned long long)w->numFrames); return BF_ERR_STATE; }
+    w->numFrames++;
+    return BF_OK;
 }
 
 int bf_sensor_data_writer_close(bf_sensor_data_writer* w) {
@@ -741,6 +754,289 @@ int bf_sens_player_next(bf_sens_player* pl, int* gotFrame) {
     if (rc) return rc;
     *gotFrame = got;
     return BF_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ recorder (bf_record.h): the player's mirror image
+// Frame k lives in slot k % numSlots.  The record call fills the slot's front half (coefficients + u16 depth: on the calling thread, or with two kernels and a
+// copy whose event the slot carries) and marks it FILLED; a worker claims the next FILLED frame in order, waits for the slot's copy event if it has one,
+// entropy-codes and deflates into the slot's blobs and marks it ENCODED.  The thread that finishes frame nextAppend appends it, and whatever is already
+// waiting behind it, to the temporary file - one appender at a time, so the file is in frame order whatever the threads' timing.
+struct bf_sens_recorder {
+    bool pinned = false; int device = 0;
+    bf_sensor_data_info info;
+    std::string tmp;
+    bf_sensor_data_writer* writer = nullptr;              // open while frames of the current recording exist; touched by the appender only (and by finish after the drain)
+    size_t coefCount = 0, depthCount = 0;
+    enum { FREE = 0, FILLING = 1, FILLED = 2, ENCODING = 3, ENCODED = 4 };
+    struct Slot {
+        int16_t* coef = nullptr; uint16_t* depth = nullptr;          // host
+        int16_t* d_coef = nullptr; uint16_t* d_depth = nullptr;      // device twin (pinned recorders)
+        hipEvent_t packed = nullptr, copied = nullptr;
+        bool onDevice = false;                            // this frame's front half arrives by the copy: wait for `copied`
+        int state = FREE; uint64_t frame = 0;
+        std::vector<uint8_t> jpeg, z; uint64_t jpegSize = 0, zSize = 0;
+    };
+    std::vector<Slot> slots;
+    hipStream_t copyStream = nullptr;
+    std::mutex m;
+    std::condition_variable cvWork, cvFree;
+    uint64_t nextRecord = 0, nextClaim = 0, nextAppend = 0;          // frames handed in / claimed by a worker / appended (or given up after an error)
+    bool appending = false, stop = false;
+    int rc = BF_OK; std::string err;                      // the first failure of a worker
+    std::vector<std::thread> threads;
+};
+
+namespace {
+
+const int RECORD_JPEG_QUALITY = 90;
+
+void recFail(bf_sens_recorder* r, int rc) {               // with r->m held
+    if (r->rc == BF_OK) { r->rc = rc; r->err = bf_last_error(); }
+}
+
+int recEncode(bf_sens_recorder* r, bf_sens_recorder::Slot& s) {
+    return guarded([&]() -> int {
+        if (s.onDevice && hipEventSynchronize(s.copied) != hipSuccess) { set_error("recorder: the copy of frame %llu failed (%s)", (unsigned long long)s.frame, hipGetErrorString(hipGetLastError())); return BF_ERR_HIP; }
+        const bf_sensor_data_info& h = r->info;
+        uint64_t n = 0;
+        BF_TRY(bf_jpeg_entropy_encode(h.colorWidth, h.colorHeight, RECORD_JPEG_QUALITY, s.coef, nullptr, 0, &n));
+        if (s.jpeg.size() < n) s.jpeg.resize(n);
+        BF_TRY(bf_jpeg_entropy_encode(h.colorWidth, h.colorHeight, RECORD_JPEG_QUALITY, s.coef, s.jpeg.data(), s.jpeg.size(), &n));
+        s.jpegSize = n;
+        const uint64_t rawBytes = (uint64_t)r->depthCount * 2;
+        if (h.depthCompressionType == BF_SENS_DEPTH_ZLIB_USHORT) {
+            uLongf bound = compressBound((uLong)rawBytes);
+            if (s.z.size() < bound) s.z.resize(bound);
+            if (compress2(s.z.data(), &bound, reinterpret_cast<const Bytef*>(s.depth), (uLong)rawBytes, 8) != Z_OK) { set_error("sens: zlib compression failed"); return BF_ERR_STATE; }
+            s.zSize = bound;
+        } else {
+            if (s.z.size() < rawBytes) s.z.resize(rawBytes);
+            memcpy(s.z.data(), s.depth, rawBytes);
+            s.zSize = rawBytes;
+        }
+        return BF_OK;
+    });
+}
+
+void recWorker(bf_sens_recorder* r) {
+    if (r->pinned) (void)hipSetDevice(r->device);
+    static const float I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    for (;;) {
+        bf_sens_recorder::Slot* s = nullptr;
+        {
+            std::unique_lock<std::mutex> lk(r->m);
+            r->cvWork.wait(lk, [&] { return r->stop || (r->nextClaim < r->nextRecord && r->slots[r->nextClaim % r->slots.size()].state == bf_sens_recorder::FILLED); });
+            if (r->stop) break;
+            s = &r->slots[r->nextClaim % r->slots.size()];
+            s->state = bf_sens_recorder::ENCODING; r->nextClaim++;
+        }
+        const int rc = recEncode(r, *s);
+        std::unique_lock<std::mutex> lk(r->m);
+        if (rc) recFail(r, rc);
+        s->state = bf_sens_recorder::ENCODED;
+        if (r->appending) continue;                       // the appender finds this frame when it gets there
+        r->appending = true;
+        for (;;) {
+            bf_sens_recorder::Slot& a = r->slots[r->nextAppend % r->slots.size()];
+            if (!(r->nextAppend < r->nextClaim && a.state == bf_sens_recorder::ENCODED && a.frame == r->nextAppend)) break;
+            const bool write = r->rc == BF_OK;            // after a failure the frames behind it are given up: the recording is lost, the ring keeps moving
+            lk.unlock();
+            int wrc = BF_OK;
+            if (write) {
+                if (!r->writer) wrc = bf_sensor_data_writer_create(r->tmp.c_str(), &r->info, &r->writer);
+                if (wrc == BF_OK) wrc = bf_sensor_data_writer_add_frame_compressed(r->writer, I, 0, 0, a.jpeg.data(), a.jpegSize, a.z.data(), a.zSize);
+            }
+            lk.lock();
+            if (wrc) recFail(r, wrc);
+            a.state = bf_sens_recorder::FREE; r->nextAppend++;
+            r->cvFree.notify_all();
+        }
+        r->appending = false;
+    }
+}
+
+// the slot of the next frame, free to fill (waits while the ring is full); null with the worker's status when one has failed
+int recAcquire(bf_sens_recorder* r, bf_sens_recorder::Slot** out) {
+    std::unique_lock<std::mutex> lk(r->m);
+    bf_sens_recorder::Slot& s = r->slots[r->nextRecord % r->slots.size()];
+    r->cvFree.wait(lk, [&] { return s.state == bf_sens_recorder::FREE; });
+    if (r->rc) { set_error("%s", r->err.c_str()); return r->rc; }
+    s.state = bf_sens_recorder::FILLING; s.frame = r->nextRecord;
+    *out = &s;
+    return BF_OK;
+}
+
+void recSubmit(bf_sens_recorder* r, bf_sens_recorder::Slot* s, bool filled) {
+    {
+        std::lock_guard<std::mutex> lk(r->m);
+        if (filled) { s->state = bf_sens_recorder::FILLED; r->nextRecord++; }
+        else s->state = bf_sens_recorder::FREE;
+    }
+    r->cvWork.notify_all();
+}
+
+bool fileExists(const std::string& f) { if (FILE* fp = fopen(f.c_str(), "rb")) { fclose(fp); return true; } return false; }
+
+}  // namespace
+
+extern "C" {
+
+int bf_sens_recorder_destroy(bf_sens_recorder* r) {
+    if (!r) return BF_OK;
+    {
+        std::lock_guard<std::mutex> lk(r->m);
+        r->stop = true;
+    }
+    r->cvWork.notify_all();
+    for (std::thread& t : r->threads) t.join();
+    if (r->writer) { bf_sensor_data_writer_close(r->writer); r->writer = nullptr; }
+    std::remove(r->tmp.c_str());
+    if (r->pinned) {
+        if (r->copyStream) (void)hipStreamSynchronize(r->copyStream);
+        for (bf_sens_recorder::Slot& s : r->slots) {
+            (void)hipHostFree(s.coef); (void)hipHostFree(s.depth); (void)hipFree(s.d_coef); (void)hipFree(s.d_depth);
+            if (s.packed) (void)hipEventDestroy(s.packed);
+            if (s.copied) (void)hipEventDestroy(s.copied);
+        }
+        if (r->copyStream) (void)hipStreamDestroy(r->copyStream);
+    } else {
+        for (bf_sens_recorder::Slot& s : r->slots) { free(s.coef); free(s.depth); }
+    }
+    delete r;
+    return BF_OK;
+}
+
+int bf_sens_recorder_create(bf_pipeline* pipeline, const bf_sensor_data_info* info, const char* tmpFilename, uint32_t numThreads, uint32_t numSlots, bf_sens_recorder** out) {
+    return guarded([&]() -> int {
+    BF_REQUIRE(info && tmpFilename && tmpFilename[0] && out, "null argument");
+    BF_REQUIRE(numThreads <= 12, "at most 12 encode threads");
+    BF_REQUIRE(numSlots == 0 || numSlots >= 2, "at least 2 slots");
+    BF_REQUIRE(numSlots <= 1024, "at most 1024 slots");
+    if (numThreads == 0) numThreads = 4;
+    if (numSlots == 0) numSlots = 4;
+    BF_REQUIRE(info->colorCompressionType == BF_SENS_COLOR_JPEG, "a recording's colour is JPEG");
+    BF_REQUIRE(info->depthCompressionType == BF_SENS_DEPTH_RAW_USHORT || info->depthCompressionType == BF_SENS_DEPTH_ZLIB_USHORT, "depth compression must be raw or zlib u16");
+    BF_REQUIRE(info->depthWidth > 0 && info->depthHeight > 0 && info->colorWidth > 0 && info->colorHeight > 0 && info->colorWidth < 65536 && info->colorHeight < 65536 &&
+                   info->depthShift > 0.0f && std::isfinite(info->depthShift), "bad image geometry");
+    BF_REQUIRE((uint64_t)info->depthWidth * info->depthHeight < 0xFFFFF000ull, "depth image too large");
+    {   // the temporary file must be writable now, not at the first frame's append
+        FILE* f = fopen(tmpFilename, "wb");
+        if (!f) { set_error("could not open file %s for writing", tmpFilename); return BF_ERR_INVALID_ARG; }
+        fclose(f);
+    }
+    bf_sens_recorder* r = new bf_sens_recorder;
+    r->info = *info; r->info.numFrames = 0; r->info.numIMUFrames = 0; r->tmp = tmpFilename; r->pinned = pipeline != nullptr;
+    r->coefCount = (size_t)((info->colorWidth + 7) / 8) * ((info->colorHeight + 7) / 8) * 192;
+    r->depthCount = (size_t)info->depthWidth * info->depthHeight;
+    r->slots.resize(numSlots);
+    if (r->pinned) {
+        bool ok = hipGetDevice(&r->device) == hipSuccess && hipStreamCreateWithFlags(&r->copyStream, hipStreamNonBlocking) == hipSuccess;
+        for (bf_sens_recorder::Slot& s : r->slots)
+            ok = ok && hipHostMalloc((void**)&s.coef, r->coefCount * 2) == hipSuccess && hipHostMalloc((void**)&s.depth, r->depthCount * 2) == hipSuccess &&
+                 BF_MALLOC(&s.d_coef, r->coefCount * 2) == hipSuccess && BF_MALLOC(&s.d_depth, r->depthCount * 2) == hipSuccess &&
+                 hipEventCreateWithFlags(&s.packed, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&s.copied, hipEventDisableTiming) == hipSuccess;
+        if (!ok) {
+            set_error("bf_sens_recorder_create: no pinned host or device memory (%s)", hipGetErrorString(hipGetLastError()));
+            bf_sens_recorder_destroy(r);
+            return BF_ERR_HIP;
+        }
+    } else {
+        for (bf_sens_recorder::Slot& s : r->slots) {
+            s.coef = (int16_t*)malloc(r->coefCount * 2); s.depth = (uint16_t*)malloc(r->depthCount * 2);
+            if (!s.coef || !s.depth) { bf_sens_recorder_destroy(r); throw std::bad_alloc(); }
+        }
+    }
+    for (uint32_t t = 0; t < numThreads; ++t) r->threads.emplace_back(recWorker, r);
+    *out = r;
+    return BF_OK;
+    });
+}
+
+int bf_sens_recorder_record_host(bf_sens_recorder* r, const uint8_t* rgbx, const float* depthFloat) {
+    BF_REQUIRE(r && rgbx && depthFloat, "null argument");
+    bf_sens_recorder::Slot* s = nullptr;
+    BF_TRY(recAcquire(r, &s));
+    const bf_sensor_data_info& h = r->info;
+    const int rc = bf_jpeg_forward_host(rgbx, 4, h.colorWidth, h.colorHeight, RECORD_JPEG_QUALITY, s->coef, r->coefCount);
+    if (rc == BF_OK) {
+        const float shift = h.depthShift;
+        for (size_t i = 0; i < r->depthCount; ++i) {
+            const float v = depthFloat[i] * shift;                            // (unsigned short) round(m_depthShift * d[i]), RGBDSensor.cpp:305
+            s->depth[i] = (v > 0.0f && v < 65535.5f) ? (uint16_t)(v + 0.5f) : (uint16_t)0;
+        }
+        s->onDevice = false;
+    }
+    recSubmit(r, s, rc == BF_OK);
+    return rc;
+}
+
+int bf_sens_recorder_record_device(bf_sens_recorder* r, const float* d_depthFloat, const uint8_t* d_rgbx, void* stream) {
+    BF_REQUIRE(r && d_depthFloat && d_rgbx, "null argument");
+    if (!r->pinned) { set_error("bf_sens_recorder_record_device: the recorder was created without a pipeline (host frames only)"); return BF_ERR_STATE; }
+    bf_sens_recorder::Slot* s = nullptr;
+    BF_TRY(recAcquire(r, &s));
+    const bf_sensor_data_info& h = r->info;
+    hipStream_t st = (hipStream_t)stream;
+    int rc = bf_image_convert_depth_to_u16(s->d_depth, d_depthFloat, h.depthShift, (uint32_t)r->depthCount, st);
+    if (rc == BF_OK) rc = bf_jpeg_forward_device(d_rgbx, h.colorWidth, h.colorHeight, RECORD_JPEG_QUALITY, s->d_coef, st);
+    if (rc == BF_OK) {
+        const bool ok = hipEventRecord(s->packed, st) == hipSuccess && hipStreamWaitEvent(r->copyStream, s->packed, 0) == hipSuccess &&
+                        hipMemcpyAsync(s->depth, s->d_depth, r->depthCount * 2, hipMemcpyDeviceToHost, r->copyStream) == hipSuccess &&
+                        hipMemcpyAsync(s->coef, s->d_coef, r->coefCount * 2, hipMemcpyDeviceToHost, r->copyStream) == hipSuccess &&
+                        hipEventRecord(s->copied, r->copyStream) == hipSuccess;
+        if (!ok) { set_error("bf_sens_recorder_record_device: %s", hipGetErrorString(hipGetLastError())); rc = BF_ERR_HIP; }
+        s->onDevice = true;
+    }
+    recSubmit(r, s, rc == BF_OK);
+    return rc;
+}
+
+int bf_sens_recorder_get_num_recorded(bf_sens_recorder* r, uint64_t* numFrames) {
+    BF_REQUIRE(r && numFrames, "null argument");
+    std::lock_guard<std::mutex> lk(r->m);
+    *numFrames = r->nextRecord;
+    return BF_OK;
+}
+
+int bf_sens_recorder_finish(bf_sens_recorder* r, const char* filename, const float* trajectory, uint64_t numTransforms, int overwrite, char* actualName, uint64_t capacity,
+                            uint64_t* numFramesWritten) {
+    return guarded([&]() -> int {
+    BF_REQUIRE(r && filename && filename[0] && (trajectory || numTransforms == 0), "null argument");
+    if (numFramesWritten) *numFramesWritten = 0;
+    if (actualName && capacity) actualName[0] = 0;
+    uint64_t recorded = 0;
+    int wrc = BF_OK; std::string werr;
+    {
+        std::unique_lock<std::mutex> lk(r->m);
+        r->cvFree.wait(lk, [&] { return r->nextAppend == r->nextRecord; });      // the ring is drained: no worker touches the writer any more
+        recorded = r->nextRecord; wrc = r->rc; werr = r->err;
+        r->nextRecord = r->nextClaim = r->nextAppend = 0; r->rc = BF_OK; r->err.clear();          // the recorder starts over, whatever happens below
+    }
+    int rc = BF_OK;
+    if (r->writer) { rc = bf_sensor_data_writer_close(r->writer); r->writer = nullptr; }
+    if (wrc) { std::remove(r->tmp.c_str()); set_error("%s", werr.c_str()); return wrc; }
+    if (rc) { std::remove(r->tmp.c_str()); return rc; }
+    if (recorded == 0 || numTransforms == 0) { std::remove(r->tmp.c_str()); return BF_OK; }
+    std::string actual = filename;
+    if (!overwrite) {                                                             // RGBDSensor.cpp:382-396
+        const size_t dot = actual.find_last_of('.');
+        const std::string base = dot == std::string::npos ? actual : actual.substr(0, dot), ext = dot == std::string::npos ? "" : actual.substr(dot);
+        for (unsigned int num = 1; fileExists(actual); ++num) actual = base + std::to_string(num) + ext;
+    }
+    bf_sensor_data* sd = nullptr;
+    rc = bf_sensor_data_open(r->tmp.c_str(), &sd);
+    if (rc == BF_OK) {
+        rc = bf_sensor_data_save_recorded(sd, actual.c_str(), trajectory, numTransforms);
+        bf_sensor_data_close(sd);
+    }
+    std::remove(r->tmp.c_str());
+    if (rc) return rc;
+    if (actualName && capacity) snprintf(actualName, (size_t)capacity, "%s", actual.c_str());
+    if (numFramesWritten) *numFramesWritten = numTransforms;
+    return BF_OK;
+    });
 }
 
 }  // extern "C"

@@ -48,6 +48,16 @@ lib.bf_evaluate_ate_rmse.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINT
 lib.bf_sensor_data_evaluate_trajectory.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]
 lib.bf_decode_color_rgb.argtypes = [C.c_void_p, C.c_uint64, C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p]
 lib.bf_encode_jpeg_rgb.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+lib.bf_jpeg_forward_host.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_void_p, C.c_uint64]
+lib.bf_jpeg_entropy_encode.argtypes = [C.c_uint32, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+lib.bf_sensor_data_writer_add_frame_compressed.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]
+lib.bf_sensor_data_save_recorded.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint64]
+lib.bf_sens_recorder_create.argtypes = [C.c_void_p, C.POINTER(SensorDataInfo), C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
+lib.bf_sens_recorder_record_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+lib.bf_sens_recorder_record_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+lib.bf_sens_recorder_get_num_recorded.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+lib.bf_sens_recorder_finish.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint64, C.c_int, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]
+lib.bf_sens_recorder_destroy.argtypes = [C.c_void_p]
 lib.bf_jpeg_parse.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(JpegInfo)]
 lib.bf_jpeg_entropy_decode.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(JpegInfo), C.c_void_p, C.c_uint64]
 lib.bf_jpeg_reconstruct_host.argtypes = [C.POINTER(JpegInfo), C.c_void_p, C.c_void_p]
@@ -79,6 +89,26 @@ def encode_jpeg_rgb(rgb, quality=90):
     check(lib.bf_encode_jpeg_rgb(a.ctypes.data, w, h, quality, None, 0, C.byref(n)))
     buf = np.empty(n.value, np.uint8)
     check(lib.bf_encode_jpeg_rgb(a.ctypes.data, w, h, quality, buf.ctypes.data, n.value, C.byref(n)))
+    return buf.tobytes()
+
+
+def jpeg_forward_host(pixels, quality=90):
+    """the encoder's forward stage (bf_jpeg_forward_host): RGB8 (h, w, 3) or RGBX8 (h, w, 4) -> int16 (blocks, 3, 64), zigzag order"""
+    a = np.ascontiguousarray(pixels, np.uint8)
+    h, w, stride = a.shape
+    coef = np.empty((((w + 7) // 8) * ((h + 7) // 8), 3, 64), np.int16)
+    check(lib.bf_jpeg_forward_host(a.ctypes.data, stride, w, h, quality, coef.ctypes.data, coef.size))
+    return coef
+
+
+def jpeg_entropy_encode(coef, width, height, quality=90):
+    """the encoder's entropy stage (bf_jpeg_entropy_encode): the coefficients of jpeg_forward_host -> the JPEG stream, as bytes"""
+    c = np.ascontiguousarray(coef, np.int16)
+    assert c.size == ((width + 7) // 8) * ((height + 7) // 8) * 192
+    n = C.c_uint64()
+    check(lib.bf_jpeg_entropy_encode(width, height, quality, c.ctypes.data, None, 0, C.byref(n)))
+    buf = np.empty(n.value, np.uint8)
+    check(lib.bf_jpeg_entropy_encode(width, height, quality, c.ctypes.data, buf.ctypes.data, n.value, C.byref(n)))
     return buf.tobytes()
 
 
@@ -205,6 +235,11 @@ class SensorData:
         T = np.ascontiguousarray(trajectory, np.float32).reshape(-1, 16)
         check(lib.bf_sensor_data_save_with_trajectory(self._h, str(filename).encode(), T.ctypes.data if len(T) else None, len(T)))
 
+    def save_recorded(self, filename, trajectory):
+        """RGBDSensor::saveRecordedFramesToFile: the first len(trajectory) frames, each with its pose"""
+        T = np.ascontiguousarray(trajectory, np.float32).reshape(-1, 16)
+        check(lib.bf_sensor_data_save_recorded(self._h, str(filename).encode(), T.ctypes.data if len(T) else None, len(T)))
+
     def evaluate_trajectory(self, trajectory):
         """SensorDataReader::evaluateTrajectory: (ATE RMSE [m], number of poses used) against the stored poses re-based to identity."""
         T = np.ascontiguousarray(trajectory, np.float32).reshape(-1, 16)
@@ -301,6 +336,66 @@ class SensorDataWriter:
 
     def __exit__(self, *exc):
         self.close()
+
+
+def record_depth_rule(depth_m, depth_shift=1000.0):
+    """the recording's depth rule (RGBDSensor.cpp:305) in float32 numpy operations, in the library's order: v = d * shift; 0 < v < 65535.5 ? u16(v + 0.5) : 0"""
+    with np.errstate(invalid="ignore", over="ignore"):
+        v = (np.asarray(depth_m, np.float32) * np.float32(depth_shift)).astype(np.float32)
+        ok = (v > np.float32(0)) & (v < np.float32(65535.5))
+        r = (np.where(ok, v, np.float32(0)) + np.float32(0.5)).astype(np.float32)
+    return np.where(ok, r.astype(np.uint16), np.uint16(0)).astype(np.uint16)
+
+
+class SensRecorder:
+    """bf_sens_recorder: the front half of a frame (coefficients + u16 depth) goes into a ring of slots, `threads` workers entropy-code and deflate, the blobs are
+    appended to `tmp_filename` in frame order; finish() attaches the trajectory and writes the .sens.  pipeline None: host frames only, no GPU needed.
+    info: a SensorDataInfo (JPEG colour; SensorDataWriter(...).info has the layout)."""
+
+    def __init__(self, pipeline, info, tmp_filename, threads=0, slots=0):
+        self._h = C.c_void_p()
+        self._pipe = pipeline
+        self.info = info
+        check(lib.bf_sens_recorder_create(pipeline._h if pipeline is not None else None, C.byref(info), str(tmp_filename).encode(), int(threads), int(slots), C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib.bf_sens_recorder_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def record(self, depth, rgbx, stream=0):
+        """depth float32 metres, rgbx uint8 (h, w, 4): host numpy arrays (packed on the calling thread) or torch device tensors (packed on `stream`)"""
+        if isinstance(depth, np.ndarray):
+            d = np.ascontiguousarray(depth, np.float32); c = np.ascontiguousarray(rgbx, np.uint8)
+            assert d.size == self.info.depthWidth * self.info.depthHeight and c.size == self.info.colorWidth * self.info.colorHeight * 4
+            check(lib.bf_sens_recorder_record_host(self._h, c.ctypes.data, d.ctypes.data))
+        else:
+            assert depth.numel() == self.info.depthWidth * self.info.depthHeight and rgbx.numel() == self.info.colorWidth * self.info.colorHeight * 4
+            check(lib.bf_sens_recorder_record_device(self._h, depth.data_ptr(), rgbx.data_ptr(), stream))
+
+    def num_recorded(self):
+        n = C.c_uint64()
+        check(lib.bf_sens_recorder_get_num_recorded(self._h, C.byref(n)))
+        return n.value
+
+    def finish(self, filename, trajectory, overwrite=False):
+        """-> (name written, frames written)"""
+        T = np.ascontiguousarray(trajectory, np.float32).reshape(-1, 16)
+        name = C.create_string_buffer(4096); n = C.c_uint64()
+        check(lib.bf_sens_recorder_finish(self._h, str(filename).encode(), T.ctypes.data if len(T) else None, len(T), int(bool(overwrite)), name, len(name), C.byref(n)))
+        return name.value.decode(), n.value
 
 
 def depth_to_u16(depth_m, depth_shift=1000.0):

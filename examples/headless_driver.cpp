@@ -90,6 +90,9 @@ int main(int argc, char** argv) {
         GlobalRenderState::get().readMembers(argv[1]);
         std::string videoDir = GlobalRenderState::get().s_generateVideo ? GlobalRenderState::get().s_generateVideoDir : "";
         for (int i = 3; i + 1 < argc; ++i) if (std::string(argv[i]) == "--video") videoDir = argv[i + 1];
+        bf_record_state rec;                                    // s_recordData / s_recordDataFile of the same file (bf_record.h)
+        check(bf_record_state_read(argv[1], &rec, nullptr));
+        if (rec.s_recordData && !rec.s_recordCompression) throw std::runtime_error("s_recordCompression = false (the legacy .sensor container) is not supported; record with s_recordCompression = true");
         const GlobalAppState& gas = GlobalAppState::get();
         const GlobalBundlingState& gbs = GlobalBundlingState::get();
         DummySensor dummy(640, 480, 30);
@@ -112,6 +115,7 @@ int main(int argc, char** argv) {
         for (;;) {
             const bool bGotDepth = imageManager.process();
             if (!bGotDepth) break;
+            if (rec.s_recordData) sensor.recordFrame();          // DepthSensing.cpp:1042-1045: the encode runs on the recorder's threads
             bundler.processInput();
             // reintegrate(): DepthSensing.cpp:854-902
             if (tm->getNumActiveOperations() < gas.s_maxFrameFixes) tm->generateUpdateLists();
@@ -152,6 +156,12 @@ int main(int argc, char** argv) {
             }
             bundler.process(gbs.s_numLocalNonLinIterations, gbs.s_numLocalLinIterations, gbs.s_numGlobalNonLinIterations, gbs.s_numGlobalLinIterations);
             std::printf("<<< [Frame: %u ] %u >>>\n", imageManager.getCurrFrameNumber(), sceneRep.getHeapFreeCount());
+        }
+        if (rec.s_recordData) {                                 // DepthSensing.cpp:475-483 (StopScanningAndSaveSensorData)
+            std::vector<mat4f> trajectory;
+            tm->getOptimizedTransforms(trajectory);
+            const std::string written = sensor.saveRecordedFramesToFile(rec.s_recordDataFile, trajectory);
+            if (!written.empty()) std::printf("recorded %zu frames to %s\n", trajectory.size(), written.c_str());
         }
         if (useFile) {                                          // DepthSensing.cpp:905-910 (StopScanningAndExit): evaluate against the recorded trajectory
             std::vector<mat4f> trajectory;

@@ -15,14 +15,16 @@
 using namespace bundlefusion;
 
 int main(int argc, char** argv) {
-    if (argc < 2) { std::printf("usage: %s sequence.sens [--ingest host|device] [--decode-threads N] [zParametersDefault.txt zParametersBundlingDefault.txt] [scan.ply]\n", argv[0]); return 0; }
+    if (argc < 2) { std::printf("usage: %s sequence.sens [--ingest host|device] [--decode-threads N] [--record out.sens] [zParametersDefault.txt zParametersBundlingDefault.txt] [scan.ply]\n", argv[0]); return 0; }
     try {
         bool deviceIngest = false;
         unsigned int decodeThreads = 4;
+        const char* recordPath = nullptr;
         std::vector<const char*> files;
         for (int i = 2; i < argc; ++i) {
             if (!std::strcmp(argv[i], "--ingest") && i + 1 < argc) { deviceIngest = !std::strcmp(argv[++i], "device"); }
             else if (!std::strcmp(argv[i], "--decode-threads") && i + 1 < argc) decodeThreads = (unsigned int)std::atoi(argv[++i]);
+            else if (!std::strcmp(argv[i], "--record") && i + 1 < argc) recordPath = argv[++i];
             else files.push_back(argv[i]);
         }
         const char* meshPath = nullptr;
@@ -39,6 +41,12 @@ int main(int argc, char** argv) {
         gas.s_sensorIdx = 8;
         bf_pipeline* p = nullptr;
         check(bf_pipeline_create(&gas, &gbs, &sensor.desc(), &p));
+        if (recordPath) {                                            // s_recordData: every accepted frame is packed on the device and encoded on the recorder's threads
+            bf_record_state rs;
+            check(files.size() >= 2 ? bf_record_state_read(files[0], &rs, nullptr) : bf_record_state_default(&rs));
+            rs.s_recordData = 1; rs.s_recordCompression = 1;
+            check(bf_pipeline_set_record_state(p, &rs, 0, nullptr));
+        }
         unsigned int frames = 0;
         if (deviceIngest) {
             SensPlayer player;
@@ -67,6 +75,11 @@ int main(int argc, char** argv) {
         check(bf_pipeline_get_counters(p, &nInt, &nDe, &nLocal, &nGlobal));
         std::printf("%s: %u frames, %u integrations, %u de-integrations, %u local / %u global solves\n", sensor.getSensorName().c_str(), frames, nInt, nDe, nLocal, nGlobal);
         sensor.evaluateTrajectory(trajectory);
+        if (recordPath) {
+            char actual[4096]; uint64_t written = 0;
+            check(bf_pipeline_save_recording(p, recordPath, 0, actual, sizeof actual, &written));
+            std::printf("%s: %llu recorded frames with their optimised poses\n", actual, (unsigned long long)written);
+        }
         if (meshPath) {
             uint32_t nv = 0, nf = 0, nt = 0;
             check(bf_pipeline_save_mesh(p, meshPath, nullptr, &nv, &nf, &nt));

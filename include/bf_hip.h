@@ -625,6 +625,16 @@ typedef struct bf_jpeg_info {
 BF_API int bf_jpeg_reconstruct_device(const bf_jpeg_info* info, const int16_t* d_coefficients, uint8_t* d_planes, uint8_t* d_rgbxOut, void* hip_stream);
 
 /* ------------------------------------------------------------------------- */
+/* Recording: a frame packed for a .sens file on the device (csrc/sensorrecord.hip), the mirror image of the two conversions above */
+/* ------------------------------------------------------------------------- */
+/* metres -> u16, the rule of RGBDSensor::recordFrame (RGBDSensor.cpp:305): v = d * depthShift; (v > 0 && v < 65535.5) ? (uint16_t)(v + 0.5f) : 0.
+ * -inf, +inf, NaN, zero and negatives give 0.  Writes exactly numPixels * 2 bytes. */
+BF_API int bf_image_convert_depth_to_u16(uint16_t* d_output, const float* d_input, float depthShift, uint32_t numPixels, void* hip_stream);
+/* the forward stage of the JPEG encoder (bf_jpeg_forward_host, bf_sensordata.h) on a width x height RGBX8 image (X ignored), 1 <= width, height < 65536:
+ * ceil(width/8) * ceil(height/8) * 192 int16 in that function's layout, and its bytes.  d_coefficients must be 16-byte aligned, d_rgbx 4-byte. */
+BF_API int bf_jpeg_forward_device(const uint8_t* d_rgbx, uint32_t width, uint32_t height, int32_t quality, int16_t* d_coefficients, void* hip_stream);
+
+/* ------------------------------------------------------------------------- */
 /* CUDAImageCalibrator:  CUDAImageCalibrator.h:1-40, .cpp:8-64                */
 /* (csrc/calibrator.hip) - registers a depth image to the colour camera       */
 /* ------------------------------------------------------------------------- */

@@ -23,8 +23,10 @@ extern "C" {
 /* (name = value; lines, // comments; parsed like ml::ParameterFile)          */
 /* ------------------------------------------------------------------------- */
 
-/* the GlobalAppState fields the hot path reads (recording / streaming keys are accepted and ignored; the rendering keys - s_material*, s_light*, s_RenderMode,
- * s_renderingDepthDiscontinuityThres*, s_generateVideo*, s_topVideo* - are ignored HERE and read from the same file into bf_render_state, bf_render.h) */
+/* the GlobalAppState fields the hot path reads (streaming keys are accepted and ignored; the rendering keys - s_material*, s_light*, s_RenderMode,
+ * s_renderingDepthDiscontinuityThres*, s_generateVideo*, s_topVideo* - are ignored HERE and read from the same file into bf_render_state, bf_render.h; likewise
+ * the recording keys - s_recordData, s_recordCompression, s_recordDataWidth / Height, s_recordDataFile - into bf_record_state, bf_record.h, which
+ * bf_pipeline_set_record_state honours) */
 typedef struct bf_global_app_state {
     uint32_t s_sensorIdx;
     uint32_t s_integrationWidth, s_integrationHeight;

@@ -55,6 +55,13 @@ BF_API int bf_decode_color_rgb(const uint8_t* data, uint64_t size, int32_t compr
 /* baseline JPEG (4:4:4, image-optimised Huffman tables) of an RGB8 image, for recording colour frames the way the reference does
  * (TYPE_JPEG, RGBDSensor.cpp:276).  out == NULL: only *size is returned (the stream is kept for the following call with a buffer). */
 BF_API int bf_encode_jpeg_rgb(const uint8_t* rgb, uint32_t width, uint32_t height, int32_t quality, uint8_t* out, uint64_t capacity, uint64_t* size);
+/* The encoder in its two stages, for callers that run the first on the device (bf_jpeg_forward_device, bf_hip.h); bf_encode_jpeg_rgb is the two in sequence.
+ *   bf_jpeg_forward_host     colour conversion, edge replication, DCT, quantisation, zigzag -> ceil(width/8) * ceil(height/8) * 192 int16: per block
+ *                            (raster order of the block grid) Y, Cb, Cr, 64 values each in zigzag order.  pixelStride 3 (RGB8) or 4 (RGBX8, X ignored);
+ *                            capacity in int16.  The arithmetic is binary32 with a defined order (csrc/bf_jpeg_fwd.h, DESIGN.md "Recording").
+ *   bf_jpeg_entropy_encode   two Huffman passes with image-optimised tables, headers, scan; out == NULL as in bf_encode_jpeg_rgb. */
+BF_API int bf_jpeg_forward_host(const uint8_t* pixels, uint32_t pixelStride, uint32_t width, uint32_t height, int32_t quality, int16_t* coefficients, uint64_t capacity);
+BF_API int bf_jpeg_entropy_encode(uint32_t width, uint32_t height, int32_t quality, const int16_t* coefficients, uint8_t* out, uint64_t capacity, uint64_t* size);
 
 /* The built-in JPEG decoder in its stages, for callers that reconstruct on the device (bf_jpeg_info, bf_jpeg_reconstruct_device: bf_hip.h):
  *   bf_jpeg_parse           headers up to the scan -> *info.  expectWidth x expectHeight: the size the container states (0 x 0: any)
@@ -116,6 +123,9 @@ BF_API int bf_sensor_data_writer_create(const char* filename, const bf_sensor_da
 BF_API int bf_sensor_data_writer_add_frame(bf_sensor_data_writer* w, const float cameraToWorld[16], uint64_t timeStampColor,
                                            uint64_t timeStampDepth, const uint8_t* colorBytes, uint64_t colorSizeBytes,
                                            const uint16_t* depth);
+/* the same with the depth bytes as they go into the file: already compressed for ZLIB_USHORT (compress2 level 8 is what _add_frame uses), the plane itself for RAW_USHORT */
+BF_API int bf_sensor_data_writer_add_frame_compressed(bf_sensor_data_writer* w, const float cameraToWorld[16], uint64_t timeStampColor, uint64_t timeStampDepth,
+                                                      const uint8_t* colorBytes, uint64_t colorSizeBytes, const uint8_t* depthBytes, uint64_t depthSizeBytes);
 BF_API int bf_sensor_data_writer_close(bf_sensor_data_writer* w);
 
 /* SensorDataReader::saveToFile(filename, trajectory) (SensorDataReader.cpp:152-165, "kind of a hack"): the same frames with

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../bf_pipeline.h"
+#include "../bf_record.h"
 #include "../bf_render.h"
 #include "../bf_sensordata.h"
 
@@ -91,7 +92,7 @@ private:
 // ---- RGBDSensor accessor contract (RGBDSensor.h:25-61); derive and fill the host buffers in processDepth/processColor
 class RGBDSensor {
 public:
-    virtual ~RGBDSensor() { if (m_recWriter) bf_sensor_data_writer_close(m_recWriter); if (!m_recTmp.empty()) std::remove(m_recTmp.c_str()); }
+    virtual ~RGBDSensor() { bf_sens_recorder_destroy(m_recorder); }      // (without a save the temporary recording goes with it)
     virtual bool processDepth() = 0;
     virtual bool processColor() = 0;
     virtual const float* getDepthFloat() const = 0;               // metres, -inf invalid
@@ -111,12 +112,13 @@ public:
     mat4f getColorExtrinsicsInv() const { return getColorExtrinsics().getInverse(); }
     const bf_rgbd_sensor_desc& desc() const { return m_desc; }
 
-    // ---- recording (RGBDSensor.cpp:264-312, 353-398, "modern .sens files"): every recordFrame() appends the current depth
-    // (u16 = round(1000 * metres), invalid -> 0, zlib) and colour to a temporary .sens; saveRecordedFramesToFile attaches the
-    // trajectory, drops frames without a pose and writes the final file.  Colour is JPEG-compressed like the reference's recordings
-    // (TYPE_JPEG; baseline 4:4:4, quality 90 - mLib uses stb_image_write, an encoder's bytes are not pinned by anything).
+    // ---- recording (RGBDSensor.cpp:264-312, 353-398, "modern .sens files"): every recordFrame() hands the current depth
+    // (u16 = round(1000 * metres), invalid -> 0, zlib) and colour to the library's recorder (bf_record.h): the front half of the encode runs here, the
+    // entropy coder, zlib and the disk on the recorder's threads.  saveRecordedFramesToFile attaches the trajectory, drops frames without a pose and
+    // writes the final file.  Colour is JPEG-compressed like the reference's recordings (TYPE_JPEG; baseline 4:4:4, quality 90 - mLib uses
+    // stb_image_write, an encoder's bytes are not pinned by anything).
     void recordFrame() {
-        if (!m_recWriter) {
+        if (!m_recorder) {
             bf_sensor_data_info info; std::memset(&info, 0, sizeof info);
             info.versionNumber = 4;
             std::snprintf(info.sensorName, sizeof info.sensorName, "%s", getSensorName().c_str());
@@ -125,53 +127,28 @@ public:
             info.colorCompressionType = BF_SENS_COLOR_JPEG; info.depthCompressionType = BF_SENS_DEPTH_ZLIB_USHORT;
             info.colorWidth = m_desc.colorWidth; info.colorHeight = m_desc.colorHeight; info.depthWidth = m_desc.depthWidth; info.depthHeight = m_desc.depthHeight;
             info.depthShift = 1000.0f;
-            m_recTmp = m_recordTmpPrefix + std::to_string((unsigned long long)(uintptr_t)this) + ".rec.sens";
-            check(bf_sensor_data_writer_create(m_recTmp.c_str(), &info, &m_recWriter));
+            const std::string tmp = m_recordTmpPrefix + std::to_string((unsigned long long)(uintptr_t)this) + ".rec.sens";
+            check(bf_sens_recorder_create(nullptr, &info, tmp.c_str(), 0, 0, &m_recorder));
         }
-        const size_t nd = (size_t)m_desc.depthWidth * m_desc.depthHeight, nc = (size_t)m_desc.colorWidth * m_desc.colorHeight;
-        std::vector<uint16_t> depth(nd);
-        std::vector<unsigned char> color(nc * 3);
-        const float* d = getDepthFloat();
-        const unsigned char* c = getColorRGBX();
-        for (size_t i = 0; i < nd; ++i) {
-            const float v = d[i] * 1000.0f;                                       // (unsigned short) round(m_depthShift * d[i]) :305
-            depth[i] = (v > 0.0f && v < 65535.5f) ? (uint16_t)(v + 0.5f) : (uint16_t)0;
-        }
-        for (size_t i = 0; i < nc; ++i) { color[3 * i] = c[4 * i]; color[3 * i + 1] = c[4 * i + 1]; color[3 * i + 2] = c[4 * i + 2]; }
-        uint64_t jpegSize = 0;
-        check(bf_encode_jpeg_rgb(color.data(), m_desc.colorWidth, m_desc.colorHeight, 90, nullptr, 0, &jpegSize));
-        std::vector<unsigned char> jpeg(jpegSize);
-        check(bf_encode_jpeg_rgb(color.data(), m_desc.colorWidth, m_desc.colorHeight, 90, jpeg.data(), jpeg.size(), &jpegSize));
-        const mat4f I = mat4f::identity();
-        check(bf_sensor_data_writer_add_frame(m_recWriter, I.m, 0, 0, jpeg.data(), jpegSize, depth.data()));
+        check(bf_sens_recorder_record_host(m_recorder, getColorRGBX(), getDepthFloat()));
         m_numRecorded++;
     }
     unsigned int getNumRecordedFrames() const { return m_numRecorded; }
     // returns the name actually written: unless overwriteExistingFile, an existing file gets a numeric suffix (:382-396)
     std::string saveRecordedFramesToFile(const std::string& filename, const std::vector<mat4f>& trajectory, bool overwriteExistingFile = false) {
-        if (!m_recWriter || trajectory.empty()) return std::string();
-        check(bf_sensor_data_writer_close(m_recWriter)); m_recWriter = nullptr;
-        std::string actual = filename;
-        if (!overwriteExistingFile) {
-            const size_t dot = filename.find_last_of('.');
-            const std::string base = dot == std::string::npos ? filename : filename.substr(0, dot), ext = dot == std::string::npos ? "" : filename.substr(dot);
-            for (unsigned int num = 1; fileExists(actual); ++num) actual = base + std::to_string(num) + ext;
-        }
-        bf_sensor_data* sd = nullptr;
-        check(bf_sensor_data_open(m_recTmp.c_str(), &sd));
-        const int rc = bf_sensor_data_save_recorded(sd, actual.c_str(), trajectory[0].m, trajectory.size());
-        bf_sensor_data_close(sd);
-        std::remove(m_recTmp.c_str()); m_recTmp.clear(); m_numRecorded = 0;
-        check(rc);
-        return actual;
+        if (!m_recorder || m_numRecorded == 0 || trajectory.empty()) return std::string();
+        char actual[4096]; actual[0] = 0;
+        uint64_t written = 0;
+        m_numRecorded = 0;
+        check(bf_sens_recorder_finish(m_recorder, filename.c_str(), trajectory[0].m, trajectory.size(), overwriteExistingFile ? 1 : 0, actual, sizeof actual, &written));
+        return std::string(actual);
     }
     void setRecordTempPrefix(const std::string& prefix) { m_recordTmpPrefix = prefix; }   // where the temporary recording lives (default: ./)
 protected:
     bf_rgbd_sensor_desc m_desc;
 private:
-    static bool fileExists(const std::string& f) { if (FILE* fp = std::fopen(f.c_str(), "rb")) { std::fclose(fp); return true; } return false; }
-    bf_sensor_data_writer* m_recWriter = nullptr;
-    std::string m_recTmp, m_recordTmpPrefix = "./bf_";
+    bf_sens_recorder* m_recorder = nullptr;
+    std::string m_recordTmpPrefix = "./bf_";
     unsigned int m_numRecorded = 0;
 };
 

@@ -39,6 +39,8 @@ def main():
     ap.add_argument("--decoder", choices=("auto", "builtin"), default="auto", help="--ingest host: auto decodes JPEG / PNG with Pillow where it is installed, builtin with the library's decoder")
     ap.add_argument("--camera-calibration", action="store_true", help="s_bUseCameraCalibration = true (a parameter file given with --app may set it as well)")
     ap.add_argument("--save", default=None, help="write a copy of the file with the optimised trajectory (SensorDataReader::saveToFile)")
+    ap.add_argument("--record", default=None, metavar="FILE", help="s_recordData: record every accepted frame and save FILE with the optimised trajectory (bf_pipeline_save_recording)")
+    ap.add_argument("--record-threads", type=int, default=4, help="encode threads of --record (1 .. 12)")
     mesh_out.add_arguments(ap)
     a = ap.parse_args()
     sd = sdm.SensorData(a.sens, use_pillow=a.ingest == "host" and a.decoder == "auto")        # (the player's workers decode with the library's own decoder)
@@ -56,6 +58,10 @@ def main():
     if n > gbs.s_maxNumImages * gbs.s_submapSize:          # SensorDataReader.cpp:65-67
         raise SystemExit("sens file #frames = %d, please change param file to accommodate" % n)
     p = bf.capi.Pipeline(gas, gbs, desc)
+    if a.record:
+        rs = bf.capi.default_record_state(a.app) if a.app else bf.capi.default_record_state()
+        rs.s_recordData, rs.s_recordCompression = 1, 1
+        p.set_record_state(rs, a.record_threads)
     print("camera calibration: %s" % ("registering depth to the colour camera" if p.camera_calibration() else
                                       "asked for, but the depth extrinsics are the identity: off" if gas.s_bUseCameraCalibration else "off"))
     t0 = time.time()
@@ -88,6 +94,10 @@ def main():
     if a.save:
         sd.save_with_trajectory(a.save, traj)
         print("wrote", a.save)
+    if a.record:
+        t1 = time.time()
+        name, frames = p.save_recording(a.record)
+        print("recorded %d frames to %s (%.3f s to drain and save)" % (frames, name, time.time() - t1))
     mesh_out.write(p, a)
 
 

@@ -33,6 +33,8 @@ def main():
     ap.add_argument("--timings-from", type=int, default=-1, help="switch the synchronous per-stage timings on at this frame")
     ap.add_argument("--bob", type=float, default=0.0, help="vertical sinusoid amplitude of the trajectory [m] (SURVEY.md 8d config 4: 0.3)")
     ap.add_argument("--maximages", type=int, default=0)
+    ap.add_argument("--record", default=None, metavar="FILE", help="s_recordData: record every accepted frame and save FILE with the optimised trajectory (bf_pipeline_save_recording)")
+    ap.add_argument("--record-threads", type=int, default=4, help="encode threads of --record (1 .. 12)")
     mesh_out.add_arguments(ap)
     a = ap.parse_args()
     W, H = a.width, a.height
@@ -55,6 +57,10 @@ def main():
     gbs.s_widthSIFT, gbs.s_heightSIFT = 640, 480
     bf.capi.bind_host_threads_to_device(0)
     p = bf.capi.Pipeline(gas, gbs, bf.capi.sensor_desc(W, H, K))
+    if a.record:
+        rs = bf.capi.default_record_state()
+        rs.s_recordData = 1
+        p.set_record_state(rs, a.record_threads)
     if os.environ.get("BF_TSDF_ARITH"):
         print("arithmetic contract of the voxel update:", p.scene().arith())
     if a.timings:
@@ -94,6 +100,10 @@ def main():
             print("%s: %d frames, none valid" % (name, n))
     sc = p.scene()
     print("allocated blocks", sc.num_allocated_blocks(), "heap free", sc.heap_free_count(), "debug", sc.debug_hash())
+    if a.record:
+        t1 = time.time()
+        name, nrec = p.save_recording(a.record)
+        print("recorded %d frames to %s (%.3f s to drain and save)" % (nrec, name, time.time() - t1))
     mesh_out.write(p, a)
     if tl:
         keys = [k for k in tl[0].keys() if k != "frame"]
