@@ -242,16 +242,38 @@ BF_DEV void emitCandidate(const Dev& d, const Frame& f, i3 b) {
 constexpr uint32_t WSET = 256;        // slots of a wave's block set (open addressing, load <= 0.5)
 constexpr uint32_t WLIST = 128;       // distinct blocks buffered per wave before they are looked up
 
-BF_DEV bool waveSetInsert(unsigned long long* set, uint64_t key) {
-    uint32_t slot = (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> 40) & (WSET - 1);
-    for (uint32_t probe = 0; probe < WSET; ++probe) {
+// The slot hash reaches no result (the set only decides which keys are new to the wave), so it is the cheapest mix that spreads neighbouring blocks: shifts and
+// adds of the biased coordinates.  x + 8 y + 64 z is one-to-one on any 8 x 8 x 4 box of blocks - a tile's rays stay in about that - and the carry term (5 per 256)
+// takes a longer run along one axis apart, so probe chains stay short.  (It was a 64-bit multiply: two quarter-rate v_mul_lo_u32 and a v_mul_hi_u32 per insert.)
+BF_DEV bool waveSetInsert(unsigned long long* set, uint64_t key, uint32_t ux, uint32_t uy, uint32_t uz) {
+    static_assert(WSET == 256, "the carry term of the mix is the part above the set's 8 slot bits");
+    const uint32_t h = ux + (uy << 3) + (uz << 6);
+    uint32_t slot = (h + (h >> 8) * 5u) & (WSET - 1);
+    bool fresh = false;
+#pragma unroll 1
+    for (uint32_t probe = 0; probe < WSET; ++probe) {       // (bounded: the set is flushed at half load, an empty slot always ends the walk)
         const unsigned long long old = atomicCAS(&set[slot], (unsigned long long)EMPTY64, (unsigned long long)key);
-        if (old == EMPTY64) return true;
-        if (old == key) return false;
+        fresh = old == EMPTY64;
+        if (fresh || old == key) break;
         slot = (slot + 1) & (WSET - 1);
     }
-    return false;       // cannot happen: the set is flushed at half load
+    return fresh;
 }
+
+// float -> int32 as f2i defines it (toward zero, saturating, NaN -> 0) in the ONE instruction that does exactly that: the portable spelling costs three compare-and-branch
+// regions per conversion, and the march converts nine times per ray before its first step and once per step.
+BF_DEV int f2iv(float v) { int r; asm("v_cvt_i32_f32 %0, %1" : "=v"(r) : "v"(v)); return r; }
+// worldToVirtualVoxelPos + virtualVoxelPosToSDFBlock of one coordinate, same float operations in the same order ((float)sgn(p) * 0.5f is +-0.5 or +0 exactly)
+BF_DEV int blockOfCoord(float pos, float voxelSize) {
+    const float p = pos / voxelSize;
+    const float h = 0.0f < p ? 0.5f : (p < 0.0f ? -0.5f : 0.0f);
+    int v = f2iv(p + h);
+    v = v < 0 ? (int)((uint32_t)v - (uint32_t)(BS - 1)) : v;
+    return v / BS;
+}
+// the value of lane - N of the same 16-lane row (row_shr:N); a lane without such a source keeps its own value - callers mask those lanes out
+template <int N>
+BF_DEV uint32_t rowShr(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x110 + N, 0xF, 0xF, false); }
 
 // Multi-GPU allocation (bf_scene_alloc_collect / _ingest): with the volume sharded by home bucket every rank would have to
 // march ALL pixels to find its own blocks - the part of an operator that does not shrink with the number of GPUs.  Instead each rank marches
@@ -314,7 +336,7 @@ BF_DEV void claimCandidate(const Dev& d, const BatchSink& bs, i3 b) {
 
 // SINK 0: queue the missing keys this volume owns (emitCandidate), 1: collect the distinct in-frustum keys of a band (collectCandidate), 2: claim for a batch
 template <int SINK>
-BF_DEV void waveSetFlush(const Dev& d, const Frame& f, const Collect& c, const BatchSink& bs, unsigned long long* set, const unsigned long long* list, uint32_t n, uint32_t lane) {
+BF_DEV void waveSetFlush(const Dev& d, const Frame& f, const Collect& c, const BatchSink& bs, unsigned long long* set, const unsigned long long* list, uint32_t n, uint32_t lane, bool last) {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");      // the list entries were written by other lanes of this wave
     for (uint32_t base = 0; base < n; base += 64) {
         const uint32_t i = base + lane;
@@ -323,6 +345,7 @@ BF_DEV void waveSetFlush(const Dev& d, const Frame& f, const Collect& c, const B
             if (blockInFrustum(f, b)) { if (SINK == 1) collectCandidate(d, c, b); else if (SINK == 2) claimCandidate(d, bs, b); else emitCandidate(d, f, b); }
         }
     }
+    if (last) return;       // the wave exits behind its last flush: nobody reads the set again
     for (uint32_t i = lane; i < WSET; i += 64) set[i] = EMPTY64;
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
 }
@@ -335,13 +358,13 @@ BF_DEV void marchTile(const Dev& d, const Frame& f, const float* __restrict__ de
     const uint32_t W = f.cam.m_imageWidth, H = f.cam.m_imageHeight;
     const uint32_t tilesX = (W + 7) / 8;
     const uint32_t lane = threadIdx.x & 63;
-    for (uint32_t i = lane; i < WSET; i += 64) set[i] = EMPTY64;
     const uint32_t x = (tile % tilesX) * 8 + (lane & 7);
     const uint32_t y = (tile / tilesX) * 8 + (lane >> 3);
     bool alive = x < W && y < H && (!COLLECT || tile < c.tile1);
     const float dd = alive ? depth[(size_t)y * W + x] : BF_MINF;
     if (tx.texel != nullptr && alive) tx.texel[(size_t)y * W + x] = make_uint2(__float_as_uint(dd), tx.color[(size_t)y * W + x]);
     if (!marches) return;       // wave-uniform
+    for (uint32_t i = lane; i < WSET; i += 64) set[i] = EMPTY64;
     if (dd == BF_MINF || dd == 0.0f) alive = false;
     if (dd >= f.maxIntegrationDistance) alive = false;
     const float t = f.truncation + f.truncScale * dd;
@@ -355,60 +378,66 @@ BF_DEV void marchTile(const Dev& d, const Frame& f, const float* __restrict__ de
     const f3 dv = rayMax - rayMin;
     const float invLen = 1.0f / sqrtf(dot3(dv, dv));
     const f3 rayDir = dv * invLen;
-    i3 cur = virtualVoxelPosToSDFBlock(worldToVirtualVoxelPos(f.voxelSize, rayMin));
-    const i3 end = virtualVoxelPosToSDFBlock(worldToVirtualVoxelPos(f.voxelSize, rayMax));
-    const f3 step = mk3((float)sgn(rayDir.x), (float)sgn(rayDir.y), (float)sgn(rayDir.z));
+    // The set-up below is the reference's (CUDASceneRepHashSDF.cu:165-251), float operation for float operation; what changed is how the integers around it are
+    // made: conversions in one instruction (f2iv), signs and the +inf cases as selects instead of branches.  sgn() of a direction is -1, 0 or +1, so
+    // f2i(fminf(fmaxf(step, 0), 1)) is "1 where the ray runs upward".
+    i3 cur, end;
+    cur.x = blockOfCoord(rayMin.x, f.voxelSize); cur.y = blockOfCoord(rayMin.y, f.voxelSize); cur.z = blockOfCoord(rayMin.z, f.voxelSize);
+    end.x = blockOfCoord(rayMax.x, f.voxelSize); end.y = blockOfCoord(rayMax.y, f.voxelSize); end.z = blockOfCoord(rayMax.z, f.voxelSize);
+    const f3 step = mk3(0.0f < rayDir.x ? 1.0f : (rayDir.x < 0.0f ? -1.0f : 0.0f), 0.0f < rayDir.y ? 1.0f : (rayDir.y < 0.0f ? -1.0f : 0.0f),
+                        0.0f < rayDir.z ? 1.0f : (rayDir.z < 0.0f ? -1.0f : 0.0f));
     i3 nb;
-    nb.x = cur.x + f2i(fminf(fmaxf(step.x, 0.0f), 1.0f));
-    nb.y = cur.y + f2i(fminf(fmaxf(step.y, 0.0f), 1.0f));
-    nb.z = cur.z + f2i(fminf(fmaxf(step.z, 0.0f), 1.0f));
+    nb.x = cur.x + (0.0f < rayDir.x ? 1 : 0);
+    nb.y = cur.y + (0.0f < rayDir.y ? 1 : 0);
+    nb.z = cur.z + (0.0f < rayDir.z ? 1 : 0);
     const float hv = 0.5f * f.voxelSize;
     const f3 boundary = SDFBlockToWorld(f.voxelSize, nb) - mk3(hv, hv, hv);
-    f3 tMax = mk3((boundary.x - rayMin.x) / rayDir.x, (boundary.y - rayMin.y) / rayDir.y, (boundary.z - rayMin.z) / rayDir.z);
+    const f3 toB = boundary - rayMin;
+    f3 tMax = mk3(toB.x / rayDir.x, toB.y / rayDir.y, toB.z / rayDir.z);
     f3 tDelta = mk3((step.x * (float)BS * f.voxelSize) / rayDir.x, (step.y * (float)BS * f.voxelSize) / rayDir.y,
                     (step.z * (float)BS * f.voxelSize) / rayDir.z);
     i3 bound;
-    bound.x = f2i((float)end.x + step.x);
-    bound.y = f2i((float)end.y + step.y);
-    bound.z = f2i((float)end.z + step.z);
-    if (rayDir.x == 0.0f) { tMax.x = BF_PINF; tDelta.x = BF_PINF; }
-    if (boundary.x - rayMin.x == 0.0f) { tMax.x = BF_PINF; tDelta.x = BF_PINF; }
-    if (rayDir.y == 0.0f) { tMax.y = BF_PINF; tDelta.y = BF_PINF; }
-    if (boundary.y - rayMin.y == 0.0f) { tMax.y = BF_PINF; tDelta.y = BF_PINF; }
-    if (rayDir.z == 0.0f) { tMax.z = BF_PINF; tDelta.z = BF_PINF; }
-    if (boundary.z - rayMin.z == 0.0f) { tMax.z = BF_PINF; tDelta.z = BF_PINF; }
+    bound.x = f2iv((float)end.x + step.x);
+    bound.y = f2iv((float)end.y + step.y);
+    bound.z = f2iv((float)end.z + step.z);
+    const bool infX = rayDir.x == 0.0f || toB.x == 0.0f, infY = rayDir.y == 0.0f || toB.y == 0.0f, infZ = rayDir.z == 0.0f || toB.z == 0.0f;
+    tMax.x = infX ? BF_PINF : tMax.x; tDelta.x = infX ? BF_PINF : tDelta.x;
+    tMax.y = infY ? BF_PINF : tMax.y; tDelta.y = infY ? BF_PINF : tDelta.y;
+    tMax.z = infZ ? BF_PINF : tMax.z; tDelta.z = infZ ? BF_PINF : tDelta.z;
+    const bool hasLeft = (lane & 7) != 0, hasUp = (lane & 8) != 0;
     uint32_t uniq = 0;                      // wave-uniform: blocks buffered in `list`
     for (unsigned iter = 0; iter < 1024; ++iter) {
         if (!__any((int)alive)) break;
-        const int live = alive ? 1 : 0;
-        const int lx = __shfl_up(cur.x, 1, 64), ly = __shfl_up(cur.y, 1, 64), lz = __shfl_up(cur.z, 1, 64), ll = __shfl_up(live, 1, 64);
-        const int ux = __shfl_up(cur.x, 8, 64), uy = __shfl_up(cur.y, 8, 64), uz = __shfl_up(cur.z, 8, 64), ul = __shfl_up(live, 8, 64);
-        const bool sameLeft = (lane & 7) != 0 && ll && lx == cur.x && ly == cur.y && lz == cur.z;
-        const bool sameUp = lane >= 8 && ul && ux == cur.x && uy == cur.y && uz == cur.z;
+        // The packed key first (the insert needs it anyway); a lane that is dead or holds no key carries EMPTY64, which equals no key.  The pre-filter compares the
+        // packed key with the left pixel's and, in the odd pixel rows, with the upper pixel's: both sit in the lane's own 16-lane row, where a DPP row shift reaches
+        // them inside the VALU (eight ds_bpermute through the LDS pipe before).  The filter only spares insert attempts - the set decides what is new - so the even
+        // rows going without their upper neighbour changes no result.
+        const uint32_t ux = (uint32_t)cur.x + (uint32_t)KEYLIM, uy = (uint32_t)cur.y + (uint32_t)KEYLIM, uz = (uint32_t)cur.z + (uint32_t)KEYLIM;
+        const bool keyed = alive && (ux | uy | uz) < 2u * (uint32_t)KEYLIM;          // keyable(cur): every biased coordinate below 2^21
+        const uint32_t klo = keyed ? (ux | (uy << 21)) : ~0u, khi = keyed ? ((uy >> 11) | (uz << 10)) : ~0u;       // packKey(cur)
+        const uint32_t dLeft = (rowShr<1>(klo) ^ klo) | (rowShr<1>(khi) ^ khi), dUp = (rowShr<8>(klo) ^ klo) | (rowShr<8>(khi) ^ khi);      // by ALL lanes: a DPP source must be active
+        const bool sameLeft = hasLeft & (dLeft == 0u);
+        const bool sameUp = hasUp & (dUp == 0u);
+        const uint64_t key = ((uint64_t)khi << 32) | klo;
         bool fresh = false;
-        uint64_t key = 0;
-        if (alive && !sameLeft && !sameUp && keyable(cur)) { key = packKey(cur); fresh = waveSetInsert(set, key); }
+        if (keyed && !sameLeft && !sameUp) fresh = waveSetInsert(set, key, ux, uy, uz);
         const unsigned long long mask = __ballot((int)fresh);
-        if (fresh) list[uniq + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] = key;
+        if (fresh) list[uniq + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u))] = key;
         uniq += (uint32_t)__popcll(mask);
-        if (uniq > WLIST - 64) { waveSetFlush<SINK>(d, f, c, bs, set, list, uniq, lane); uniq = 0; }
+        if (uniq > WLIST - 64) { waveSetFlush<SINK>(d, f, c, bs, set, list, uniq, lane, false); uniq = 0; }
+        // one DDA step along the axis whose boundary comes first (x before z before y on ties, as the reference's if / else if / else), as selects
+        const bool sx = tMax.x < tMax.y && tMax.x < tMax.z;
+        const bool sz = !sx && tMax.z < tMax.y;
+        const bool sy = !sx && !sz;
+        const int nc = f2iv((float)(sx ? cur.x : (sz ? cur.z : cur.y)) + (sx ? step.x : (sz ? step.z : step.y)));
+        const bool stop = nc == (sx ? bound.x : (sz ? bound.z : bound.y));
         if (alive) {
-            if (tMax.x < tMax.y && tMax.x < tMax.z) {
-                cur.x = f2i((float)cur.x + step.x);
-                if (cur.x == bound.x) alive = false;
-                tMax.x += tDelta.x;
-            } else if (tMax.z < tMax.y) {
-                cur.z = f2i((float)cur.z + step.z);
-                if (cur.z == bound.z) alive = false;
-                tMax.z += tDelta.z;
-            } else {
-                cur.y = f2i((float)cur.y + step.y);
-                if (cur.y == bound.y) alive = false;
-                tMax.y += tDelta.y;
-            }
+            cur.x = sx ? nc : cur.x; cur.z = sz ? nc : cur.z; cur.y = sy ? nc : cur.y;
+            tMax.x = sx ? tMax.x + tDelta.x : tMax.x; tMax.z = sz ? tMax.z + tDelta.z : tMax.z; tMax.y = sy ? tMax.y + tDelta.y : tMax.y;
+            alive = !stop;
         }
     }
-    if (uniq) waveSetFlush<SINK>(d, f, c, bs, set, list, uniq, lane);
+    if (uniq) waveSetFlush<SINK>(d, f, c, bs, set, list, uniq, lane, true);
 }
 
 template <bool COLLECT>
