@@ -513,6 +513,7 @@ struct bf_sift {
     Levels levels;
     GradJobs gradJobs; int gradBlocks = 0;
     DetectCfg detect; int detectBlocks = 0;
+    uint32_t orientBlocks = 0;             // k_orientation: one workgroup per raw key
     std::vector<BlurJobs> schedule;        // the level-by-level pyramid (k_blur)
     float* gauss[NUM_OCT][NLEV];
     float* mag[NUM_OCT][3]; float* ang[NUM_OCT][3];
@@ -528,10 +529,24 @@ int bf_sift_create(uint32_t width, uint32_t height, uint32_t depthWidth, uint32_
     BF_REQUIRE(out, "null argument");
     BF_REQUIRE(width >= 64 && height >= 64 && (width % 8) == 0 && (height % 8) == 0, "SIFT image must be >= 64x64 and a multiple of 8");
     BF_REQUIRE(maxNumKeysPerImage > 0, "maxNumKeysPerImage must be positive");
+    // candidate keys are packed as row << 16 | col
+    BF_REQUIRE(width <= 65536 && height <= 65536, "SIFT image too large: key coordinates must fit 16 bits");
+    // raw, and nOri / outPos in the LDS of k_reshape, hold MAXRAW keys: every level may deliver its fmax (featureCountThreshold 0)
+    uint64_t sumFmax = 0, maxFmax = 0;
+    for (int o = 0; o < NUM_OCT; ++o) {
+        const uint64_t px = (uint64_t)(width >> o) * (height >> o);
+        uint64_t fm = px > 2000000 ? 4096 : (uint64_t)(int)((float)px * 0.005f);
+        fm = fm > 4096 ? 4096 : (fm < 32 ? 32 : fm);
+        sumFmax += DOG_LEVELS * fm;
+        maxFmax = std::max(maxFmax, fm);
+    }
+    BF_REQUIRE(sumFmax <= MAXRAW, "SIFT image too large: the per-level key caps sum to more than the 6144 raw keys the detector holds (640x480 is the largest supported size)");
     bf_sift* s = new bf_sift();
     s->W = (int)width; s->H = (int)height; s->depthW = (int)depthWidth; s->depthH = (int)depthHeight;
     s->depthMin = depthMin; s->depthMax = depthMax; s->minKeyScale = minKeyScale;
     s->featureCountThreshold = (int)featureCountThreshold; s->maxFeatures = (int)maxNumKeysPerImage;
+    // raw keys after LimitFeatureCount(0): the loop stops at the first level with total - levelNum <= threshold, so total <= threshold + that level's fmax
+    s->orientBlocks = (uint32_t)std::min<uint64_t>(sumFmax, featureCountThreshold > 0 ? (uint64_t)featureCountThreshold + maxFmax : sumFmax);
     // SiftParam::ParseSiftParam (SiftGPU.cpp:126-174): level_min -1, 3 DoG levels, level_max 4
     const float sigma0 = 1.6f * powf(2.0f, 1.0f / DOG_LEVELS);
     const float sigmak = powf(2.0f, 1.0f / DOG_LEVELS);
@@ -641,7 +656,7 @@ int bf_sift_run(bf_sift* s, const float* d_intensity, const float* d_depth, floa
     }
     hipLaunchKernelGGL(k_detect, dim3(s->detectBlocks + s->gradBlocks), dim3(256), 0, st, s->levels, s->detect, s->d, d_depth, s->gradJobs, s->detectBlocks);
     hipLaunchKernelGGL(k_keys_finalize, dim3(NKL), dim3(1024), 0, st, s->levels, s->d, s->featureCountThreshold);
-    hipLaunchKernelGGL(k_orientation, dim3(2048), dim3(64), 0, st, s->levels, s->d);
+    hipLaunchKernelGGL(k_orientation, dim3(s->orientBlocks), dim3(64), 0, st, s->levels, s->d);
     hipLaunchKernelGGL(k_reshape, dim3(1), dim3(1024), 0, st, s->levels, s->d, s->minKeyScale, s->featureCountThreshold, s->maxFeatures);
     hipLaunchKernelGGL(k_descriptor, dim3(4 * (uint32_t)s->maxFeatures), dim3(256), 0, st, s->levels, s->d);
     hipLaunchKernelGGL(k_desc_finalize, dim3(div_up((uint32_t)s->maxFeatures, 8)), dim3(256), 0, st, s->levels, s->d, s->detect, d_depth, d_keyPoints,

@@ -102,7 +102,7 @@ inline float butterfly(float* lane) {       // 64-lane xor butterfly sum
 
 // BuildPyramid + DetectKeypoints (SiftPyramid.cpp:82-145, 351-394): the pyramid and the raw key lists per (octave, DoG level) slot
 static void buildAndDetect(const SiftParams& P, const float* intensity, const float* depth, int W, int H, int depthW, int depthH, float depthMin, float depthMax,
-                           std::vector<Octave>& oct, std::vector<RawKey>* raw, int* levelNum) {
+                           std::vector<Octave>& oct, std::vector<RawKey>* raw, int* levelNum, int* uncapped = nullptr) {
     // ---- BuildPyramid, SiftPyramid.cpp:82-145
     for (int o = 0; o < NUM_OCT; ++o) {
         Octave& oc = oct[o];
@@ -148,6 +148,7 @@ static void buildAndDetect(const SiftParams& P, const float* intensity, const fl
             };
             const int fmaxRaw = (int)(w * h * 0.005f);
             const int fmax = fmaxRaw > 4096 ? 4096 : (fmaxRaw < 32 ? 32 : fmaxRaw);
+            int found = 0;
             for (int row = 1; row < h - 2; ++row)
                 for (int col = 1; col < w - 2; ++col) {
                     const long index = (long)row * w + col;
@@ -182,24 +183,31 @@ static void buildAndDetect(const SiftParams& P, const float* intensity, const fl
                     cmp3(tmp, j + 1, index - w); if (reject) continue;
                     cmp3(tmp, j + 1, index); if (reject) continue;
                     cmp3(tmp, j + 1, index + w); if (reject) continue;
+                    ++found;
                     if ((int)raw[li].size() < fmax) raw[li].push_back({col, row, li, {0, 0}, 0});
                 }
             levelNum[li] = (int)raw[li].size();
+            if (uncapped) uncapped[li] = found;
         }
     }
 }
 
-extern "C" {
+// read-only view of the stages between detection and the key list (or_sift_stages): every member optional
+struct Stages {
+    int* uncapped;      // 12: extrema per slot with the fmax cap on the raw list lifted
+    int* level0;        // 12: raw counts after LimitFeatureCount(0)
+    int* reshaped;      // 12: counts after the scale gate and the capped orientation expansion, before LimitFeatureCount(1)
+    int* nOri;          // 12 x capacity: orientations (0..2) of raw key k of a slot in (row, col) order; -1 where limit 0 dropped the slot or beyond its list
+    int capacity;
+};
 
-// returns the number of features; keys: 4 floats each (x, y, scale, depth); descs: 128 bytes each.
-// levelCounts (optional, 12 ints): per (octave, level) feature count after the final limit.
-int or_sift_run(const float* intensity, const float* depth, int W, int H, int depthW, int depthH, float depthMin, float depthMax,
-                float minKeyScale, int featureCountThreshold, int maxFeatures, float* keys, uint8_t* descs, int* levelCounts) {
+static int siftRun(const float* intensity, const float* depth, int W, int H, int depthW, int depthH, float depthMin, float depthMax,
+                   float minKeyScale, int featureCountThreshold, int maxFeatures, float* keys, uint8_t* descs, int* levelCounts, const Stages* st) {
     static SiftParams P = makeParams();
     std::vector<Octave> oct(NUM_OCT);
     std::vector<RawKey> raw[NUM_OCT * DOG_LEVELS];
     int levelNum[NUM_OCT * DOG_LEVELS];
-    buildAndDetect(P, intensity, depth, W, H, depthW, depthH, depthMin, depthMax, oct, raw, levelNum);
+    buildAndDetect(P, intensity, depth, W, H, depthW, depthH, depthMin, depthMax, oct, raw, levelNum, st ? st->uncapped : nullptr);
     // ---- LimitFeatureCount(0), SiftPyramid.cpp:227-255 (TruncateMethod 0)
     auto limit = [&](int* lv) {
         if (featureCountThreshold <= 0) return;
@@ -209,6 +217,7 @@ int or_sift_run(const float* intensity, const float* depth, int W, int H, int de
         while (i < NUM_OCT * DOG_LEVELS && total - lv[i] > featureCountThreshold) { total -= lv[i]; lv[i++] = 0; }
     };
     limit(levelNum);
+    if (st && st->level0) memcpy(st->level0, levelNum, sizeof levelNum);
     // ---- GetFeatureOrientations, SiftPyramid.cpp:426-450 + ComputeOrientation_Kernel :905-1142
     for (int li = 0; li < NUM_OCT * DOG_LEVELS; ++li) {
         if (levelNum[li] == 0) { raw[li].clear(); continue; }
@@ -284,6 +293,9 @@ int or_sift_run(const float* intensity, const float* depth, int W, int H, int de
             }
         }
     }
+    if (st && st->nOri)
+        for (int li = 0; li < NUM_OCT * DOG_LEVELS; ++li)
+            for (int k = 0; k < st->capacity; ++k) st->nOri[(size_t)li * st->capacity + k] = k < (int)raw[li].size() ? raw[li][k].nOri : -1;
     // ---- ReshapeFeatureList (scale gate) + LimitFeatureCount(1)
     struct Feat { float x, y, s, o; int li; };
     std::vector<Feat> feats[NUM_OCT * DOG_LEVELS];
@@ -303,7 +315,14 @@ int or_sift_run(const float* intensity, const float* depth, int W, int H, int de
         }
         finalNum[li] = (int)feats[li].size();
     }
+    if (st && st->reshaped) memcpy(st->reshaped, finalNum, sizeof finalNum);
     limit(finalNum);
+    if (st && !keys) {        // or_sift_stages: counts only
+        if (levelCounts) memcpy(levelCounts, finalNum, sizeof finalNum);
+        int total = 0;
+        for (int li = 0; li < NUM_OCT * DOG_LEVELS; ++li) total += finalNum[li];
+        return total;
+    }
     // ---- descriptors (ComputeDescriptor_Kernel :1178-1257, NormalizeDescriptor_Kernel :1339-1370),
     //      key list (CreateGlobalKeyPointList_Kernel :2049-2081), uchar (:2100-2107)
     int n = 0;
@@ -378,6 +397,23 @@ int or_sift_run(const float* intensity, const float* depth, int W, int H, int de
         }
     }
     return n;
+}
+
+extern "C" {
+
+// returns the number of features; keys: 4 floats each (x, y, scale, depth); descs: 128 bytes each.
+// levelCounts (optional, 12 ints): per (octave, level) feature count after the final limit.
+int or_sift_run(const float* intensity, const float* depth, int W, int H, int depthW, int depthH, float depthMin, float depthMax,
+                float minKeyScale, int featureCountThreshold, int maxFeatures, float* keys, uint8_t* descs, int* levelCounts) {
+    return siftRun(intensity, depth, W, H, depthW, depthH, depthMin, depthMax, minKeyScale, featureCountThreshold, maxFeatures, keys, descs, levelCounts, nullptr);
+}
+
+// test hook: the counts between the stages of or_sift_run (same arguments, no descriptors): uncapped extrema, after limit 0, after the reshape, after limit 1
+// (12 ints each), and the number of orientations of every raw key (12 x capacity).  Returns the number of features before the maxFeatures check.
+int or_sift_stages(const float* intensity, const float* depth, int W, int H, int depthW, int depthH, float depthMin, float depthMax, float minKeyScale,
+                   int featureCountThreshold, int* uncapped, int* level0, int* reshaped, int* level1, int* nOri, int capacity) {
+    const Stages st = {uncapped, level0, reshaped, nOri, capacity};
+    return siftRun(intensity, depth, W, H, depthW, depthH, depthMin, depthMax, minKeyScale, featureCountThreshold, 0, nullptr, nullptr, level1, &st);
 }
 
 // test hook: raw key lists after DetectKeypoints, before any limit: counts[12] and (col, row) pairs per slot (capacity keys per slot)

@@ -312,6 +312,23 @@ def sift_run(intensity, depth, depth_min=0.1, depth_max=4.0, min_key_scale=3.0, 
     return n, keys[:n].copy(), descs[:n].copy(), levels
 
 
+def sift_stages(intensity, depth, depth_min=0.1, depth_max=4.0, min_key_scale=3.0, feature_count_threshold=150, capacity=4096, **_):
+    """The counts between the stages of sift_run, 12 ints each: `uncapped` (extrema with the fmax cap on the raw list lifted), `level0` (after limit 0),
+    `reshaped` (after the scale gate and the capped orientation expansion), `level1` (after limit 1); `n_ori`: list of 12 arrays, the number of
+    orientations of every raw key of a slot in (row, col) order, empty where limit 0 dropped the slot."""
+    intensity = np.ascontiguousarray(intensity, np.float32)
+    depth = np.ascontiguousarray(depth, np.float32)
+    H, W = intensity.shape
+    dH, dW = depth.shape
+    unc, l0, rs, l1 = (np.zeros(12, np.int32) for _ in range(4))
+    nori = np.zeros((12, capacity), np.int32)
+    olib.or_sift_stages.restype = C.c_int
+    n = olib.or_sift_stages(_fp(intensity), _fp(depth), W, H, dW, dH, C.c_float(depth_min), C.c_float(depth_max), C.c_float(min_key_scale),
+                            feature_count_threshold, _fp(unc), _fp(l0), _fp(rs), _fp(l1), _fp(nori), capacity)
+    assert l0.max() <= capacity
+    return dict(n=n, uncapped=unc, level0=l0, reshaped=rs, level1=l1, n_ori=[nori[i, :l0[i]].copy() for i in range(12)])
+
+
 def sift_pyramid_level(intensity, octave, index):
     intensity = np.ascontiguousarray(intensity, np.float32)
     H, W = intensity.shape
