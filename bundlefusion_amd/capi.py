@@ -107,6 +107,19 @@ def check(rc):
         raise BFError("libbf_hip status %d: %s" % (rc, lib.bf_last_error().decode()))
 
 
+def debug_live_resources():
+    """bf_debug_live_resources: (live owners, live device allocations, live device bytes, live pinned allocations + events + streams, acquisitions so far,
+    failed releases) of this process"""
+    out = (C.c_uint64 * 6)()
+    check(lib.bf_debug_live_resources(out))
+    return tuple(int(v) for v in out)
+
+
+def debug_fail_acquire(nth):
+    """bf_debug_fail_acquire: the nth acquisition from now on fails as out-of-memory, once (0: off)"""
+    check(lib.bf_debug_fail_acquire(C.c_uint64(int(nth))))
+
+
 def mat16(m):
     a = np.ascontiguousarray(np.asarray(m, dtype=np.float32).reshape(16))
     return (C.c_float * 16)(*a.tolist())

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/bf_hip.h"
+#include "bf_resources.h"
 
 namespace bf {
 
@@ -19,7 +20,7 @@ struct MeshWeld {
 };
 
 // Welds numTriangles triangles at d_triangles on `stream` (see meshweld.hip for the definition); waits for the stream twice (vertex count, face count).
-int meshweld_run(MeshWeld& w, hipStream_t stream, const bf_mc_triangle* d_triangles, uint32_t numTriangles, const float transform[16]);
-void meshweld_free(MeshWeld& w);
+// The buffers of `w` are taken from, and stay with, `res`: the owner of the handle that holds `w`.
+int meshweld_run(MeshWeld& w, Resources& res, hipStream_t stream, const bf_mc_triangle* d_triangles, uint32_t numTriangles, const float transform[16]);
 
 }  // namespace bf

@@ -16,7 +16,7 @@
 #include <vector>
 
 #include "bf_device.h"
-#include "bf_internal.h"
+#include "bf_resources.h"
 
 using namespace bf;
 
@@ -211,7 +211,7 @@ struct bf_cache {
     std::vector<bf_cached_frame> frames;
     bf_cached_frame* d_frames = nullptr;
     float* d_scratch = nullptr;
-    std::vector<void*> allocations;
+    bf::Resources res;
     hipStream_t stream = nullptr;
 };
 
@@ -223,6 +223,7 @@ int bf_cache_create(uint32_t dw, uint32_t dh, uint32_t W, uint32_t H, uint32_t m
     BF_REQUIRE(W > 1 && H > 1 && dw > 1 && dh > 1 && maxNumImages > 0, "bad sizes");
     BF_REQUIRE(ceil(2.0 * colorDownSigma) <= MAX_R && ceil(2.0 * depthDownSigmaD) <= MAX_R, "filter radius > 6 not supported");
     bf_cache* c = new bf_cache();
+    bf::CreateGuard<bf_cache> guard(c, bf_cache_destroy);
     c->W = W; c->H = H; c->dw = dw; c->dh = dh; c->maxImages = maxNumImages;
     memcpy(c->inputIntrinsics.e, K, 64);
     c->intrinsics = c->inputIntrinsics;                                  // CUDACache.cpp:20-24
@@ -237,11 +238,10 @@ int bf_cache_create(uint32_t dw, uint32_t dh, uint32_t W, uint32_t H, uint32_t m
     const size_t n = (size_t)W * H;
     // one slab per array type: frame i at offset i*n  (288 GB of HBM: 1200 frames are 300 MB)
     float *depth, *campos, *inten, *derivs, *normals; uint8_t* nu;
-    auto A = [&](void** p, size_t bytes) { if (BF_MALLOC(p, bytes) != hipSuccess) return false; c->allocations.push_back(*p); return true; };
-    bool ok = A((void**)&depth, n * 4 * maxNumImages) && A((void**)&campos, n * 16 * maxNumImages) && A((void**)&inten, n * 4 * maxNumImages) &&
-              A((void**)&derivs, n * 8 * maxNumImages) && A((void**)&nu, n * 4 * maxNumImages) && A((void**)&normals, n * 16 * maxNumImages) &&
-              A((void**)&c->d_frames, sizeof(bf_cached_frame) * maxNumImages) && A((void**)&c->d_scratch, n * 4);
-    if (!ok) { set_error("bf_cache_create: hipMalloc failed"); bf_cache_destroy(c); return BF_ERR_HIP; }
+    bf::Resources& R = c->res;
+    BF_TRY(R.device(&depth, n * maxNumImages)); BF_TRY(R.device(&campos, n * 4 * maxNumImages)); BF_TRY(R.device(&inten, n * maxNumImages));
+    BF_TRY(R.device(&derivs, n * 2 * maxNumImages)); BF_TRY(R.device(&nu, n * 4 * maxNumImages)); BF_TRY(R.device(&normals, n * 4 * maxNumImages));
+    BF_TRY(R.device(&c->d_frames, maxNumImages)); BF_TRY(R.device(&c->d_scratch, n));
     c->frames.resize(maxNumImages);
     for (uint32_t i = 0; i < maxNumImages; ++i) {
         bf_cached_frame& f = c->frames[i];
@@ -253,14 +253,13 @@ int bf_cache_create(uint32_t dw, uint32_t dh, uint32_t W, uint32_t H, uint32_t m
         f.d_normalsDownsampled = normals + 4 * n * i;
     }
     BF_HIP_TRY(hipMemcpy(c->d_frames, c->frames.data(), sizeof(bf_cached_frame) * maxNumImages, hipMemcpyHostToDevice));
-    *out = c;
+    *out = guard.dismiss();
     return BF_OK;
 }
 
 int bf_cache_destroy(bf_cache* c) {
     if (!c) return BF_OK;
     (void)hipStreamSynchronize(c->stream);
-    for (void* p : c->allocations) (void)hipFree(p);
     delete c;
     return BF_OK;
 }

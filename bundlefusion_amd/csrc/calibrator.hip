@@ -13,7 +13,7 @@
 #include <cmath>
 
 #include "bf_device.h"
-#include "bf_internal.h"
+#include "bf_resources.h"
 
 using namespace bf;
 
@@ -21,6 +21,7 @@ struct bf_image_calibrator {
     uint32_t width = 0, height = 0;
     uint32_t* d_scratch = nullptr;          // width * height words; +inf (as bits) between frames
     hipStream_t stream = nullptr;
+    bf::Resources res;
 };
 
 namespace {
@@ -135,13 +136,13 @@ extern "C" {
 int bf_image_calibrator_create(uint32_t width, uint32_t height, bf_image_calibrator** out) {
     BF_REQUIRE(out && width > 0 && height > 0 && width < 32768 && height < 32768, "bad image size");
     bf_image_calibrator* c = new bf_image_calibrator;
+    bf::CreateGuard<bf_image_calibrator> guard(c, bf_image_calibrator_destroy);
     c->width = width; c->height = height;
     const uint32_t n = width * height;
-    if (BF_MALLOC((void**)&c->d_scratch, (size_t)n * 4) != hipSuccess) { delete c; set_error("bf_image_calibrator_create: out of device memory"); return BF_ERR_HIP; }
+    BF_TRY(c->res.device(&c->d_scratch, n));
     k_calib_arm<<<div_up(n, 256), 256, 0, nullptr>>>(c->d_scratch, n);
-    const hipError_t e = hipStreamSynchronize(nullptr);          // armed before any stream of the caller's can use it
-    if (e != hipSuccess) { (void)hipFree(c->d_scratch); delete c; set_error("bf_image_calibrator_create: %s", hipGetErrorString(e)); return BF_ERR_HIP; }
-    *out = c;
+    BF_HIP_TRY(hipStreamSynchronize(nullptr));          // armed before any stream of the caller's can use it
+    *out = guard.dismiss();
     return BF_OK;
 }
 
@@ -149,7 +150,6 @@ int bf_image_calibrator_create(uint32_t width, uint32_t height, bf_image_calibra
 int bf_image_calibrator_destroy(bf_image_calibrator* c) {
     if (!c) return BF_OK;
     (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(c->d_scratch);
     delete c;
     return BF_OK;
 }

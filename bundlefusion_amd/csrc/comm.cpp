@@ -9,7 +9,7 @@
 #include <mutex>
 #include <string>
 
-#include "bf_internal.h"
+#include "bf_resources.h"
 #include "../../include/bf_comm.h"
 
 namespace {
@@ -66,6 +66,7 @@ struct bf_comm {
     bf_all_gather_fn fn = nullptr; void* user = nullptr;
     // staging of bf_chunk_exchange
     uint8_t *d_send = nullptr, *d_recv = nullptr; uint64_t stageBytes = 0;
+    bf::Resources res;
 };
 
 extern "C" {
@@ -114,8 +115,6 @@ int bf_comm_create_callback(bf_all_gather_fn fn, void* user, uint32_t world, uin
 
 int bf_comm_destroy(bf_comm* c) {
     if (!c) return BF_OK;
-    if (c->d_send) (void)hipFree(c->d_send);
-    if (c->d_recv) (void)hipFree(c->d_recv);
     if (c->nccl && c->ownsNccl) (void)rccl().CommDestroy(c->nccl);
     delete c;
     return BF_OK;
@@ -146,11 +145,10 @@ int bf_chunk_exchange(bf_comm* c, const void* h_mine, void* h_all, uint64_t pack
     hipStream_t st = (hipStream_t)hip_stream;
     if (c->world == 1) { memcpy(h_all, h_mine, package_bytes); return BF_OK; }
     if (c->stageBytes < package_bytes) {
-        if (c->d_send) (void)hipFree(c->d_send);
-        if (c->d_recv) (void)hipFree(c->d_recv);
-        c->d_send = c->d_recv = nullptr; c->stageBytes = 0;
-        BF_HIP_TRY(BF_MALLOC((void**)&c->d_send, package_bytes));
-        BF_HIP_TRY(BF_MALLOC((void**)&c->d_recv, package_bytes * c->world));
+        c->res.release(c->d_send); c->res.release(c->d_recv);
+        c->stageBytes = 0;
+        BF_TRY(c->res.device(&c->d_send, package_bytes));
+        BF_TRY(c->res.device(&c->d_recv, package_bytes * c->world));
         c->stageBytes = package_bytes;
     }
     BF_HIP_TRY(hipMemcpyAsync(c->d_send, h_mine, package_bytes, hipMemcpyHostToDevice, st));

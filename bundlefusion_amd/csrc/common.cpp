@@ -10,7 +10,7 @@
 #include <cstdlib>
 #include <string>
 
-#include "bf_internal.h"
+#include "bf_resources.h"
 
 namespace bf {
 static thread_local std::string g_last_error;
@@ -23,6 +23,7 @@ void set_error(const char* fmt, ...) {
     va_end(ap);
     g_last_error = buf;
 }
+ResourceCounters g_resources;
 }  // namespace bf
 
 extern "C" {
@@ -108,6 +109,14 @@ int bf_bind_host_threads_to_device(int device, char* cpulist_out, size_t cpulist
     if (cpulist_out && cpulist_len) snprintf(cpulist_out, cpulist_len, "%s", list.c_str());
     return BF_OK;
 }
+
+int bf_debug_live_resources(uint64_t out[6]) {
+    BF_REQUIRE(out, "null argument");
+    const bf::ResourceCounters& c = bf::g_resources;
+    out[0] = c.owners.load(); out[1] = c.deviceAllocs.load(); out[2] = c.deviceBytes.load(); out[3] = c.others.load(); out[4] = c.acquisitions.load(); out[5] = c.releaseErrors.load();
+    return BF_OK;
+}
+int bf_debug_fail_acquire(uint64_t nth) { bf::g_resources.failIn.store((int64_t)nth); return BF_OK; }
 
 int bf_device_count(void) {
     int n = 0;

@@ -28,7 +28,7 @@
 
 #include "../../include/bf_pipeline.h"
 #include "bf_device.h"
-#include "bf_internal.h"
+#include "bf_resources.h"
 
 using namespace bf;
 
@@ -155,6 +155,7 @@ struct bf_correspondence_evaluator {
     std::map<std::string, bf_corr_evaluation> totals;          // sum of evaluate() results per corrType (not in the reference: it only logs)
     // device scratch
     m44* d_T = nullptr; uint32_t* d_counts = nullptr; uint32_t capacity = 0;
+    bf::Resources res;
     bool logging() const { return !logFilePrefix.empty(); }
 };
 
@@ -162,12 +163,11 @@ namespace {
 
 int evEnsure(bf_correspondence_evaluator* ev, uint32_t n) {
     if (n <= ev->capacity) return BF_OK;
-    if (ev->d_T) hipFree(ev->d_T);
-    if (ev->d_counts) hipFree(ev->d_counts);
-    ev->d_T = nullptr; ev->d_counts = nullptr; ev->capacity = 0;
+    ev->res.release(ev->d_T); ev->res.release(ev->d_counts);
+    ev->capacity = 0;
     const uint32_t cap = std::max<uint32_t>(64, 2 * n);
-    BF_HIP_TRY(BF_MALLOC((void**)&ev->d_T, sizeof(m44) * 2 * cap));
-    BF_HIP_TRY(BF_MALLOC((void**)&ev->d_counts, sizeof(uint32_t) * 4 * cap));
+    BF_TRY(ev->res.device(&ev->d_T, 2 * (size_t)cap));
+    BF_TRY(ev->res.device(&ev->d_counts, 4 * (size_t)cap));
     ev->capacity = cap;
     return BF_OK;
 }
@@ -233,6 +233,7 @@ extern "C" {
 int bf_correspondence_evaluator_create(const float* h_referenceTrajectory, uint32_t numTransforms, const char* logFilePrefix, bf_correspondence_evaluator** out) {
     BF_REQUIRE(out && (h_referenceTrajectory || numTransforms == 0), "null argument");
     bf_correspondence_evaluator* ev = new bf_correspondence_evaluator;
+    bf::CreateGuard<bf_correspondence_evaluator> guard(ev, bf_correspondence_evaluator_destroy);
     ev->referenceTrajectory.resize(numTransforms);
     if (numTransforms) memcpy(ev->referenceTrajectory.data(), h_referenceTrajectory, sizeof(m44) * numTransforms);
     ev->logFilePrefix = logFilePrefix ? logFilePrefix : "";
@@ -241,20 +242,17 @@ int bf_correspondence_evaluator_create(const float* h_referenceTrajectory, uint3
         ev->outIncorrect.open(ev->logFilePrefix + "_wrong.csv");
         if (!ev->outPerFrame.is_open() || !ev->outIncorrect.is_open()) {
             set_error("[CorrespondenceEvaluator] failed to open log file(s): %s", ev->logFilePrefix.c_str());
-            delete ev;
             return BF_ERR_INVALID_ARG;
         }
         ev->outPerFrame << "numFrames,curFrame,type,precision,recall,numCorrect,numDetected,numTotal" << std::endl;
         ev->outIncorrect << "numFrames,curFrame,matchFrame,type,err" << std::endl;
     }
-    *out = ev;
+    *out = guard.dismiss();
     return BF_OK;
 }
 
 int bf_correspondence_evaluator_destroy(bf_correspondence_evaluator* ev) {
     if (!ev) return BF_OK;
-    if (ev->d_T) hipFree(ev->d_T);
-    if (ev->d_counts) hipFree(ev->d_counts);
     delete ev;
     return BF_OK;
 }

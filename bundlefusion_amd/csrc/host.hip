@@ -5,7 +5,7 @@
 //  * one HIP stream carries a frame from ingest to integration; the only host read-back per frame is a 96-byte record
 //    (last matched frame, validity, #residuals, #keys, SIFT pose) — the reference blocks on ~20 small D2H copies per frame;
 //  * all frames stay resident in HBM at integration resolution (the reference keeps them on the host and re-uploads a
-//    frame for every integrate / de-integrate), slab-allocated so that ingest never calls hipMalloc in steady state;
+//    frame for every integrate / de-integrate), slab-allocated so that ingest never allocates device memory in steady state;
 //  * bundling reads the ingest buffers in place (the reference's copyToBundling makes three device-to-device copies per
 //    frame because its bundler lives on a second GPU).
 #include <algorithm>
@@ -26,7 +26,7 @@
 #include "../../include/bf_render.h"
 #include "../../include/bf_sensordata.h"
 #include "bf_device.h"
-#include "bf_internal.h"
+#include "bf_resources.h"
 #include "bf_se3.h"
 #include "volume_queue.h"
 
@@ -209,6 +209,7 @@ struct bf_image_manager {
         uint32_t next = 0;
         bool ready = false;
     } rawIn;
+    bf::Resources res;
 };
 
 extern "C" {
@@ -218,6 +219,7 @@ int bf_image_manager_create(uint32_t wInt, uint32_t hInt, uint32_t wSIFT, uint32
     BF_REQUIRE(sensor && gbs && out, "null argument");
     BF_REQUIRE(wInt > 1 && hInt > 1 && sensor->depthWidth > 1 && sensor->depthHeight > 1 && sensor->colorWidth > 1 && sensor->colorHeight > 1, "bad image size");
     bf_image_manager* im = new bf_image_manager;
+    bf::CreateGuard<bf_image_manager> guard(im, bf_image_manager_destroy);
     im->sensor = *sensor; im->gbs = *gbs;
     im->wInt = wInt; im->hInt = hInt; im->wSIFT = wSIFT; im->hSIFT = hSIFT; im->onGPU = storeFramesOnGPU != 0; im->scratch = storeFramesOnGPU == 2;
     im->siftDepthIntrinsics = toM(sensor->depthIntrinsics);
@@ -229,26 +231,26 @@ int bf_image_manager_create(uint32_t wInt, uint32_t hInt, uint32_t wSIFT, uint32
     im->depthExtrinsicsInv = inverse44(im->depthExtrinsics);
     const size_t nd = (size_t)sensor->depthWidth * sensor->depthHeight, nc = (size_t)sensor->colorWidth * sensor->colorHeight;
     for (uint32_t k = 0; k < (im->scratch ? 1u : bf_image_manager::NSETS); ++k) {
-        BF_HIP_TRY(BF_MALLOC((void**)&im->rawSet[k], nd * 4));
-        BF_HIP_TRY(BF_MALLOC((void**)&im->filtSet[k], nd * 4));
-        BF_HIP_TRY(BF_MALLOC((void**)&im->colSet[k], nc * 4));
+        BF_TRY(im->res.device(&im->rawSet[k], nd));
+        BF_TRY(im->res.device(&im->filtSet[k], nd));
+        BF_TRY(im->res.device(&im->colSet[k], nc * 4));
     }
     if (im->scratch) for (uint32_t k = 1; k < bf_image_manager::NSETS; ++k) { im->rawSet[k] = im->rawSet[0]; im->filtSet[k] = im->filtSet[0]; im->colSet[k] = im->colSet[0]; }
     im->d_depthInputRaw = im->rawSet[0]; im->d_depthInputFiltered = im->filtSet[0]; im->d_colorInput = im->colSet[0];
     if (!im->onGPU) {
-        BF_HIP_TRY(BF_MALLOC((void**)&im->d_stageDepth, im->nInt() * 4));
-        BF_HIP_TRY(BF_MALLOC((void**)&im->d_stageColor, im->nInt() * 4));
+        BF_TRY(im->res.device(&im->d_stageDepth, im->nInt()));
+        BF_TRY(im->res.device(&im->d_stageColor, im->nInt() * 4));
     }
-    *out = im;
+    *out = guard.dismiss();
     return BF_OK;
 }
 
 int bf_image_manager_reset(bf_image_manager* im) {
     BF_REQUIRE(im, "null manager");
     (void)hipStreamSynchronize(im->stream);
-    for (auto p : im->depthSlabs) (void)hipFree(p);
-    for (auto p : im->colorSlabs) (void)hipFree(p);
-    for (auto p : im->texelSlabs) (void)hipFree(p);
+    for (auto& p : im->depthSlabs) im->res.release(p);
+    for (auto& p : im->colorSlabs) im->res.release(p);
+    for (auto& p : im->texelSlabs) im->res.release(p);
     im->texelSlabs.clear();
     im->depthSlabs.clear(); im->colorSlabs.clear(); im->hostDepth.clear(); im->hostColor.clear();
     im->activeDepth = im->activeColor = -1;
@@ -258,16 +260,8 @@ int bf_image_manager_reset(bf_image_manager* im) {
 
 int bf_image_manager_destroy(bf_image_manager* im) {
     if (!im) return BF_OK;
-    bf_image_manager_reset(im);
-    for (uint32_t k = 0; k < (im->scratch ? 1u : bf_image_manager::NSETS); ++k) { (void)hipFree(im->rawSet[k]); (void)hipFree(im->filtSet[k]); (void)hipFree(im->colSet[k]); }
-    (void)hipFree(im->d_stageDepth); (void)hipFree(im->d_stageColor);
+    (void)hipStreamSynchronize(im->stream);
     bf_image_calibrator_destroy(im->calib);
-    {
-        bf_image_manager::RawIngest& r = im->rawIn;
-        (void)hipFree(r.d_depthU16); (void)hipFree(r.d_colourIn); (void)hipFree(r.d_planes); (void)hipFree(r.d_depth); (void)hipFree(r.d_rgbx);
-        for (uint32_t k = 0; k < bf_image_manager::NSETS; ++k) { (void)hipHostFree(r.h_depth[k]); (void)hipHostFree(r.h_colour[k]); if (r.uploaded[k]) (void)hipEventDestroy(r.uploaded[k]); }
-        if (r.evDecoded) (void)hipEventDestroy(r.evDecoded);
-    }
     delete im;
     return BF_OK;
 }
@@ -339,10 +333,10 @@ static int im_process(bf_image_manager* im, const float* depth, const uint8_t* c
         if (f / bf_image_manager::SLAB >= im->depthSlabs.size()) {
             float* pd = nullptr; uint8_t* pc = nullptr;
             const size_t slots = im->scratch ? 1 : bf_image_manager::SLAB;
-            BF_HIP_TRY(BF_MALLOC((void**)&pd, ni * 4 * slots));
-            BF_HIP_TRY(BF_MALLOC((void**)&pc, ni * 4 * slots));
+            BF_TRY(im->res.device(&pd, ni * slots));
+            BF_TRY(im->res.device(&pc, ni * 4 * slots));
             im->depthSlabs.push_back(pd); im->colorSlabs.push_back(pc);
-            if (im->storeTexels) { uint8_t* pt = nullptr; BF_HIP_TRY(BF_MALLOC((void**)&pt, ni * 8 * slots)); im->texelSlabs.push_back(pt); }
+            if (im->storeTexels) { uint8_t* pt = nullptr; BF_TRY(im->res.device(&pt, ni * 8 * slots)); im->texelSlabs.push_back(pt); }
         }
         frameDepth = im->depthSlabs[f / bf_image_manager::SLAB] + (size_t)(f % bf_image_manager::SLAB) * ni;
         frameColor = im->colorSlabs[f / bf_image_manager::SLAB] + (size_t)(f % bf_image_manager::SLAB) * ni * 4;
@@ -421,20 +415,21 @@ int rawEnsure(bf_image_manager* im, size_t colourInBytes, size_t planeBytes) {
     bf_image_manager::RawIngest& r = im->rawIn;
     const size_t nd = (size_t)im->sensor.depthWidth * im->sensor.depthHeight, nc = (size_t)im->sensor.colorWidth * im->sensor.colorHeight;
     if (!r.ready) {
-        BF_HIP_TRY(BF_MALLOC((void**)&r.d_depthU16, nd * 2));
-        BF_HIP_TRY(BF_MALLOC((void**)&r.d_depth, nd * 4));
-        BF_HIP_TRY(BF_MALLOC((void**)&r.d_rgbx, nc * 4));
+        // (a call that fails part way keeps what it took with the manager and takes only the rest when it is repeated)
+        if (!r.d_depthU16) BF_TRY(im->res.device(&r.d_depthU16, nd));
+        if (!r.d_depth) BF_TRY(im->res.device(&r.d_depth, nd));
+        if (!r.d_rgbx) BF_TRY(im->res.device(&r.d_rgbx, nc * 4));
         for (uint32_t k = 0; k < bf_image_manager::NSETS; ++k) {
-            BF_HIP_TRY(hipHostMalloc((void**)&r.h_depth[k], nd * 2));
-            BF_HIP_TRY(hipEventCreateWithFlags(&r.uploaded[k], hipEventDisableTiming));
+            if (!r.h_depth[k]) BF_TRY(im->res.pinned(&r.h_depth[k], nd * 2));
+            if (!r.uploaded[k]) BF_TRY(im->res.event(&r.uploaded[k], hipEventDisableTiming));
         }
-        BF_HIP_TRY(hipEventCreateWithFlags(&r.evDecoded, hipEventDisableTiming));
+        if (!r.evDecoded) BF_TRY(im->res.event(&r.evDecoded, hipEventDisableTiming));
         r.ready = true;
     }
     if (colourInBytes > r.colourInBytes || planeBytes > r.planeBytes) {          // a larger frame than any before it: the kernels of the frames before must be done with the buffers
         BF_HIP_TRY(hipStreamSynchronize(im->stream));
-        if (colourInBytes > r.colourInBytes) { (void)hipFree(r.d_colourIn); r.d_colourIn = nullptr; r.colourInBytes = 0; BF_HIP_TRY(BF_MALLOC((void**)&r.d_colourIn, colourInBytes)); r.colourInBytes = colourInBytes; }
-        if (planeBytes > r.planeBytes) { (void)hipFree(r.d_planes); r.d_planes = nullptr; r.planeBytes = 0; BF_HIP_TRY(BF_MALLOC((void**)&r.d_planes, planeBytes)); r.planeBytes = planeBytes; }
+        if (colourInBytes > r.colourInBytes) { r.colourInBytes = 0; BF_TRY(im->res.regrow(&r.d_colourIn, colourInBytes)); r.colourInBytes = colourInBytes; }
+        if (planeBytes > r.planeBytes) { r.planeBytes = 0; BF_TRY(im->res.regrow(&r.d_planes, planeBytes)); r.planeBytes = planeBytes; }
     }
     return BF_OK;
 }
@@ -445,8 +440,9 @@ int rawSlot(bf_image_manager* im, size_t bytes, uint32_t* slot) {
     const uint32_t k = r.next % bf_image_manager::NSETS;
     BF_HIP_TRY(hipEventSynchronize(r.uploaded[k]));
     if (bytes > r.h_colourBytes[k]) {
-        (void)hipHostFree(r.h_colour[k]); r.h_colour[k] = nullptr; r.h_colourBytes[k] = 0;
-        BF_HIP_TRY(hipHostMalloc((void**)&r.h_colour[k], bytes));
+        r.h_colourBytes[k] = 0;
+        im->res.release(r.h_colour[k]);
+        BF_TRY(im->res.pinned(&r.h_colour[k], bytes));
         r.h_colourBytes[k] = bytes;
     }
     *slot = k;
@@ -627,6 +623,7 @@ struct bf_bundler {
     uint32_t numSolves = 0;
     std::vector<int> validScratch;
     bf_correspondence_evaluator* corrEvaluator = nullptr;       // Bundler.h:101-103
+    bf::Resources res;
 };
 
 namespace {
@@ -812,28 +809,27 @@ int bf_bundler_create(uint32_t maxNumImages, uint32_t maxNumKeysPerImage, const 
                       const bf_global_app_state* gas, const bf_global_bundling_state* gbs, bf_bundler** out) {
     BF_REQUIRE(siftIntrinsicsInv && manager && gas && gbs && out && maxNumImages >= 2, "bad argument");
     bf_bundler* b = new bf_bundler;
+    bf::CreateGuard<bf_bundler> guard(b, bf_bundler_destroy);
     b->gas = *gas; b->gbs = *gbs; b->maxImages = maxNumImages; b->maxKeys = maxNumKeysPerImage; b->isLocal = isLocal != 0;
     b->siftIntrinsicsInv = toM(siftIntrinsicsInv);
     b->siftIntrinsics = inverse44(b->siftIntrinsicsInv);
-    int rc = BF_OK;
     const bf_rgbd_sensor_desc& sn = manager->sensor;
     if (b->isLocal)              // initSift: SetParams(w, h, false, 150, depthMin, depthMax) (:57-69)
-        rc = bf_sift_create(gbs->s_widthSIFT, gbs->s_heightSIFT, sn.depthWidth, sn.depthHeight, 150, gas->s_sensorDepthMin, gas->s_sensorDepthMax, gbs->s_minKeyScale,
-                            maxNumKeysPerImage, &b->sift);
+        BF_TRY(bf_sift_create(gbs->s_widthSIFT, gbs->s_heightSIFT, sn.depthWidth, sn.depthHeight, 150, gas->s_sensorDepthMin, gas->s_sensorDepthMax, gbs->s_minKeyScale,
+                              maxNumKeysPerImage, &b->sift));
     const uint32_t maxNumResiduals = 25 * (maxNumImages * (maxNumImages - 1)) / 2;
     bf_solver_config cfg;
     cfg.optMaxResThresh = gbs->s_optMaxResThresh; cfg.denseDistThresh = gbs->s_denseDistThresh; cfg.denseNormalThresh = gbs->s_denseNormalThresh;
     cfg.denseColorThresh = gbs->s_denseColorThresh; cfg.denseColorGradientMin = gbs->s_denseColorGradientMin; cfg.denseDepthMin = gbs->s_denseDepthMin;
     cfg.denseDepthMax = gbs->s_denseDepthMax; cfg.denseOverlapCheckSubsampleFactor = gbs->s_denseOverlapCheckSubsampleFactor;
     cfg.verifyOptDistThresh = 0.02f; cfg.verifyOptPercentThresh = 0.05f; cfg.recordConvergence = gbs->s_recordSolverConvergence;
-    if (!rc) rc = bf_solver_create(maxNumImages, maxNumResiduals, &cfg, &b->solver);
-    if (!rc) rc = bf_cache_create(sn.depthWidth, sn.depthHeight, gbs->s_downsampledWidth, gbs->s_downsampledHeight, maxNumImages, manager->siftDepthIntrinsics.e,
-                                  gbs->s_colorDownSigma, gbs->s_depthDownSigmaD, gbs->s_depthDownSigmaR, &b->cache);
-    if (!rc) rc = bf_siftmgr_create(maxNumImages, maxNumKeysPerImage, &b->mgr);
-    if (rc) { bf_bundler_destroy(b); return rc; }
-    BF_HIP_TRY(BF_MALLOC((void**)&b->d_trajectory, sizeof(m44) * (maxNumImages + 1)));
-    BF_HIP_TRY(BF_MALLOC((void**)&b->d_xRot, sizeof(float) * 3 * maxNumImages));
-    BF_HIP_TRY(BF_MALLOC((void**)&b->d_xTrans, sizeof(float) * 3 * maxNumImages));
+    BF_TRY(bf_solver_create(maxNumImages, maxNumResiduals, &cfg, &b->solver));
+    BF_TRY(bf_cache_create(sn.depthWidth, sn.depthHeight, gbs->s_downsampledWidth, gbs->s_downsampledHeight, maxNumImages, manager->siftDepthIntrinsics.e,
+                           gbs->s_colorDownSigma, gbs->s_depthDownSigmaD, gbs->s_depthDownSigmaR, &b->cache));
+    BF_TRY(bf_siftmgr_create(maxNumImages, maxNumKeysPerImage, &b->mgr));
+    BF_TRY(b->res.device(&b->d_trajectory, (size_t)maxNumImages + 1));
+    BF_TRY(b->res.device(&b->d_xRot, 3 * (size_t)maxNumImages));
+    BF_TRY(b->res.device(&b->d_xTrans, 3 * (size_t)maxNumImages));
     k_fill_identity<<<div_up(maxNumImages + 1, 64), 64>>>(b->d_trajectory, maxNumImages + 1);
     BF_HIP_TRY(hipDeviceSynchronize());
     const uint32_t maxNumIts = std::max(gbs->s_numGlobalNonLinIterations, gbs->s_numLocalNonLinIterations);     // SBA.cpp:28-38
@@ -844,7 +840,7 @@ int bf_bundler_create(uint32_t maxNumImages, uint32_t maxNumKeysPerImage, const 
     b->useGlobalDenseOpt = false;
     b->comprehensive = gbs->s_useComprehensiveFrameInvalidation != 0;          // SBA.h:31-32
     b->useLocalDense = gbs->s_useLocalDense != 0;
-    *out = b;
+    *out = guard.dismiss();
     return BF_OK;
 }
 
@@ -852,7 +848,6 @@ int bf_bundler_destroy(bf_bundler* b) {
     if (!b) return BF_OK;
     bf_sift_destroy(b->sift); bf_solver_destroy(b->solver); bf_cache_destroy(b->cache); bf_siftmgr_destroy(b->mgr);
     bf_correspondence_evaluator_destroy(b->corrEvaluator);
-    (void)hipFree(b->d_trajectory); (void)hipFree(b->d_xRot); (void)hipFree(b->d_xTrans);
     delete b;
     return BF_OK;
 }
@@ -1330,6 +1325,7 @@ struct bf_online_bundler {
     bool isLastLocalFrame(uint32_t curFrame) const { return curFrame >= submapSize && (curFrame % submapSize) == 0; }
     void invalidateImages(uint32_t s, uint32_t e = 0xFFFFFFFFu) { if (e == 0xFFFFFFFFu) invalidImagesList[s] = 0; else for (uint32_t i = s; i < e; ++i) invalidImagesList[i] = 0; }
     void validateImages(uint32_t s) { invalidImagesList[s] = 1; }
+    bf::Resources res;
 };
 
 namespace {
@@ -1571,6 +1567,7 @@ int bf_online_bundler_create(const bf_rgbd_sensor_desc* sensor, bf_image_manager
                              bf_online_bundler** out) {
     BF_REQUIRE(sensor && im && gas && gbs && out, "null argument");
     bf_online_bundler* ob = new bf_online_bundler;
+    bf::CreateGuard<bf_online_bundler> guard(ob, bf_online_bundler_destroy);
     ob->gas = *gas; ob->gbs = *gbs; ob->im = im;
     ob->depthW = sensor->depthWidth; ob->depthH = sensor->depthHeight; ob->colorW = sensor->colorWidth; ob->colorH = sensor->colorHeight;
     ob->widthSIFT = gbs->s_widthSIFT; ob->heightSIFT = gbs->s_heightSIFT;
@@ -1578,39 +1575,39 @@ int bf_online_bundler_create(const bf_rgbd_sensor_desc* sensor, bf_image_manager
     ob->siftIntrinsicsInv = inverse44(ob->siftIntrinsics);
     ob->submapSize = gbs->s_submapSize; ob->numOptPerResidualRemoval = std::max(gbs->s_numOptPerResidualRemoval, 1u);
     const uint32_t maxNumImages = gbs->s_maxNumImages, S = ob->submapSize;
-    int rc = bf_bundler_create(S + 1, gbs->s_maxNumKeysPerImage, ob->siftIntrinsicsInv.e, im, 1, gas, gbs, &ob->local);
-    if (!rc) rc = bf_bundler_create(S + 1, gbs->s_maxNumKeysPerImage, ob->siftIntrinsicsInv.e, im, 1, gas, gbs, &ob->optLocal);
-    if (!rc) rc = bf_bundler_create(maxNumImages, gbs->s_maxNumKeysPerImage, ob->siftIntrinsicsInv.e, im, 0, gas, gbs, &ob->global);
-    if (!rc) rc = bf_trajectory_manager_create(maxNumImages * S, gas->s_topNActive, gas->s_minPoseDistSqrt, &ob->tm);
-    if (!rc) rc = bf_bundler_create(bf_online_bundler::STAGE, gbs->s_maxNumKeysPerImage, ob->siftIntrinsicsInv.e, im, 1, gas, gbs, &ob->stage);
-    for (uint32_t k = 0; k < bf_online_bundler::STAGE && !rc; ++k) {                     // the staging slots exist from the start (empty images)
+    BF_TRY(bf_bundler_create(S + 1, gbs->s_maxNumKeysPerImage, ob->siftIntrinsicsInv.e, im, 1, gas, gbs, &ob->local));
+    BF_TRY(bf_bundler_create(S + 1, gbs->s_maxNumKeysPerImage, ob->siftIntrinsicsInv.e, im, 1, gas, gbs, &ob->optLocal));
+    BF_TRY(bf_bundler_create(maxNumImages, gbs->s_maxNumKeysPerImage, ob->siftIntrinsicsInv.e, im, 0, gas, gbs, &ob->global));
+    BF_TRY(bf_trajectory_manager_create(maxNumImages * S, gas->s_topNActive, gas->s_minPoseDistSqrt, &ob->tm));
+    BF_TRY(bf_bundler_create(bf_online_bundler::STAGE, gbs->s_maxNumKeysPerImage, ob->siftIntrinsicsInv.e, im, 1, gas, gbs, &ob->stage));
+    for (uint32_t k = 0; k < bf_online_bundler::STAGE; ++k) {                     // the staging slots exist from the start (empty images)
         bf_sift_image_gpu img;
-        rc = bf_siftmgr_create_image(ob->stage->mgr, &img);
-        if (!rc) rc = bf_siftmgr_finalize_image(ob->stage->mgr, 0);
+        BF_TRY(bf_siftmgr_create_image(ob->stage->mgr, &img));
+        BF_TRY(bf_siftmgr_finalize_image(ob->stage->mgr, 0));
     }
-    if (rc) { bf_online_bundler_destroy(ob); return rc; }
+    bf::Resources& R = ob->res;
     for (uint32_t k = 0; k < bf_online_bundler::STAGE; ++k) {
-        BF_HIP_TRY(hipEventCreateWithFlags(&ob->evDetect[k], hipEventDisableTiming));
-        BF_HIP_TRY(hipEventCreateWithFlags(&ob->evCache[k], hipEventDisableTiming));
-        BF_HIP_TRY(hipEventCreateWithFlags(&ob->evStageFree[k], hipEventDisableTiming));
+        BF_TRY(R.event(&ob->evDetect[k], hipEventDisableTiming));
+        BF_TRY(R.event(&ob->evCache[k], hipEventDisableTiming));
+        BF_TRY(R.event(&ob->evStageFree[k], hipEventDisableTiming));
     }
-    const size_t nAll = (size_t)maxNumImages * S;
-    BF_HIP_TRY(BF_MALLOC((void**)&ob->d_intensitySIFT, sizeof(float) * ob->widthSIFT * ob->heightSIFT));
-    BF_HIP_TRY(BF_MALLOC((void**)&ob->d_intensityFilterHelper, sizeof(float) * ob->widthSIFT * ob->heightSIFT));
-    BF_HIP_TRY(BF_MALLOC((void**)&ob->d_completeTrajectory, sizeof(m44) * nAll));
-    BF_HIP_TRY(BF_MALLOC((void**)&ob->d_localTrajectories, sizeof(m44) * (size_t)maxNumImages * (S + 1)));
-    BF_HIP_TRY(BF_MALLOC((void**)&ob->d_siftTrajectory, sizeof(m44) * nAll));
-    BF_HIP_TRY(BF_MALLOC((void**)&ob->d_currIntegrateTransform, sizeof(m44) * nAll));
-    BF_HIP_TRY(BF_MALLOC((void**)&ob->d_imageInvalidateList, sizeof(int) * nAll));
-    BF_HIP_TRY(hipHostMalloc((void**)&ob->h_pinT, bf_online_bundler::PEND * sizeof(m44)));
-    BF_HIP_TRY(BF_MALLOC((void**)&ob->d_completeShadow, sizeof(m44) * nAll));
+    const size_t nAll = (size_t)maxNumImages * S, nSift = (size_t)ob->widthSIFT * ob->heightSIFT;
+    BF_TRY(R.device(&ob->d_intensitySIFT, nSift));
+    BF_TRY(R.device(&ob->d_intensityFilterHelper, nSift));
+    BF_TRY(R.device(&ob->d_completeTrajectory, nAll));
+    BF_TRY(R.device(&ob->d_localTrajectories, (size_t)maxNumImages * (S + 1)));
+    BF_TRY(R.device(&ob->d_siftTrajectory, nAll));
+    BF_TRY(R.device(&ob->d_currIntegrateTransform, nAll));
+    BF_TRY(R.device(&ob->d_imageInvalidateList, nAll));
+    BF_TRY(R.pinned(&ob->h_pinT, bf_online_bundler::PEND * sizeof(m44)));
+    BF_TRY(R.device(&ob->d_completeShadow, nAll));
     BF_HIP_TRY(hipMemset(ob->d_completeShadow, 0, sizeof(m44) * nAll));
-    BF_HIP_TRY(hipEventCreateWithFlags(&ob->evChunk, hipEventDisableTiming));
-    BF_HIP_TRY(hipEventCreateWithFlags(&ob->evChunkCopy, hipEventDisableTiming));
+    BF_TRY(R.event(&ob->evChunk, hipEventDisableTiming));
+    BF_TRY(R.event(&ob->evChunkCopy, hipEventDisableTiming));
     for (int k = 0; k < 2; ++k) {
-        BF_HIP_TRY(hipEventCreateWithFlags(&ob->evImage[k], hipEventDisableTiming));
-        BF_HIP_TRY(hipEventCreateWithFlags(&ob->evPairDone[k], hipEventDisableTiming));
-        BF_HIP_TRY(hipEventCreateWithFlags(&ob->evPairSetFree[k], hipEventDisableTiming));
+        BF_TRY(R.event(&ob->evImage[k], hipEventDisableTiming));
+        BF_TRY(R.event(&ob->evPairDone[k], hipEventDisableTiming));
+        BF_TRY(R.event(&ob->evPairSetFree[k], hipEventDisableTiming));
     }
     k_fill_identity<<<div_up((uint32_t)(maxNumImages * (S + 1)), 64), 64>>>(ob->d_localTrajectories, maxNumImages * (S + 1));
     k_fill_identity<<<1, 64>>>(ob->d_siftTrajectory, 1);
@@ -1621,24 +1618,15 @@ int bf_online_bundler_create(const bf_rgbd_sensor_desc* sensor, bf_image_manager
     ob->invalidImagesList.assign(nAll, 1);
     ob->currIntegrateTransform.assign(nAll, minfM());
     ob->currIntegrateTransform[0] = identity44();
-    *out = ob;
+    *out = guard.dismiss();
     return BF_OK;
 }
 
 int bf_online_bundler_destroy(bf_online_bundler* ob) {
     if (!ob) return BF_OK;
     if (ob->job.th.joinable()) ob->job.th.join();
-    (void)hipFree(ob->d_completeShadow);
-    if (ob->evChunk) (void)hipEventDestroy(ob->evChunk);
-    if (ob->evChunkCopy) (void)hipEventDestroy(ob->evChunkCopy);
-    for (int k = 0; k < 2; ++k) for (hipEvent_t e : {ob->evImage[k], ob->evPairDone[k], ob->evPairSetFree[k]}) if (e) (void)hipEventDestroy(e);
     bf_bundler_destroy(ob->local); bf_bundler_destroy(ob->optLocal); bf_bundler_destroy(ob->global); bf_bundler_destroy(ob->stage); bf_trajectory_manager_destroy(ob->tm);
-    for (uint32_t k = 0; k < bf_online_bundler::STAGE; ++k) { if (ob->evDetect[k]) (void)hipEventDestroy(ob->evDetect[k]); if (ob->evCache[k]) (void)hipEventDestroy(ob->evCache[k]); if (ob->evStageFree[k]) (void)hipEventDestroy(ob->evStageFree[k]); }
-    if (ob->sift2) bf_sift_destroy(ob->sift2);
-    (void)hipFree(ob->d_intensitySIFT2); (void)hipFree(ob->d_intensityFilterHelper2);
-    (void)hipFree(ob->d_intensitySIFT); (void)hipFree(ob->d_intensityFilterHelper); (void)hipFree(ob->d_completeTrajectory); (void)hipFree(ob->d_localTrajectories);
-    (void)hipFree(ob->d_siftTrajectory); (void)hipFree(ob->d_currIntegrateTransform); (void)hipFree(ob->d_imageInvalidateList);
-    if (ob->h_pinT) (void)hipHostFree(ob->h_pinT);
+    bf_sift_destroy(ob->sift2);
     delete ob;
     return BF_OK;
 }
@@ -1691,12 +1679,10 @@ int bf_online_bundler_set_second_detect_stream(bf_online_bundler* ob, void* s) {
     BF_REQUIRE(ob && ob->detectStream, "set_second_detect_stream needs bf_online_bundler_set_detect_stream first");
     ob->detectStream2 = (hipStream_t)s;
     if (!s) return BF_OK;
-    if (!ob->sift2) {
-        const bf_bundler* b = ob->stage;
-        BF_TRY(bf_sift_create(b->gbs.s_widthSIFT, b->gbs.s_heightSIFT, ob->depthW, ob->depthH, 150, b->gas.s_sensorDepthMin, b->gas.s_sensorDepthMax, b->gbs.s_minKeyScale, b->maxKeys, &ob->sift2));
-        BF_HIP_TRY(BF_MALLOC((void**)&ob->d_intensitySIFT2, sizeof(float) * ob->widthSIFT * ob->heightSIFT));
-        BF_HIP_TRY(BF_MALLOC((void**)&ob->d_intensityFilterHelper2, sizeof(float) * ob->widthSIFT * ob->heightSIFT));
-    }
+    const bf_bundler* b = ob->stage;
+    if (!ob->sift2) BF_TRY(bf_sift_create(b->gbs.s_widthSIFT, b->gbs.s_heightSIFT, ob->depthW, ob->depthH, 150, b->gas.s_sensorDepthMin, b->gas.s_sensorDepthMax, b->gbs.s_minKeyScale, b->maxKeys, &ob->sift2));
+    if (!ob->d_intensitySIFT2) BF_TRY(ob->res.device(&ob->d_intensitySIFT2, (size_t)ob->widthSIFT * ob->heightSIFT));
+    if (!ob->d_intensityFilterHelper2) BF_TRY(ob->res.device(&ob->d_intensityFilterHelper2, (size_t)ob->widthSIFT * ob->heightSIFT));
     return bf_sift_set_stream(ob->sift2, s);
 }
 
@@ -2152,9 +2138,19 @@ struct bf_pipeline {
     bool timings = false;
     hipEvent_t ev[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     bf_frame_timing last;
+    bf::Resources res;
 };
 
 namespace {
+
+// one of the pipeline's own streams
+int plStream(bf_pipeline* p, hipStream_t* s, int priority) {
+    hipStream_t st = nullptr;
+    BF_HIP_TRY(hipStreamCreateWithPriority(&st, hipStreamNonBlocking, priority));
+    BF_TRY(p->res.adopt(st));
+    *s = st;
+    return BF_OK;
+}
 
 // a volume operator on frame `frame`: its pointers, texels and event are resolved here, on the calling thread
 int volPost(bf_pipeline* p, VolumeQueue::Op op, uint32_t frame, const float* T0, const float* T1, int waitEv) {
@@ -2322,8 +2318,8 @@ int plFrame(bf_pipeline* p, const float* depth, const uint8_t* color, bool devic
     if (tm) { (void)hipEventRecord(p->ev[1], sd); (void)hipEventRecord(p->ev[8], sa); }
     if (got && !p->tracePath.empty() && p->trace.size() < 4096) {
         bf_pipeline::TraceRec r; memset(&r, 0, sizeof r); r.frame = frame; r.hDet0 = tIn;
-        (void)hipEventCreate(&r.gDet); (void)hipEventCreate(&r.gChain0); (void)hipEventCreate(&r.gChain1);
-        if (!p->traceBase) { (void)hipEventCreate(&p->traceBase); (void)hipEventRecord(p->traceBase, p->sDetect); (void)hipEventSynchronize(p->traceBase); p->traceBaseHost = plNow(); }
+        (void)p->res.event(&r.gDet); (void)p->res.event(&r.gChain0); (void)p->res.event(&r.gChain1);          // (BF_PIPELINE_TRACE only: kept until the pipeline goes)
+        if (!p->traceBase) { (void)p->res.event(&p->traceBase); (void)hipEventRecord(p->traceBase, p->sDetect); (void)hipEventSynchronize(p->traceBase); p->traceBaseHost = plNow(); }
         p->trace.push_back(r);
     }
     if (got && ahead) BF_TRY(bf_online_bundler_detect_ahead_after(p->ob, p->evIngest[frame % bf_pipeline::NEV]));
@@ -2366,14 +2362,15 @@ int bf_pipeline_create(const bf_global_app_state* gas, const bf_global_bundling_
     BF_REQUIRE(gas && gbs && sensor && out, "null argument");
     BF_REQUIRE(!gas->s_streamingEnabled, "chunk streaming is not part of the BundleFusion path (zParametersDefault.txt:100)");
     bf_pipeline* p = new bf_pipeline;
+    bf::CreateGuard<bf_pipeline> guard(p, bf_pipeline_destroy);
     p->gas = *gas; p->gbs = *gbs; p->sensor = *sensor;
     memset(&p->last, 0, sizeof p->last);
-    int rc = bf_image_manager_create(gas->s_integrationWidth, gas->s_integrationHeight, gbs->s_widthSIFT, gbs->s_heightSIFT, sensor, gbs, 1, &p->im);
+    BF_TRY(bf_image_manager_create(gas->s_integrationWidth, gas->s_integrationHeight, gbs->s_widthSIFT, gbs->s_heightSIFT, sensor, gbs, 1, &p->im));
     // (bf_image_manager_set_store_texels - a third plane per stored frame, depth and colour interleaved for the fast voxel update - is not used here: measured no
     // gain, 680 vs 685 frames/s, gpurun r04l; since round 5 the batch's march writes the texels of its operators.)
-    if (!rc && gas->s_bUseCameraCalibration)
-        rc = bf_image_manager_set_camera_calibration(p->im, 1, gas->s_remappingDepthDiscontinuityThresOffset, gas->s_remappingDepthDiscontinuityThresLin);
-    if (!rc) rc = bf_online_bundler_create(sensor, p->im, gas, gbs, &p->ob);
+    if (gas->s_bUseCameraCalibration)
+        BF_TRY(bf_image_manager_set_camera_calibration(p->im, 1, gas->s_remappingDepthDiscontinuityThresOffset, gas->s_remappingDepthDiscontinuityThresLin));
+    BF_TRY(bf_online_bundler_create(sensor, p->im, gas, gbs, &p->ob));
     bf_hash_params hp;                                          // CUDASceneRepHashSDF::parametersFromGlobalAppState :39-59
     memset(&hp, 0, sizeof hp);
     const m44 I = identity44();
@@ -2384,22 +2381,21 @@ int bf_pipeline_create(const bf_global_app_state* gas, const bf_global_bundling_
     hp.m_integrationWeightSample = gas->s_SDFIntegrationWeightSample; hp.m_integrationWeightMax = gas->s_SDFIntegrationWeightMax;
     for (int i = 0; i < 3; ++i) { hp.m_streamingVoxelExtents[i] = gas->s_streamingVoxelExtents[i]; hp.m_streamingGridDimensions[i] = gas->s_streamingGridDimensions[i]; hp.m_streamingMinGridPos[i] = gas->s_streamingMinGridPos[i]; }
     hp.m_streamingInitialChunkListSize = gas->s_streamingInitialChunkListSize;
-    if (!rc) rc = bf_scene_create(&hp, &p->scene);
-    if (rc) { bf_pipeline_destroy(p); return rc; }
+    BF_TRY(bf_scene_create(&hp, &p->scene));
     {   // registered depth lives in the colour camera: integrate with its intrinsics (DepthSensing.cpp:285-288)
         const m44& K = p->im->calib ? p->im->colorIntrinsics : p->im->depthIntrinsics;
         p->cam.fx = K.e[0]; p->cam.fy = K.e[5]; p->cam.mx = K.e[2]; p->cam.my = K.e[6];
     }
     p->cam.m_sensorDepthWorldMin = gas->s_renderDepthMin; p->cam.m_sensorDepthWorldMax = gas->s_renderDepthMax;      // DepthSensing.cpp:636-643
     p->cam.m_imageWidth = gas->s_integrationWidth; p->cam.m_imageHeight = gas->s_integrationHeight;
-    for (auto& e : p->ev) BF_HIP_TRY(hipEventCreate(&e));
-    for (auto& e : p->evIngest) BF_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    for (auto& e : p->ev) BF_TRY(p->res.event(&e));
+    for (auto& e : p->evIngest) BF_TRY(p->res.event(&e, hipEventDisableTiming));
     BF_HIP_TRY(hipDeviceSynchronize());                                  // creation-time work was issued on the null stream
     {   // the feature pipeline is a chain of small latency-bound kernels with a host read-back at its end: it gets priority over
         // the wide, throughput-bound voxel updates of the volume stream
         int least = 0, greatest = 0;
         BF_HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
-        BF_HIP_TRY(hipStreamCreateWithPriority(&p->sBundle, hipStreamNonBlocking, greatest));
+        BF_TRY(plStream(p, &p->sBundle, greatest));
         // The volume stream may use all but `reserve` compute units (BF_VOLUME_CU_RESERVE, 0: the whole device at the lowest queue priority): the matching chain is
         // ~20 dependent small launches, and behind a batched voxel update that fills every CU each of them waits for waves to retire.  With the frame's operators
         // batched the volume queue is busy about half of the time, so the slower update costs nothing: 873 / 893 / 939 / 944 frames/s at R = 0 / 16 / 32 / 64, the
@@ -2413,19 +2409,22 @@ int bf_pipeline_create(const bf_global_app_state* gas, const bf_global_bundling_
             const uint32_t ncu = (uint32_t)prop.multiProcessorCount, use = ncu > reserve ? ncu - reserve : 1u;
             std::vector<uint32_t> mask((ncu + 31u) / 32u, 0u);
             for (uint32_t i = 0; i < use; ++i) mask[i >> 5] |= 1u << (i & 31u);
-            BF_HIP_TRY(hipExtStreamCreateWithCUMask(&p->sVolume, (uint32_t)mask.size(), mask.data()));
+            hipStream_t masked = nullptr;
+            BF_HIP_TRY(hipExtStreamCreateWithCUMask(&masked, (uint32_t)mask.size(), mask.data()));
+            BF_TRY(p->res.adopt(masked));
+            p->sVolume = masked;
         } else
-        BF_HIP_TRY(hipStreamCreateWithPriority(&p->sVolume, hipStreamNonBlocking, least));
-        BF_HIP_TRY(hipStreamCreateWithPriority(&p->sDetect, hipStreamNonBlocking, greatest));
+        BF_TRY(plStream(p, &p->sVolume, least));
+        BF_TRY(plStream(p, &p->sDetect, greatest));
         // The HIP runtime maps streams onto a small pool of hardware queues (GPU_MAX_HW_QUEUES, four by default) by priority class and creation order, and streams
         // that share a queue serialise.  Which streams exist - even idle ones - therefore decides the frame rate: measured on one box (gpurun r04i - r04k) 710
         // frames/s with exactly this set in exactly this order (allocation [the scene's], bundling, volume, detection, solve, ingest, pair x 2), 440 - 660 with
         // any other set tried (a second preparation stream, no solve / pair streams, the ingest on the bundling stream, 2 - 16 queues requested).  Round 6, with the
         // volume on a masked stream and the lagged schedule: eight creation orders of the five streams below gave 937 - 1037 frames/s, this one 985 - 1005 (gpurun r06m / r06n:
         // within the spread; whichever streams share a queue, the waits move and their sum stays - profiles/r06_loop_schedule.md).
-        BF_HIP_TRY(hipStreamCreateWithPriority(&p->sSolve, hipStreamNonBlocking, greatest));
-        BF_HIP_TRY(hipStreamCreateWithPriority(&p->sIngest, hipStreamNonBlocking, greatest));
-        for (auto& st : p->sPair) BF_HIP_TRY(hipStreamCreateWithPriority(&st, hipStreamNonBlocking, greatest));
+        BF_TRY(plStream(p, &p->sSolve, greatest));
+        BF_TRY(plStream(p, &p->sIngest, greatest));
+        for (auto& st : p->sPair) BF_TRY(plStream(p, &st, greatest));
     }
     if (const char* e = getenv("BF_PIPELINE_LOOKAHEAD")) p->lookahead = atoi(e) != 0;
     if (const char* e = getenv("BF_PIPELINE_DEPTH")) p->depth = (uint32_t)std::min(std::max(atoi(e), 2), std::min<int>(bf_online_bundler::PEND, (int)bf_online_bundler::STAGE));
@@ -2453,7 +2452,7 @@ int bf_pipeline_create(const bf_global_app_state* gas, const bf_global_bundling_
     int dev = 0;
     BF_HIP_TRY(hipGetDevice(&dev));
     p->vol.start(p->scene, p->cam, dev);
-    *out = p;
+    *out = guard.dismiss();
     return BF_OK;
 }
 
@@ -2673,21 +2672,12 @@ int bf_pipeline_destroy(bf_pipeline* p) {
                 const double b = p->traceBaseHost;
                 fprintf(f, "%5u | %8.3f %8.3f  %8.3f %8.3f  %8.3f %8.3f  %8.3f | %8.3f %8.3f %8.3f\n", r.frame, 1e3 * (r.hDet0 - b), 1e3 * (r.hDet1 - b), 1e3 * (r.hEnq0 - b), 1e3 * (r.hEnq1 - b),
                         1e3 * (r.hWait0 - b), 1e3 * (r.hWait1 - b), 1e3 * (r.hBody1 - b), gd, g0, g1);
-                (void)hipEventDestroy(r.gDet); (void)hipEventDestroy(r.gChain0); (void)hipEventDestroy(r.gChain1);
             }
             fclose(f);
         }
     }
     bf_online_bundler_destroy(p->ob); bf_image_manager_destroy(p->im); bf_scene_destroy(p->scene);
-    for (auto& e : p->ev) if (e) (void)hipEventDestroy(e);
-    for (auto& e : p->evIngest) if (e) (void)hipEventDestroy(e);
-    if (p->sBundle) (void)hipStreamDestroy(p->sBundle);
-    if (p->sVolume) (void)hipStreamDestroy(p->sVolume);
-    if (p->sDetect) (void)hipStreamDestroy(p->sDetect);
-    if (p->sSolve) (void)hipStreamDestroy(p->sSolve);
-    if (p->sIngest) (void)hipStreamDestroy(p->sIngest);
-    for (auto st : p->sPair) if (st) (void)hipStreamDestroy(st);
-    delete p;
+    delete p;          // the streams go last, behind everything that ran on them
     return BF_OK;
 }
 
@@ -2707,7 +2697,7 @@ int bf_pipeline_set_solve_lag(bf_pipeline* p, uint32_t lag) {
         // then starved by the volume stream's wide launches and a chunk's solves take longer than the ten frames they have
         int least = 0, greatest = 0;
         BF_HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
-        BF_HIP_TRY(hipStreamCreateWithPriority(&p->sSolve, hipStreamNonBlocking, greatest));
+        BF_TRY(plStream(p, &p->sSolve, greatest));
     }
     return bf_online_bundler_set_solve_lag(p->ob, lag, p->sSolve);
 }
@@ -2861,6 +2851,7 @@ struct bf_chunk_worker {
     hipStream_t stream = nullptr;
     uint32_t cacheW = 0, cacheH = 0;
     uint64_t packageBytes = 0, offKeys = 0, offDescs = 0, offCache[6] = {0, 0, 0, 0, 0, 0};
+    bf::Resources res;
 };
 
 extern "C" {
@@ -2869,19 +2860,19 @@ int bf_chunk_worker_create(const bf_global_app_state* gas, const bf_global_bundl
     BF_REQUIRE(gas && gbs && sensor && out, "null argument");
     BF_REQUIRE(gbs->s_submapSize + 1 <= BF_CHUNK_MAX_FRAMES, "s_submapSize + 1 exceeds BF_CHUNK_MAX_FRAMES");
     bf_chunk_worker* w = new bf_chunk_worker;
+    bf::CreateGuard<bf_chunk_worker> guard(w, bf_chunk_worker_destroy);
     w->gas = *gas; w->gbs = *gbs; w->sensor = *sensor;
     w->siftIntrinsics = scaleIntrinsics(sensor->colorIntrinsics, gbs->s_widthSIFT, gbs->s_heightSIFT, sensor->colorWidth, sensor->colorHeight);
     w->siftIntrinsicsInv = inverse44(w->siftIntrinsics);
-    int rc = bf_image_manager_create(gas->s_integrationWidth, gas->s_integrationHeight, gbs->s_widthSIFT, gbs->s_heightSIFT, sensor, gbs, 2, &w->im);
-    if (!rc && gas->s_bUseCameraCalibration)            // the worker's ingest sees the frames the main loop's does
-        rc = bf_image_manager_set_camera_calibration(w->im, 1, gas->s_remappingDepthDiscontinuityThresOffset, gas->s_remappingDepthDiscontinuityThresLin);
-    if (!rc) rc = bf_bundler_create(gbs->s_submapSize + 1, gbs->s_maxNumKeysPerImage, w->siftIntrinsicsInv.e, w->im, 1, gas, gbs, &w->local);
-    if (!rc) rc = bf_siftmgr_create(2, gbs->s_maxNumKeysPerImage, &w->fuseMgr);
-    if (rc) { bf_chunk_worker_destroy(w); return rc; }
+    BF_TRY(bf_image_manager_create(gas->s_integrationWidth, gas->s_integrationHeight, gbs->s_widthSIFT, gbs->s_heightSIFT, sensor, gbs, 2, &w->im));
+    if (gas->s_bUseCameraCalibration)            // the worker's ingest sees the frames the main loop's does
+        BF_TRY(bf_image_manager_set_camera_calibration(w->im, 1, gas->s_remappingDepthDiscontinuityThresOffset, gas->s_remappingDepthDiscontinuityThresLin));
+    BF_TRY(bf_bundler_create(gbs->s_submapSize + 1, gbs->s_maxNumKeysPerImage, w->siftIntrinsicsInv.e, w->im, 1, gas, gbs, &w->local));
+    BF_TRY(bf_siftmgr_create(2, gbs->s_maxNumKeysPerImage, &w->fuseMgr));
     const size_t nS = (size_t)gbs->s_widthSIFT * gbs->s_heightSIFT;
-    BF_HIP_TRY(BF_MALLOC((void**)&w->d_intensity, nS * 4));
-    BF_HIP_TRY(BF_MALLOC((void**)&w->d_intensityHelper, nS * 4));
-    BF_HIP_TRY(BF_MALLOC((void**)&w->d_rec, sizeof(bf_chunk_frame_record) * BF_CHUNK_MAX_FRAMES));
+    BF_TRY(w->res.device(&w->d_intensity, nS));
+    BF_TRY(w->res.device(&w->d_intensityHelper, nS));
+    BF_TRY(w->res.device(&w->d_rec, BF_CHUNK_MAX_FRAMES));
     float k4[4];
     BF_TRY(bf_cache_get_geometry(w->local->cache, &w->cacheW, &w->cacheH, k4));
     const uint64_t n = (uint64_t)w->cacheW * w->cacheH, mk = gbs->s_maxNumKeysPerImage;
@@ -2892,7 +2883,7 @@ int bf_chunk_worker_create(const bf_global_app_state* gas, const bf_global_bundl
     for (int k = 0; k < 6; ++k) { w->offCache[k] = off; off += cb[k]; }
     w->packageBytes = (off + 255) / 256 * 256;
     BF_HIP_TRY(hipDeviceSynchronize());
-    *out = w;
+    *out = guard.dismiss();
     return BF_OK;
 }
 
@@ -2900,7 +2891,6 @@ int bf_chunk_worker_destroy(bf_chunk_worker* w) {
     if (!w) return BF_OK;
     (void)hipDeviceSynchronize();
     bf_bundler_destroy(w->local); bf_siftmgr_destroy(w->fuseMgr); bf_image_manager_destroy(w->im);
-    (void)hipFree(w->d_intensity); (void)hipFree(w->d_intensityHelper); (void)hipFree(w->d_rec);
     delete w;
     return BF_OK;
 }

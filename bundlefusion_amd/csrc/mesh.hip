@@ -30,7 +30,7 @@
 #include <vector>
 
 #include "bf_device.h"
-#include "bf_internal.h"
+#include "bf_resources.h"
 #include "bf_meshweld.h"
 #include "bf_volume.h"
 
@@ -312,6 +312,7 @@ struct bf_marching_cubes {
     uint32_t numTrianglesFound = 0;     // before clamping
     std::vector<bf_mc_triangle> mesh;   // m_meshData: triangles accumulated by copyTrianglesToCPU
     MeshWeld weld;                      // the indexed mesh of the last bf_marching_cubes_weld, in HBM (meshweld.hip)
+    bf::Resources res;                  // owns every buffer above, the weld's included
 };
 
 extern "C" {
@@ -328,24 +329,22 @@ int bf_marching_cubes_create(const bf_marching_cubes_params* p, bf_marching_cube
     BF_REQUIRE(p && out, "bad argument");          // m_maxNumTriangles == 0: the triangle buffer is sized to the volume by every extraction
     BF_REQUIRE(p->m_sdfBlockSize == BF_SDF_BLOCK_SIZE && p->m_hashBucketSize == BF_HASH_BUCKET_SIZE, "block size 8 / bucket size 4 expected");
     bf_marching_cubes* m = new bf_marching_cubes;
+    bf::CreateGuard<bf_marching_cubes> guard(m, bf_marching_cubes_destroy);
     m->params = *p;
     McTables t; makeTables(t);
-    BF_HIP_TRY(BF_MALLOC((void**)&m->d_tables, sizeof t));
+    BF_TRY(m->res.device(&m->d_tables, 1));
     BF_HIP_TRY(hipMemcpy(m->d_tables, &t, sizeof t, hipMemcpyHostToDevice));
-    if (p->m_maxNumTriangles) BF_HIP_TRY(BF_MALLOC((void**)&m->d_triangles, sizeof(bf_mc_triangle) * (size_t)p->m_maxNumTriangles));
+    if (p->m_maxNumTriangles) BF_TRY(m->res.device(&m->d_triangles, p->m_maxNumTriangles));
     m->capTriangles = p->m_maxNumTriangles;
-    BF_HIP_TRY(BF_MALLOC((void**)&m->d_numBlocks, 4));
-    BF_HIP_TRY(BF_MALLOC((void**)&m->d_total, 4));
-    *out = m;
+    BF_TRY(m->res.device(&m->d_numBlocks, 1));
+    BF_TRY(m->res.device(&m->d_total, 1));
+    *out = guard.dismiss();
     return BF_OK;
 }
 
 int bf_marching_cubes_destroy(bf_marching_cubes* m) {
     if (!m) return BF_OK;
     (void)hipDeviceSynchronize();
-    (void)hipFree(m->d_tables); (void)hipFree(m->d_triangles); (void)hipFree(m->d_numBlocks); (void)hipFree(m->d_total);
-    (void)hipFree(m->d_tileCounts); (void)hipFree(m->d_slots); (void)hipFree(m->d_blockCounts);
-    meshweld_free(m->weld);
     delete m;
     return BF_OK;
 }
@@ -361,10 +360,11 @@ static int mcExtract(bf_marching_cubes* m, const bf_hash_data* hd, const bf_hash
     const uint32_t numSlots = hp->m_hashNumBuckets * BF_HASH_BUCKET_SIZE;
     const uint32_t numTiles = div_up(numSlots, TILE);
     if (numSlots > m->capSlots) {
-        (void)hipFree(m->d_tileCounts); (void)hipFree(m->d_slots); (void)hipFree(m->d_blockCounts);
-        BF_HIP_TRY(BF_MALLOC((void**)&m->d_tileCounts, 4 * (size_t)(numTiles + 1)));
-        BF_HIP_TRY(BF_MALLOC((void**)&m->d_slots, 4 * (size_t)numSlots));
-        BF_HIP_TRY(BF_MALLOC((void**)&m->d_blockCounts, 4 * (size_t)numSlots));
+        m->capSlots = 0;
+        m->res.release(m->d_tileCounts); m->res.release(m->d_slots); m->res.release(m->d_blockCounts);
+        BF_TRY(m->res.device(&m->d_tileCounts, (size_t)numTiles + 1));
+        BF_TRY(m->res.device(&m->d_slots, numSlots));
+        BF_TRY(m->res.device(&m->d_blockCounts, numSlots));
         m->capSlots = numSlots;
     }
     McArgs a;
@@ -392,8 +392,8 @@ static int mcExtract(bf_marching_cubes* m, const bf_hash_data* hd, const bf_hash
         BF_HIP_TRY(hipMemcpyAsync(&need, m->d_total, 4, hipMemcpyDeviceToHost, st));
         BF_HIP_TRY(hipStreamSynchronize(st));
         if (need > m->capTriangles) {
-            (void)hipFree(m->d_triangles); m->d_triangles = nullptr; m->capTriangles = 0;
-            BF_HIP_TRY(BF_MALLOC((void**)&m->d_triangles, sizeof(bf_mc_triangle) * (size_t)need));
+            m->capTriangles = 0;
+            BF_TRY(m->res.regrow(&m->d_triangles, need));
             m->capTriangles = need;
         }
         a.maxTriangles = need;
@@ -489,7 +489,7 @@ int bf_marching_cubes_save_mesh(bf_marching_cubes* m, const char* filename, cons
 int bf_marching_cubes_weld(bf_marching_cubes* m, const bf_mc_triangle* d_triangles, uint32_t numTriangles, const float transform[16], bf_indexed_mesh* out) {
     BF_REQUIRE(m, "null argument");
     if (!d_triangles) { d_triangles = m->d_triangles; numTriangles = m->numTriangles; }
-    BF_TRY(meshweld_run(m->weld, m->stream, d_triangles, numTriangles, transform));
+    BF_TRY(meshweld_run(m->weld, m->res, m->stream, d_triangles, numTriangles, transform));
     if (out) { out->d_positions = m->weld.d_positions; out->d_colors = m->weld.d_colors; out->d_faces = m->weld.d_faces; out->numVertices = m->weld.numVertices; out->numFaces = m->weld.numFaces; }
     return BF_OK;
 }

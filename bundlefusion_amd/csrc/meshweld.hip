@@ -26,7 +26,7 @@
 #include <vector>
 
 #include "bf_device.h"
-#include "bf_internal.h"
+#include "bf_resources.h"
 #include "bf_meshweld.h"
 
 using namespace bf;
@@ -203,23 +203,11 @@ __global__ __launch_bounds__(256) void k_weld_face_ids(const uint32_t* __restric
 
 uint32_t gridFor(uint32_t n) { return std::max(1u, std::min(div_up(n, WG), MAX_GRID)); }
 
-int regrow(void** p, size_t bytes) {
-    (void)hipFree(*p); *p = nullptr;
-    BF_HIP_TRY(BF_MALLOC(p, bytes));
-    return BF_OK;
-}
-
 }  // namespace
 
 namespace bf {
 
-void meshweld_free(MeshWeld& w) {
-    (void)hipFree(w.d_table); (void)hipFree(w.d_rep); (void)hipFree(w.d_vid); (void)hipFree(w.d_faceIds); (void)hipFree(w.d_faceRep); (void)hipFree(w.d_tiles); (void)hipFree(w.d_totals);
-    (void)hipFree(w.d_positions); (void)hipFree(w.d_colors); (void)hipFree(w.d_faces);
-    w = MeshWeld();
-}
-
-int meshweld_run(MeshWeld& w, hipStream_t st, const bf_mc_triangle* d_triangles, uint32_t T, const float transform[16]) {
+int meshweld_run(MeshWeld& w, Resources& res, hipStream_t st, const bf_mc_triangle* d_triangles, uint32_t T, const float transform[16]) {
     w.numVertices = w.numFaces = 0;
     if (T == 0) return BF_OK;
     BF_REQUIRE(d_triangles, "null triangle buffer");
@@ -229,14 +217,14 @@ int meshweld_run(MeshWeld& w, hipStream_t st, const bf_mc_triangle* d_triangles,
     while (cap < 2u * n) cap <<= 1;
     const uint32_t mask = cap - 1u;
     const uint32_t tilesV = div_up(n, TILE), tilesF = div_up(T, TILE);
-    if (cap > w.capTable) { w.capTable = 0; BF_TRY(regrow((void**)&w.d_table, 4 * (size_t)cap)); w.capTable = cap; }
+    if (cap > w.capTable) { w.capTable = 0; BF_TRY(res.regrow(&w.d_table, cap)); w.capTable = cap; }
     if (T > w.capTriangles) {
         w.capTriangles = 0;
-        BF_TRY(regrow((void**)&w.d_rep, 4 * (size_t)n)); BF_TRY(regrow((void**)&w.d_vid, 4 * (size_t)n)); BF_TRY(regrow((void**)&w.d_faceIds, 4 * (size_t)n));
-        BF_TRY(regrow((void**)&w.d_faceRep, 4 * (size_t)T)); BF_TRY(regrow((void**)&w.d_tiles, 4 * (size_t)tilesV));
+        BF_TRY(res.regrow(&w.d_rep, n)); BF_TRY(res.regrow(&w.d_vid, n)); BF_TRY(res.regrow(&w.d_faceIds, n));
+        BF_TRY(res.regrow(&w.d_faceRep, T)); BF_TRY(res.regrow(&w.d_tiles, tilesV));
         w.capTriangles = T;
     }
-    if (!w.d_totals) BF_HIP_TRY(BF_MALLOC((void**)&w.d_totals, 8));
+    if (!w.d_totals) BF_TRY(res.device(&w.d_totals, 2));
     const float* tris = (const float*)d_triangles;
     m44 xf; memset(&xf, 0, sizeof xf);
     if (transform) memcpy(xf.e, transform, 64);
@@ -255,7 +243,7 @@ int meshweld_run(MeshWeld& w, hipStream_t st, const bf_mc_triangle* d_triangles,
     BF_REQUIRE(nv >= 1 && nv <= n, "vertex count out of range");
     if (nv > w.capVertices) {
         w.capVertices = 0;
-        BF_TRY(regrow((void**)&w.d_positions, 12 * (size_t)nv)); BF_TRY(regrow((void**)&w.d_colors, 12 * (size_t)nv));
+        BF_TRY(res.regrow(&w.d_positions, 3 * (size_t)nv)); BF_TRY(res.regrow(&w.d_colors, 3 * (size_t)nv));
         w.capVertices = nv;
     }
     hipLaunchKernelGGL(k_weld_tile_scatter<true>, dim3(std::min(tilesV, MAX_GRID)), dim3(WG), 0, st, (const uint32_t*)w.d_rep, n, tilesV, (const uint32_t*)w.d_tiles, nv, tris, xf, hasXf,
@@ -273,7 +261,7 @@ int meshweld_run(MeshWeld& w, hipStream_t st, const bf_mc_triangle* d_triangles,
     BF_HIP_TRY(hipMemcpyAsync(&nf, w.d_totals + 1, 4, hipMemcpyDeviceToHost, st));
     BF_HIP_TRY(hipStreamSynchronize(st));
     BF_REQUIRE(nf <= T, "face count out of range");
-    if (nf > w.capFaces) { w.capFaces = 0; BF_TRY(regrow((void**)&w.d_faces, 12 * (size_t)nf)); w.capFaces = nf; }
+    if (nf > w.capFaces) { w.capFaces = 0; BF_TRY(res.regrow(&w.d_faces, 3 * (size_t)nf)); w.capFaces = nf; }
     if (nf) {
         hipLaunchKernelGGL(k_weld_tile_scatter<false>, dim3(std::min(tilesF, MAX_GRID)), dim3(WG), 0, st, (const uint32_t*)w.d_faceRep, T, tilesF, (const uint32_t*)w.d_tiles, nf,
                            (const float*)nullptr, xf, 0, (uint32_t*)nullptr, (float*)nullptr, (float*)nullptr, (const uint32_t*)w.d_faceIds, w.d_faces);

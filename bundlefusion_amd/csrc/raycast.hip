@@ -24,7 +24,7 @@
 #include <cstring>
 
 #include "bf_device.h"
-#include "bf_internal.h"
+#include "bf_resources.h"
 #include "bf_volume.h"
 
 using namespace bf;
@@ -282,6 +282,7 @@ struct bf_ray_cast {
     uint32_t capacity = 0;          // pixels allocated
     float *d_depth = nullptr, *d_depth4 = nullptr, *d_normals = nullptr, *d_colors = nullptr, *d_rayMin = nullptr, *d_rayMax = nullptr;
     uint32_t *d_minKey = nullptr, *d_maxKey = nullptr;
+    bf::Resources res;
 };
 
 extern "C" {
@@ -290,22 +291,18 @@ int bf_ray_cast_create(const bf_ray_cast_params* p, bf_ray_cast** out) {        
     BF_REQUIRE(p && out, "null argument");
     BF_REQUIRE(p->m_width > 0 && p->m_height > 0, "empty ray cast image");
     bf_ray_cast* rc = new bf_ray_cast;
+    bf::CreateGuard<bf_ray_cast> guard(rc, bf_ray_cast_destroy);
     rc->params = *p;
     const size_t n = (size_t)p->m_width * p->m_height;
     rc->capacity = (uint32_t)n;
-    hipError_t e = hipSuccess;
-    auto A = [&](void** ptr, size_t bytes) { if (e == hipSuccess) e = BF_MALLOC(ptr, bytes); };
-    A((void**)&rc->d_depth, n * 4); A((void**)&rc->d_depth4, n * 16); A((void**)&rc->d_normals, n * 16); A((void**)&rc->d_colors, n * 16);
-    A((void**)&rc->d_rayMin, n * 4); A((void**)&rc->d_rayMax, n * 4); A((void**)&rc->d_minKey, n * 4); A((void**)&rc->d_maxKey, n * 4);
-    if (e != hipSuccess) { bf_ray_cast_destroy(rc); set_error("hipMalloc failed: %s", hipGetErrorString(e)); return BF_ERR_HIP; }
-    *out = rc;
+    BF_TRY(rc->res.device(&rc->d_depth, n)); BF_TRY(rc->res.device(&rc->d_depth4, n * 4)); BF_TRY(rc->res.device(&rc->d_normals, n * 4)); BF_TRY(rc->res.device(&rc->d_colors, n * 4));
+    BF_TRY(rc->res.device(&rc->d_rayMin, n)); BF_TRY(rc->res.device(&rc->d_rayMax, n)); BF_TRY(rc->res.device(&rc->d_minKey, n)); BF_TRY(rc->res.device(&rc->d_maxKey, n));
+    *out = guard.dismiss();
     return BF_OK;
 }
 
 int bf_ray_cast_destroy(bf_ray_cast* rc) {
     if (!rc) return BF_OK;
-    (void)hipFree(rc->d_depth); (void)hipFree(rc->d_depth4); (void)hipFree(rc->d_normals); (void)hipFree(rc->d_colors);
-    (void)hipFree(rc->d_rayMin); (void)hipFree(rc->d_rayMax); (void)hipFree(rc->d_minKey); (void)hipFree(rc->d_maxKey);
     delete rc;
     return BF_OK;
 }

@@ -15,7 +15,7 @@
 #include "../../include/bf_detmath.h"
 #include "../../include/bf_render.h"
 #include "bf_device.h"
-#include "bf_internal.h"
+#include "bf_resources.h"
 
 using namespace bf;
 
@@ -24,6 +24,7 @@ struct bf_frame_renderer {
     float4* d_target = nullptr;
     uint32_t* d_rgba = nullptr;
     hipStream_t stream = nullptr;
+    bf::Resources res;
 };
 
 namespace {
@@ -193,21 +194,18 @@ int bf_ray_cast_intrinsics_inv(const bf_ray_cast_params* p, float out[16]) {
 int bf_frame_renderer_create(uint32_t width, uint32_t height, bf_frame_renderer** out) {
     BF_REQUIRE(out && width > 0 && height > 0 && width < 32768 && height < 32768, "bad image size");
     bf_frame_renderer* r = new bf_frame_renderer;
+    bf::CreateGuard<bf_frame_renderer> guard(r, bf_frame_renderer_destroy);
     r->width = width; r->height = height;
     const size_t n = (size_t)width * height;
-    if (BF_MALLOC((void**)&r->d_target, n * 16) != hipSuccess || BF_MALLOC((void**)&r->d_rgba, n * 4) != hipSuccess) {
-        (void)hipFree(r->d_target); delete r;
-        set_error("bf_frame_renderer_create: out of device memory");
-        return BF_ERR_HIP;
-    }
-    *out = r;
+    BF_TRY(r->res.device(&r->d_target, n));
+    BF_TRY(r->res.device(&r->d_rgba, n));
+    *out = guard.dismiss();
     return BF_OK;
 }
 
 int bf_frame_renderer_destroy(bf_frame_renderer* r) {
     if (!r) return BF_OK;
     (void)hipStreamSynchronize(r->stream);
-    (void)hipFree(r->d_target); (void)hipFree(r->d_rgba);
     delete r;
     return BF_OK;
 }

@@ -22,7 +22,7 @@
 
 #include "../../include/bf_record.h"
 #include "../../include/bf_sensordata.h"
-#include "bf_internal.h"
+#include "bf_resources.h"
 
 using namespace bf;
 
@@ -591,6 +591,7 @@ struct bf_sens_player {
     std::vector<Slot> slots;
     size_t colourCapacity = 0;
     bool pinned = false;
+    bf::Resources res;                        // the slots' buffers when pinned (malloc otherwise)
     std::mutex m;
     std::condition_variable cvWork, cvReady;
     uint64_t nextClaim = 0, nextOut = 0, numFrames = 0;
@@ -689,10 +690,7 @@ int bf_sens_player_destroy(bf_sens_player* pl) {
     }
     pl->cvWork.notify_all();
     for (std::thread& t : pl->threads) t.join();
-    for (bf_sens_player::Slot& s : pl->slots) {
-        if (pl->pinned) { (void)hipHostFree(s.depth); (void)hipHostFree(s.colour); }
-        else { free(s.depth); free(s.colour); }
-    }
+    if (!pl->pinned) for (bf_sens_player::Slot& s : pl->slots) { free(s.depth); free(s.colour); }
     delete pl;
     return BF_OK;
 }
@@ -705,6 +703,7 @@ int bf_sens_player_create(bf_pipeline* pipeline, bf_sensor_data* sd, uint32_t nu
     const bf_sensor_data_info& h = sd->info;
     BF_REQUIRE(h.depthWidth > 0 && h.depthHeight > 0 && h.colorWidth > 0 && h.colorHeight > 0, "the file has no depth or no colour images");
     bf_sens_player* pl = new bf_sens_player;
+    bf::CreateGuard<bf_sens_player> guard(pl, bf_sens_player_destroy);
     pl->pipe = pipeline; pl->sd = sd; pl->numFrames = sd->frames.size(); pl->pinned = pipeline != nullptr;
     // the coefficients of any layout the device takes: three components at no more than full resolution, padded to whole 16 x 16 MCUs, 2 bytes each
     const size_t padW = ((size_t)h.colorWidth + 15) / 16 * 16, padH = ((size_t)h.colorHeight + 15) / 16 * 16;
@@ -713,18 +712,15 @@ int bf_sens_player_create(bf_pipeline* pipeline, bf_sensor_data* sd, uint32_t nu
     pl->slots.resize(numThreads + 2);
     for (bf_sens_player::Slot& s : pl->slots) {
         if (pl->pinned) {
-            if (hipHostMalloc((void**)&s.depth, depthBytes) != hipSuccess || hipHostMalloc((void**)&s.colour, pl->colourCapacity) != hipSuccess) {
-                set_error("bf_sens_player_create: no pinned host memory (%s)", hipGetErrorString(hipGetLastError()));
-                bf_sens_player_destroy(pl);
-                return BF_ERR_HIP;
-            }
+            BF_TRY(pl->res.pinned(&s.depth, depthBytes));
+            BF_TRY(pl->res.pinned(&s.colour, pl->colourCapacity));
         } else {
             s.depth = (uint16_t*)malloc(depthBytes); s.colour = (uint8_t*)malloc(pl->colourCapacity);
-            if (!s.depth || !s.colour) { bf_sens_player_destroy(pl); throw std::bad_alloc(); }
+            if (!s.depth || !s.colour) throw std::bad_alloc();
         }
     }
     for (uint32_t t = 0; t < numThreads; ++t) pl->threads.emplace_back(playerWorker, pl);
-    *out = pl;
+    *out = guard.dismiss();
     return BF_OK;
     });
 }
@@ -780,6 +776,7 @@ struct bf_sens_recorder {
     };
     std::vector<Slot> slots;
     hipStream_t copyStream = nullptr;
+    bf::Resources res;                                    // copyStream and the slots' buffers and events when pinned (malloc otherwise)
     std::mutex m;
     std::condition_variable cvWork, cvFree;
     uint64_t nextRecord = 0, nextClaim = 0, nextAppend = 0;          // frames handed in / claimed by a worker / appended (or given up after an error)
@@ -895,12 +892,6 @@ int bf_sens_recorder_destroy(bf_sens_recorder* r) {
     std::remove(r->tmp.c_str());
     if (r->pinned) {
         if (r->copyStream) (void)hipStreamSynchronize(r->copyStream);
-        for (bf_sens_recorder::Slot& s : r->slots) {
-            (void)hipHostFree(s.coef); (void)hipHostFree(s.depth); (void)hipFree(s.d_coef); (void)hipFree(s.d_depth);
-            if (s.packed) (void)hipEventDestroy(s.packed);
-            if (s.copied) (void)hipEventDestroy(s.copied);
-        }
-        if (r->copyStream) (void)hipStreamDestroy(r->copyStream);
     } else {
         for (bf_sens_recorder::Slot& s : r->slots) { free(s.coef); free(s.depth); }
     }
@@ -927,29 +918,30 @@ int bf_sens_recorder_create(bf_pipeline* pipeline, const bf_sensor_data_info* in
         fclose(f);
     }
     bf_sens_recorder* r = new bf_sens_recorder;
+    bf::CreateGuard<bf_sens_recorder> guard(r, bf_sens_recorder_destroy);
     r->info = *info; r->info.numFrames = 0; r->info.numIMUFrames = 0; r->tmp = tmpFilename; r->pinned = pipeline != nullptr;
     r->coefCount = (size_t)((info->colorWidth + 7) / 8) * ((info->colorHeight + 7) / 8) * 192;
     r->depthCount = (size_t)info->depthWidth * info->depthHeight;
     r->slots.resize(numSlots);
     if (r->pinned) {
-        bool ok = hipGetDevice(&r->device) == hipSuccess && hipStreamCreateWithFlags(&r->copyStream, hipStreamNonBlocking) == hipSuccess;
-        for (bf_sens_recorder::Slot& s : r->slots)
-            ok = ok && hipHostMalloc((void**)&s.coef, r->coefCount * 2) == hipSuccess && hipHostMalloc((void**)&s.depth, r->depthCount * 2) == hipSuccess &&
-                 BF_MALLOC(&s.d_coef, r->coefCount * 2) == hipSuccess && BF_MALLOC(&s.d_depth, r->depthCount * 2) == hipSuccess &&
-                 hipEventCreateWithFlags(&s.packed, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&s.copied, hipEventDisableTiming) == hipSuccess;
-        if (!ok) {
-            set_error("bf_sens_recorder_create: no pinned host or device memory (%s)", hipGetErrorString(hipGetLastError()));
-            bf_sens_recorder_destroy(r);
-            return BF_ERR_HIP;
+        BF_HIP_TRY(hipGetDevice(&r->device));
+        hipStream_t copy = nullptr;
+        BF_HIP_TRY(hipStreamCreateWithFlags(&copy, hipStreamNonBlocking));
+        BF_TRY(r->res.adopt(copy));
+        r->copyStream = copy;
+        for (bf_sens_recorder::Slot& s : r->slots) {
+            BF_TRY(r->res.pinned(&s.coef, r->coefCount * 2)); BF_TRY(r->res.pinned(&s.depth, r->depthCount * 2));
+            BF_TRY(r->res.device(&s.d_coef, r->coefCount)); BF_TRY(r->res.device(&s.d_depth, r->depthCount));
+            BF_TRY(r->res.event(&s.packed, hipEventDisableTiming)); BF_TRY(r->res.event(&s.copied, hipEventDisableTiming));
         }
     } else {
         for (bf_sens_recorder::Slot& s : r->slots) {
             s.coef = (int16_t*)malloc(r->coefCount * 2); s.depth = (uint16_t*)malloc(r->depthCount * 2);
-            if (!s.coef || !s.depth) { bf_sens_recorder_destroy(r); throw std::bad_alloc(); }
+            if (!s.coef || !s.depth) throw std::bad_alloc();
         }
     }
     for (uint32_t t = 0; t < numThreads; ++t) r->threads.emplace_back(recWorker, r);
-    *out = r;
+    *out = guard.dismiss();
     return BF_OK;
     });
 }

@@ -19,7 +19,7 @@
 
 #include "../../include/bf_detmath.h"
 #include "bf_device.h"
-#include "bf_internal.h"
+#include "bf_resources.h"
 
 using namespace bf;
 
@@ -519,7 +519,7 @@ struct bf_sift {
     float* mag[NUM_OCT][3]; float* ang[NUM_OCT][3];
     SiftDev d{};
     int* d_count = nullptr;
-    std::vector<void*> allocations;
+    bf::Resources res;
 };
 
 extern "C" {
@@ -542,6 +542,7 @@ int bf_sift_create(uint32_t width, uint32_t height, uint32_t depthWidth, uint32_
     }
     BF_REQUIRE(sumFmax <= MAXRAW, "SIFT image too large: the per-level key caps sum to more than the 6144 raw keys the detector holds (640x480 is the largest supported size)");
     bf_sift* s = new bf_sift();
+    bf::CreateGuard<bf_sift> guard(s, bf_sift_destroy);
     s->W = (int)width; s->H = (int)height; s->depthW = (int)depthWidth; s->depthH = (int)depthHeight;
     s->depthMin = depthMin; s->depthMax = depthMax; s->minKeyScale = minKeyScale;
     s->featureCountThreshold = (int)featureCountThreshold; s->maxFeatures = (int)maxNumKeysPerImage;
@@ -556,15 +557,13 @@ int bf_sift_create(uint32_t width, uint32_t height, uint32_t depthWidth, uint32_
     memset(&s->taps, 0, sizeof s->taps);
     makeTapsHost(initSigma, s->taps.fw[0], s->taps.k[0]);
     for (int i = 0; i < 5; ++i) makeTapsHost(dsigma0 * powf(sigmak, (float)i), s->taps.fw[i + 1], s->taps.k[i + 1]);
-    auto A = [&](void** p, size_t bytes) { if (BF_MALLOC(p, bytes) != hipSuccess) return false; s->allocations.push_back(*p); return true; };
-    bool ok = true;
+    bf::Resources& R = s->res;
     uint32_t candTotal = 0;
     for (int o = 0; o < NUM_OCT; ++o) {
         const int w = s->W >> o, h = s->H >> o;
-        for (int a = 0; a < NLEV; ++a) ok = ok && A((void**)&s->gauss[o][a], (size_t)w * h * 4);
-        for (int a = 0; a < 3; ++a) ok = ok && A((void**)&s->mag[o][a], (size_t)w * h * 4) && A((void**)&s->ang[o][a], (size_t)w * h * 4);
+        for (int a = 0; a < NLEV; ++a) BF_TRY(R.device(&s->gauss[o][a], (size_t)w * h));
+        for (int a = 0; a < 3; ++a) { BF_TRY(R.device(&s->mag[o][a], (size_t)w * h)); BF_TRY(R.device(&s->ang[o][a], (size_t)w * h)); }
     }
-    if (!ok) { set_error("bf_sift_create: hipMalloc failed"); bf_sift_destroy(s); return BF_ERR_HIP; }
     int gb = 0, db = 0;
     for (int o = 0; o < NUM_OCT; ++o) {
         const int w = s->W >> o, h = s->H >> o;
@@ -592,10 +591,9 @@ int bf_sift_create(uint32_t width, uint32_t height, uint32_t depthWidth, uint32_
     s->detect.depthMin = depthMin; s->detect.depthMax = depthMax;
     s->detect.dogThreshold = 0.02f / DOG_LEVELS;
     s->detect.edgeT = (10.0f + 1) * (10.0f + 1) / 10.0f;
-    ok = A((void**)&s->d.cand, (size_t)candTotal * 4) && A((void**)&s->d.candCount, NKL * 4) && A((void**)&s->d.raw, MAXRAW * sizeof(RawKey)) &&
-         A((void**)&s->d.counts, CNT_TOTAL * 4) && A((void**)&s->d.feats, (size_t)(maxNumKeysPerImage + 8) * sizeof(Feat)) &&
-         A((void**)&s->d.des, (size_t)(maxNumKeysPerImage + 8) * 128 * 4) && A((void**)&s->d_count, 4) && A((void**)&s->d.ticket, 4);
-    if (!ok) { set_error("bf_sift_create: hipMalloc failed"); bf_sift_destroy(s); return BF_ERR_HIP; }
+    BF_TRY(R.device((void**)&s->d.cand, (size_t)candTotal * 4)); BF_TRY(R.device((void**)&s->d.candCount, NKL * 4)); BF_TRY(R.device((void**)&s->d.raw, MAXRAW * sizeof(RawKey)));
+    BF_TRY(R.device((void**)&s->d.counts, CNT_TOTAL * 4)); BF_TRY(R.device((void**)&s->d.feats, (size_t)(maxNumKeysPerImage + 8) * sizeof(Feat)));
+    BF_TRY(R.device((void**)&s->d.des, (size_t)(maxNumKeysPerImage + 8) * 128 * 4)); BF_TRY(R.device((void**)&s->d_count, 4)); BF_TRY(R.device((void**)&s->d.ticket, 4));
     (void)hipMemset(s->d.ticket, 0, 4);
     (void)hipMemset(s->d.candCount, 0, NKL * 4);
     (void)hipMemset(s->d.counts, 0, CNT_TOTAL * 4);
@@ -628,14 +626,13 @@ int bf_sift_create(uint32_t width, uint32_t height, uint32_t depthWidth, uint32_
             }
         if (bj.n) s->schedule.push_back(bj);
     }
-    *out = s;
+    *out = guard.dismiss();
     return BF_OK;
 }
 
 int bf_sift_destroy(bf_sift* s) {
     if (!s) return BF_OK;
     (void)hipStreamSynchronize(s->stream);
-    for (void* p : s->allocations) (void)hipFree(p);
     delete s;
     return BF_OK;
 }

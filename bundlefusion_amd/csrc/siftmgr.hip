@@ -24,7 +24,7 @@
 
 #include "../../include/bf_detmath.h"
 #include "bf_device.h"
-#include "bf_internal.h"
+#include "bf_resources.h"
 
 using namespace bf;
 
@@ -959,9 +959,6 @@ __global__ void k_reset_valid(int* valid, uint32_t n, int* globNum) {
     if (i == 0) *globNum = 0;
 }
 
-template <class T>
-int dalloc(T*& p, size_t n) { BF_HIP_TRY(BF_MALLOC((void**)&p, std::max<size_t>(n, 1) * sizeof(T))); return BF_OK; }
-
 m44 toM44(const float* p) { m44 m; memcpy(m.e, p, 64); return m; }
 
 }  // namespace
@@ -1164,6 +1161,7 @@ struct bf_siftmgr {
     std::deque<uint32_t> retry;
     // scratch of the device-side fuseToGlobal (allocated at first use)
     void* fuseScratch = nullptr; size_t fuseScratchBytes = 0; int* d_fuseError = nullptr;
+    bf::Resources res;
 };
 
 static void selectPairSet(bf_siftmgr* m, int k) {
@@ -1198,50 +1196,39 @@ int bf_siftmgr_commit_pairs(bf_siftmgr* m, uint32_t curFrame, uint32_t startFram
 int bf_siftmgr_create(uint32_t maxImages, uint32_t maxKeyPointsPerImage, bf_siftmgr** out) {
     BF_REQUIRE(out && maxImages >= 1 && maxKeyPointsPerImage >= 16 && maxKeyPointsPerImage <= 1024, "maxKeyPointsPerImage must be in [16, 1024]");
     bf_siftmgr* m = new bf_siftmgr;
+    bf::CreateGuard<bf_siftmgr> guard(m, bf_siftmgr_destroy);
     m->maxImages = maxImages; m->maxKeys = maxKeyPointsPerImage;
     m->maxResiduals = MAX_FILT * (maxImages * (maxImages - 1)) / 2;
-    int rc;
-    const size_t nk = (size_t)maxImages * maxKeyPointsPerImage;
-    rc = BF_OK;
-    for (int k = 0; k < 2 && !rc; ++k) {
+    const size_t nk = (size_t)maxImages * maxKeyPointsPerImage, nRaw = (size_t)maxImages * MAX_RAW, nFilt = (size_t)maxImages * MAX_FILT, nRow = (size_t)maxImages * 1024;
+    const size_t nRes = std::max<size_t>(m->maxResiduals, 1);          // one image: no pairs, the buffers exist all the same
+    bf::Resources& R = m->res;
+    for (int k = 0; k < 2; ++k) {
         bf_siftmgr::PairSet& P = m->sets[k];
-        (rc = dalloc(P.numMatches, maxImages)) || (rc = dalloc(P.dist, (size_t)maxImages * MAX_RAW)) || (rc = dalloc(P.idx, (size_t)maxImages * MAX_RAW)) ||
-        (rc = dalloc(P.numFilt, maxImages)) || (rc = dalloc(P.fdist, (size_t)maxImages * MAX_FILT)) || (rc = dalloc(P.fidx, (size_t)maxImages * MAX_FILT)) ||
-        (rc = dalloc(P.T, maxImages)) || (rc = dalloc(P.Tinv, maxImages)) ||
-        (rc = dalloc(P.ms.rowRes, (size_t)maxImages * 1024)) || (rc = dalloc(P.ms.rowDist, (size_t)maxImages * 1024)) || (rc = dalloc(P.ms.colRes, (size_t)maxImages * 1024)) ||
-        (rc = dalloc(P.ms.ticket, maxImages));
-        if (!rc) { BF_HIP_TRY(hipMemset(P.numMatches, 0, sizeof(int) * maxImages)); BF_HIP_TRY(hipMemset(P.numFilt, 0, sizeof(int) * maxImages)); BF_HIP_TRY(hipMemset(P.ms.ticket, 0, sizeof(uint32_t) * maxImages)); }
+        BF_TRY(R.device(&P.numMatches, maxImages)); BF_TRY(R.device(&P.dist, nRaw)); BF_TRY(R.device(&P.idx, nRaw));
+        BF_TRY(R.device(&P.numFilt, maxImages)); BF_TRY(R.device(&P.fdist, nFilt)); BF_TRY(R.device(&P.fidx, nFilt));
+        BF_TRY(R.device(&P.T, maxImages)); BF_TRY(R.device(&P.Tinv, maxImages));
+        BF_TRY(R.device(&P.ms.rowRes, nRow)); BF_TRY(R.device(&P.ms.rowDist, nRow)); BF_TRY(R.device(&P.ms.colRes, nRow));
+        BF_TRY(R.device(&P.ms.ticket, maxImages));
+        BF_HIP_TRY(hipMemset(P.numMatches, 0, sizeof(int) * maxImages)); BF_HIP_TRY(hipMemset(P.numFilt, 0, sizeof(int) * maxImages)); BF_HIP_TRY(hipMemset(P.ms.ticket, 0, sizeof(uint32_t) * maxImages));
     }
-    if (rc) { delete m; return rc; }
     selectPairSet(m, 0);
-    if ((rc = dalloc(m->d_keys, nk)) || (rc = dalloc(m->d_descs, nk * 128)) || (rc = dalloc(m->d_numKeys, maxImages)) ||
-        (rc = dalloc(m->d_validImages, maxImages)) || (rc = dalloc(m->d_validOpt, 1)) ||
-        (rc = dalloc(m->d_glob, m->maxResiduals)) || (rc = dalloc(m->d_globKeys, m->maxResiduals)) || (rc = dalloc(m->d_globNum, 1)) || (rc = dalloc(m->d_res, 1))) {
-        delete m; return rc;
-    }
-    BF_HIP_TRY(hipHostMalloc((void**)&m->h_res, sizeof(FrameResult) * bf_siftmgr::RES_SLOTS));
-    for (auto& e : m->evRes) BF_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    BF_TRY(R.device(&m->d_keys, nk)); BF_TRY(R.device(&m->d_descs, nk * 128)); BF_TRY(R.device(&m->d_numKeys, maxImages));
+    BF_TRY(R.device(&m->d_validImages, maxImages)); BF_TRY(R.device(&m->d_validOpt, 1));
+    BF_TRY(R.device(&m->d_glob, nRes)); BF_TRY(R.device(&m->d_globKeys, nRes)); BF_TRY(R.device(&m->d_globNum, 1)); BF_TRY(R.device(&m->d_res, 1));
+    BF_TRY(R.pinned(&m->h_res, sizeof(FrameResult) * bf_siftmgr::RES_SLOTS));
+    for (auto& e : m->evRes) BF_TRY(R.event(&e, hipEventDisableTiming));
     BF_HIP_TRY(hipMemset(m->d_numKeys, 0, sizeof(int) * maxImages));
     BF_HIP_TRY(hipMemset(m->d_globNum, 0, sizeof(int)));
     BF_HIP_TRY(hipMemset(m->d_res, 0, sizeof(FrameResult)));
     m->validImages.assign(maxImages, 0);
     m->validImages[0] = 1;
     BF_HIP_TRY(hipMemcpy(m->d_validImages, m->validImages.data(), sizeof(int) * maxImages, hipMemcpyHostToDevice));
-    *out = m;
+    *out = guard.dismiss();
     return BF_OK;
 }
 
 int bf_siftmgr_destroy(bf_siftmgr* m) {
     if (!m) return BF_OK;
-    hipFree(m->d_keys); hipFree(m->d_descs); hipFree(m->d_numKeys);
-    for (auto& P : m->sets) { hipFree(P.numMatches); hipFree(P.dist); hipFree(P.idx); hipFree(P.numFilt); hipFree(P.fdist); hipFree(P.fidx); hipFree(P.T); hipFree(P.Tinv);
-                              hipFree(P.ms.rowRes); hipFree(P.ms.rowDist); hipFree(P.ms.colRes); hipFree(P.ms.ticket); }
-    hipFree(m->d_validImages); hipFree(m->d_validOpt);
-    hipFree(m->d_glob); hipFree(m->d_globKeys); hipFree(m->d_globNum); hipFree(m->d_res);
-    if (m->fuseScratch) hipFree(m->fuseScratch);
-    if (m->d_fuseError) hipFree(m->d_fuseError);
-    if (m->h_res) hipHostFree(m->h_res);
-    for (auto& e : m->evRes) if (e) (void)hipEventDestroy(e);
     delete m;
     return BF_OK;
 }
@@ -1591,13 +1578,12 @@ int bf_siftmgr_fuse_to_global(bf_siftmgr* local, bf_siftmgr* global, const float
     // scratch: 8 arrays of N words + N key points + 2R edges
     const size_t need = N * 4 * 9 + N * sizeof(Key) + (size_t)2 * local->maxResiduals * sizeof(FuseAdj) + 256;
     if (local->fuseScratchBytes < need) {
-        if (local->fuseScratch) BF_HIP_TRY(hipFree(local->fuseScratch));
-        local->fuseScratch = nullptr; local->fuseScratchBytes = 0;
+        local->fuseScratchBytes = 0;
         const size_t cap = (size_t)local->maxImages * mk * 4 * 9 + (size_t)local->maxImages * mk * sizeof(Key) + (size_t)2 * local->maxResiduals * sizeof(FuseAdj) + 256;
-        BF_HIP_TRY(BF_MALLOC(&local->fuseScratch, cap));
+        BF_TRY(local->res.regrow(&local->fuseScratch, cap));
         local->fuseScratchBytes = cap;
     }
-    if (!local->d_fuseError) { BF_HIP_TRY(BF_MALLOC((void**)&local->d_fuseError, sizeof(int))); BF_HIP_TRY(hipMemset(local->d_fuseError, 0, sizeof(int))); }
+    if (!local->d_fuseError) { BF_TRY(local->res.device(&local->d_fuseError, 1)); BF_HIP_TRY(hipMemset(local->d_fuseError, 0, sizeof(int))); }
     bf_sift_image_gpu img;
     { const int rc = bf_siftmgr_create_image(global, &img); if (rc != BF_OK) return rc; }
     FuseArgs a;

@@ -22,7 +22,7 @@
 #include <vector>
 
 #include "bf_device.h"
-#include "bf_internal.h"
+#include "bf_resources.h"
 #include "bf_se3.h"
 
 using namespace bf;
@@ -1042,7 +1042,7 @@ struct bf_solver {
     uint32_t maxImages, maxResiduals, maxCorrPerImage;
     Dev d{};
     hipStream_t stream = nullptr;
-    std::vector<void*> allocations;
+    bf::Resources res;
     std::vector<float> convergence;
     float hMaxRes = 0.0f; int hMaxIdx = 0; int hBarrierFail = 0;
     bool pcgWide = true;                 // (BF_PCG_WIDE=0: the 256-thread kernel for every problem, for the A/B)
@@ -1055,23 +1055,13 @@ struct bf_solver {
     bool lastUsedDense = false;
 };
 
-namespace {
-template <class T>
-bool sAlloc(bf_solver* s, T** p, size_t n) {
-    void* q = nullptr;
-    if (BF_MALLOC(&q, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) return false;
-    s->allocations.push_back(q);
-    *p = (T*)q;
-    return true;
-}
-}  // namespace
-
 extern "C" {
 
 int bf_solver_create(uint32_t maxNumberOfImages, uint32_t maxNumResiduals, const bf_solver_config* cfg, bf_solver** out) {
     BF_REQUIRE(cfg && out, "null argument");
     BF_REQUIRE(maxNumberOfImages >= 2 && maxNumResiduals > 0, "bad capacity");
     bf_solver* s = new bf_solver();
+    bf::CreateGuard<bf_solver> guard(s, bf_solver_destroy);
     s->cfg = *cfg;
     s->maxImages = maxNumberOfImages; s->maxResiduals = maxNumResiduals;
     BF_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pcg<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)PCG_LDS_MAX));
@@ -1094,26 +1084,26 @@ int bf_solver_create(uint32_t maxNumberOfImages, uint32_t maxNumResiduals, const
     d.maxSlots = (uint32_t)std::min<size_t>(M, 2 * C + (N <= 64 ? M : 4 * N));
     d.maxPairs = (uint32_t)(N * (N - 1) / 2);
     if (N > 64) d.maxPairs = (uint32_t)std::min<size_t>(d.maxPairs, d.maxSlots);
-    bool ok = sAlloc(s, &d.T, N) && sAlloc(s, &d.Tinv, N) && sAlloc(s, &d.keyCount, M) && sAlloc(s, &d.keyStart, M) && sAlloc(s, &d.cursor, M) &&
-              sAlloc(s, &d.slotOfKey, M) && sAlloc(s, &d.denseRaw, M) && sAlloc(s, &d.keyPair, M) && sAlloc(s, &d.rowStart, N + 1) &&
-              sAlloc(s, &d.slotCol, (size_t)d.maxSlots) && sAlloc(s, &d.slotKey, (size_t)d.maxSlots) && sAlloc(s, &d.corrList, 2 * C) &&
-              sAlloc(s, &d.slotD, (size_t)d.maxSlots * 36) && sAlloc(s, &d.slotO, (size_t)d.maxSlots * 36) && sAlloc(s, &d.slotG, (size_t)d.maxSlots * 6) &&
-              sAlloc(s, &d.slotP, (size_t)d.maxSlots * 4) && sAlloc(s, &d.diagA, N * 36) && sAlloc(s, &d.rhs, N * 6) && sAlloc(s, &d.prec, N * 6) &&
-              sAlloc(s, &d.delta, N * 6) && sAlloc(s, &d.r, N * 6) && sAlloc(s, &d.p, N * 6) && sAlloc(s, &d.Ap, N * 6) &&
-              sAlloc(s, &d.densePairs, (size_t)d.maxPairs) && sAlloc(s, &d.denseWeight, (size_t)d.maxPairs) &&
-              sAlloc(s, &d.denseBlocks, (size_t)d.maxPairs * DENSE_BLK) && sAlloc(s, &d.flags, FL_COUNT) && sAlloc(s, &d.gridBar, 32) && sAlloc(s, &d.energies, 40) &&
-              sAlloc(s, &d.maxRes, 1) && sAlloc(s, &d.maxIdx, 1) && sAlloc(s, &d.highCount, 1) && sAlloc(s, &d.numEntriesPerRow, N) &&
-              sAlloc(s, &d.scanRow, 3 * (N + 1)) && sAlloc(s, &d.coopVec, s->coopVecFloats = ((31 * N + 4096 <= PCG_LDS_MAX / 4 && !s->forceVecGlobal) ? (size_t)4 : (size_t)s->maxCoopGroups * ((31 * N + 1 + 3) & ~(size_t)3))) && sAlloc(s, &d.maxResPart, MAXRES_GROUPS) && sAlloc(s, &d.maxIdxPart, MAXRES_GROUPS);
-    if (!ok) { set_error("bf_solver_create: hipMalloc failed"); bf_solver_destroy(s); return BF_ERR_HIP; }
+    s->coopVecFloats = ((31 * N + 4096 <= PCG_LDS_MAX / 4 && !s->forceVecGlobal) ? (size_t)4 : (size_t)s->maxCoopGroups * ((31 * N + 1 + 3) & ~(size_t)3));
+    bf::Resources& R = s->res;
+    BF_TRY(R.device(&d.T, N)); BF_TRY(R.device(&d.Tinv, N)); BF_TRY(R.device(&d.keyCount, M)); BF_TRY(R.device(&d.keyStart, M)); BF_TRY(R.device(&d.cursor, M));
+    BF_TRY(R.device(&d.slotOfKey, M)); BF_TRY(R.device(&d.denseRaw, M)); BF_TRY(R.device(&d.keyPair, M)); BF_TRY(R.device(&d.rowStart, N + 1));
+    BF_TRY(R.device(&d.slotCol, (size_t)d.maxSlots)); BF_TRY(R.device(&d.slotKey, (size_t)d.maxSlots)); BF_TRY(R.device(&d.corrList, 2 * C));
+    BF_TRY(R.device(&d.slotD, (size_t)d.maxSlots * 36)); BF_TRY(R.device(&d.slotO, (size_t)d.maxSlots * 36)); BF_TRY(R.device(&d.slotG, (size_t)d.maxSlots * 6));
+    BF_TRY(R.device(&d.slotP, (size_t)d.maxSlots * 4)); BF_TRY(R.device(&d.diagA, N * 36)); BF_TRY(R.device(&d.rhs, N * 6)); BF_TRY(R.device(&d.prec, N * 6));
+    BF_TRY(R.device(&d.delta, N * 6)); BF_TRY(R.device(&d.r, N * 6)); BF_TRY(R.device(&d.p, N * 6)); BF_TRY(R.device(&d.Ap, N * 6));
+    BF_TRY(R.device(&d.densePairs, (size_t)d.maxPairs)); BF_TRY(R.device(&d.denseWeight, (size_t)d.maxPairs));
+    BF_TRY(R.device(&d.denseBlocks, (size_t)d.maxPairs * DENSE_BLK)); BF_TRY(R.device(&d.flags, FL_COUNT)); BF_TRY(R.device(&d.gridBar, 32)); BF_TRY(R.device(&d.energies, 40));
+    BF_TRY(R.device(&d.maxRes, 1)); BF_TRY(R.device(&d.maxIdx, 1)); BF_TRY(R.device(&d.highCount, 1)); BF_TRY(R.device(&d.numEntriesPerRow, N));
+    BF_TRY(R.device(&d.scanRow, 3 * (N + 1))); BF_TRY(R.device(&d.coopVec, s->coopVecFloats)); BF_TRY(R.device(&d.maxResPart, MAXRES_GROUPS)); BF_TRY(R.device(&d.maxIdxPart, MAXRES_GROUPS));
     (void)hipMemset(d.flags, 0, FL_COUNT * sizeof(int));
-    *out = s;
+    *out = guard.dismiss();
     return BF_OK;
 }
 
 int bf_solver_destroy(bf_solver* s) {
     if (!s) return BF_OK;
     (void)hipStreamSynchronize(s->stream);
-    for (void* p : s->allocations) (void)hipFree(p);
     delete s;
     return BF_OK;
 }
@@ -1309,8 +1299,9 @@ int bf_solver_debug_dense_system(bf_solver* s, float* hJtJ, float* hJtr, uint32_
     BF_REQUIRE(s && hJtJ && hJtr && numPairs && N == s->lastN, "bad argument");
     const size_t dim = 6 * (size_t)N;
     float *dJ = nullptr, *dr = nullptr;
-    BF_HIP_TRY(BF_MALLOC(&dJ, dim * dim * 4));
-    BF_HIP_TRY(BF_MALLOC(&dr, dim * 4));
+    bf::Resources scratch;          // this call's own, given back at its return
+    BF_TRY(scratch.device(&dJ, dim * dim));
+    BF_TRY(scratch.device(&dr, dim));
     BF_HIP_TRY(hipMemsetAsync(dJ, 0, dim * dim * 4, s->stream));
     BF_HIP_TRY(hipMemsetAsync(dr, 0, dim * 4, s->stream));
     if (s->lastUsedDense) hipLaunchKernelGGL(k_expand_dense, dim3(1), dim3(64), 0, s->stream, s->d, dJ, dr);
@@ -1320,7 +1311,6 @@ int bf_solver_debug_dense_system(bf_solver* s, float* hJtJ, float* hJtr, uint32_
     BF_HIP_TRY(hipMemcpyAsync(flags, s->d.flags, sizeof flags, hipMemcpyDeviceToHost, s->stream));
     BF_HIP_TRY(hipStreamSynchronize(s->stream));
     *numPairs = s->lastUsedDense ? flags[FL_NUM_PAIRS] : 0;
-    (void)hipFree(dJ); (void)hipFree(dr);
     return BF_OK;
 }
 

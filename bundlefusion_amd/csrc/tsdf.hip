@@ -26,7 +26,7 @@
 #include <vector>
 
 #include "bf_device.h"
-#include "bf_internal.h"
+#include "bf_resources.h"
 #include "../../include/bf_comm.h"
 
 using namespace bf;
@@ -1822,22 +1822,12 @@ struct bf_scene {
     bool timing = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
     size_t eventsUsed = 0;
-    std::vector<void*> allocations;
+    bf::Resources res;
 };
 
 #define BF_TRY_RC(expr) do { int _rc = (expr); if (_rc != BF_OK) return _rc; } while (0)
 
 namespace {
-
-template <class T>
-int devAlloc(bf_scene* s, T** p, size_t count) {
-    void* q = nullptr;
-    hipError_t e = BF_MALLOC(&q, count * sizeof(T));
-    if (e != hipSuccess) { set_error("BF_MALLOC(%zu B) failed: %s", count * sizeof(T), hipGetErrorString(e)); return BF_ERR_HIP; }
-    s->allocations.push_back(q);
-    *p = (T*)q;
-    return BF_OK;
-}
 
 Frame makeFrame(const bf_scene* s) {
     Frame f;
@@ -1900,12 +1890,12 @@ ApxPose makeApxPose(const Frame& f) {
 int probeCvt(bf_scene* s) {
     if (s->cvtRne >= 0) return BF_OK;
     uint32_t* d_out = nullptr;
-    BF_HIP_TRY(BF_MALLOC((void**)&d_out, 8 * sizeof(uint32_t)));
+    bf::Resources scratch;          // the probe's own, given back at its return
+    BF_TRY_RC(scratch.device(&d_out, 8));
     hipLaunchKernelGGL(k_probe_cvt, dim3(1), dim3(64), 0, s->stream, d_out);
     uint32_t h[8];
     hipError_t e = hipMemcpyAsync(h, d_out, sizeof h, hipMemcpyDeviceToHost, s->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-    hipFree(d_out);
     if (e != hipSuccess) { set_error("cvt probe failed: %s", hipGetErrorString(e)); return BF_ERR_HIP; }
     uint32_t b[8];
     for (int i = 0; i < 8; ++i) {
@@ -2038,8 +2028,8 @@ int beginTimed(bf_scene* s, uint32_t ops, uint32_t images, std::pair<hipEvent_t,
     if (!s->timing) return BF_OK;
     if (s->eventsUsed == s->events.size()) {
         hipEvent_t e0, e1;
-        BF_HIP_TRY(hipEventCreate(&e0));
-        BF_HIP_TRY(hipEventCreate(&e1));
+        BF_TRY_RC(s->res.event(&e0));
+        BF_TRY_RC(s->res.event(&e1));
         s->events.push_back({e0, e1});
     }
     ev = &s->events[s->eventsUsed++];
@@ -2071,7 +2061,8 @@ int runOperator(bf_scene* s, int kind, const Frame& f, const Frame& fo, const bf
     const size_t npx = (size_t)s->cam.m_imageWidth * s->cam.m_imageHeight;
     if (useTexel && !opTexels && s->texelPixels < npx) {
         BF_TRY_RC(syncAll(s));
-        for (int k = 0; k < bf_scene::NBMAX; ++k) { if (s->texel[k]) (void)hipFree(s->texel[k]); s->texel[k] = nullptr; BF_HIP_TRY(BF_MALLOC((void**)&s->texel[k], npx * sizeof(uint2))); }
+        s->texelPixels = 0;
+        for (int k = 0; k < bf_scene::NBMAX; ++k) BF_TRY_RC(s->res.regrow(&s->texel[k], npx));
         s->texelPixels = npx;
     }
     // The preparation writes the operator's snapshot and list into buffer b (and, fast contract, the frame's texels into texel buffer b): not before the update
@@ -2125,18 +2116,15 @@ int ensureBatch(bf_scene* s) {
     uint32_t ds = 1u << 18;
     while (ds < (1u << 22) && (size_t)ds < 4u * N) ds <<= 1;
     BatchDev& bd = s->bd;
-    int rc = BF_OK;
-#define A(ptr, cnt) if (rc == BF_OK) rc = devAlloc(s, &(ptr), (cnt))
-    A(bd.set, (size_t)ds);
-    A(bd.opMask, (size_t)ds);
-    A(bd.candList, (size_t)ds / 2);
-    A(bd.candCount, 1);
-    A(bd.bins, (size_t)BMAX * NBINS * BINCAP);
-    A(bd.binCount, (size_t)BMAX * NBINS);
-    A(bd.bucketCnt, (size_t)s->params.m_hashNumBuckets);
-    A(bd.flags, 4);
-#undef A
-    if (rc != BF_OK) return rc;
+    bf::Resources& R = s->res;
+    BF_TRY_RC(R.device(&bd.set, ds));
+    BF_TRY_RC(R.device(&bd.opMask, ds));
+    BF_TRY_RC(R.device(&bd.candList, ds / 2));
+    BF_TRY_RC(R.device(&bd.candCount, 1));
+    BF_TRY_RC(R.device(&bd.bins, (size_t)BMAX * NBINS * BINCAP));
+    BF_TRY_RC(R.device(&bd.binCount, (size_t)BMAX * NBINS));
+    BF_TRY_RC(R.device(&bd.bucketCnt, s->params.m_hashNumBuckets));
+    BF_TRY_RC(R.device(&bd.flags, 4));
     bd.setMask = ds - 1; bd.candCap = ds / 2;
     hipLaunchKernelGGL(k_batch_reset, dim3(2048), dim3(256), 0, s->overlap ? s->prep : s->stream, bd, s->params.m_hashNumBuckets);      // (the stream the first march follows on)
     BF_HIP_TRY(hipGetLastError());
@@ -2147,8 +2135,8 @@ int ensureBatch(bf_scene* s) {
 constexpr uint32_t VERIFY_CAP = 1u << 16;
 int verifyBuffers(bf_scene* s) {
     if (s->vlog) return BF_OK;
-    for (int q = 0; q < 2; ++q) BF_HIP_TRY(BF_MALLOC((void**)&s->vshadow[q], (size_t)s->params.m_numSDFBlocks * VOX * sizeof(bf_voxel)));
-    BF_HIP_TRY(hipHostMalloc((void**)&s->vlog, sizeof(VerifyLog) + (size_t)VERIFY_CAP * sizeof(VerifyRec), hipHostMallocCoherent));
+    for (int q = 0; q < 2; ++q) if (!s->vshadow[q]) BF_TRY_RC(s->res.device(&s->vshadow[q], (size_t)s->params.m_numSDFBlocks * VOX));
+    BF_TRY_RC(s->res.pinned(&s->vlog, sizeof(VerifyLog) + (size_t)VERIFY_CAP * sizeof(VerifyRec), hipHostMallocCoherent));
     memset(s->vlog, 0, sizeof(VerifyLog));
     s->vlog->cap = VERIFY_CAP;
     return BF_OK;
@@ -2174,9 +2162,8 @@ int runBatch(bf_scene* s, const bf_scene_batch_op* ops, uint32_t n) {
         s->btexelPixels = 0;                    // (a failed allocation below leaves the sets to be rebuilt by the next call)
         for (int q = 0; q < bf_scene::NBMAX; ++q)
             for (uint32_t k = 0; k < BMAX; ++k) {
-                if (s->btexel[q][k]) (void)hipFree(s->btexel[q][k]);
-                s->btexel[q][k] = nullptr;
-                if (q < s->NB) BF_HIP_TRY(BF_MALLOC((void**)&s->btexel[q][k], npx * sizeof(uint2)));
+                s->res.release(s->btexel[q][k]);
+                if (q < s->NB) BF_TRY_RC(s->res.device(&s->btexel[q][k], npx));
             }
         s->btexelPixels = npx;
     }
@@ -2340,60 +2327,61 @@ int bf_scene_create(const bf_hash_params* p, bf_scene** out) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_error("no HIP device visible"); return BF_ERR_NO_DEVICE; }
     bf_scene* s = new bf_scene();
+    bf::CreateGuard<bf_scene> guard(s, bf_scene_destroy);
     s->params = *p;
     const size_t numEntries = (size_t)p->m_hashNumBuckets * BF_HASH_BUCKET_SIZE;
     const size_t N = p->m_numSDFBlocks;
     uint32_t ds = 1u << 16;
     while (ds < 2u * NBINS * BINCAP && ds < 4u * N) ds <<= 1;
     s->dedupeSize = ds;
-    int rc = BF_OK;
-#define A(ptr, cnt) if (rc == BF_OK) rc = devAlloc(s, &(ptr), (cnt))
-    A(s->d.hash, numEntries);
-    A(s->d.heap, N);
-    A(s->d.heapCounter, 1);
-    A(s->d.vox, N * VOX);
-    for (int b = 0; b < bf_scene::NBMAX; ++b) { A(s->cbuf[b], N); A(s->csrc[b], N); A(s->ccnt[b], 4); }      // ccnt: [0] list length, [1] operator blocks of a union list (entries in the new frustum + entries in the old one)
-    A(s->d.occSum, 3);
-    A(s->d.allocList, N);
-    A(s->d.allocListAlt, N);
-    A(s->d.allocCount, 1);
-    A(s->d.dedupe, (size_t)ds);
-    A(s->d.bins, (size_t)NBINS * BINCAP);
-    A(s->d.binCount, NBINS);
-    A(s->d.overflow, OVCAP);
-    A(s->d.overflowCount, 1);
-    A(s->d.stuckSlots, OVCAP);
-    A(s->d.tileCounts, N / TILE + 4);
-    A(s->d.stats, ST_COUNT);
-    A(s->d_hashDecision, 4);
-#undef A
-    if (rc != BF_OK) { bf_scene_destroy(s); return rc; }
+    bf::Resources& R = s->res;
+    BF_TRY_RC(R.device(&s->d.hash, numEntries));
+    BF_TRY_RC(R.device(&s->d.heap, N));
+    BF_TRY_RC(R.device(&s->d.heapCounter, 1));
+    BF_TRY_RC(R.device(&s->d.vox, N * VOX));
+    for (int b = 0; b < bf_scene::NBMAX; ++b) { BF_TRY_RC(R.device(&s->cbuf[b], N)); BF_TRY_RC(R.device(&s->csrc[b], N)); BF_TRY_RC(R.device(&s->ccnt[b], 4)); }      // ccnt: [0] list length, [1] operator blocks of a union list (entries in the new frustum + entries in the old one)
+    BF_TRY_RC(R.device(&s->d.occSum, 3));
+    BF_TRY_RC(R.device(&s->d.allocList, N));
+    BF_TRY_RC(R.device(&s->d.allocListAlt, N));
+    BF_TRY_RC(R.device(&s->d.allocCount, 1));
+    BF_TRY_RC(R.device(&s->d.dedupe, ds));
+    BF_TRY_RC(R.device(&s->d.bins, (size_t)NBINS * BINCAP));
+    BF_TRY_RC(R.device(&s->d.binCount, NBINS));
+    BF_TRY_RC(R.device(&s->d.overflow, OVCAP));
+    BF_TRY_RC(R.device(&s->d.overflowCount, 1));
+    BF_TRY_RC(R.device(&s->d.stuckSlots, OVCAP));
+    BF_TRY_RC(R.device(&s->d.tileCounts, N / TILE + 4));
+    BF_TRY_RC(R.device(&s->d.stats, ST_COUNT));
+    BF_TRY_RC(R.device(&s->d_hashDecision, 4));
     s->d.dedupeMask = ds - 1;
     useBuf(s, 0);
     {   // allocation / compaction are short and sit on the critical path of the next voxel update: give them queue priority
         int least = 0, greatest = 0;
         BF_HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
-        BF_HIP_TRY(hipStreamCreateWithPriority(&s->prep, hipStreamNonBlocking, greatest));
+        hipStream_t prep = nullptr;
+        BF_HIP_TRY(hipStreamCreateWithPriority(&prep, hipStreamNonBlocking, greatest));
+        BF_TRY_RC(R.adopt(prep));
+        s->prep = prep;
     }
     for (int b = 0; b < bf_scene::NBMAX; ++b)
-        for (hipEvent_t* e : {&s->evPrep[b], &s->evUpd[b]}) BF_HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
+        for (hipEvent_t* e : {&s->evPrep[b], &s->evUpd[b]}) BF_TRY_RC(R.event(e, hipEventDisableTiming));
     for (hipEvent_t* e : {&s->evBarrier, &s->evTmp, &s->evPlace})
-        BF_HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
+        BF_TRY_RC(R.event(e, hipEventDisableTiming));
     s->gridCompact = std::min<uint32_t>(std::max<uint32_t>(div_up((uint32_t)N, TILE), 1u), 2048u);
     s->gridUpdateCol = s->gridUpdateColPlain = 8192;      // see k_update_col
     if (const char* e = getenv("BF_TSDF_EXACT_DIV")) s->forceExactDiv = atoi(e) != 0;
     if (const char* e = getenv("BF_DEBUG_VERIFY_BATCH")) s->verifyPath = e;
     if (const char* e = getenv("BF_DEBUG_UPDATE_LDS")) s->updateLds = (uint32_t)atoi(e);
-    *out = s;
-    int rcReset = bf_scene_reset(s);
-    if (rcReset != BF_OK) return rcReset;
+    BF_TRY_RC(bf_scene_reset(s));
     int arith = BF_TSDF_ARITH_FAST;
     if (const char* e = getenv("BF_TSDF_ARITH")) {
         if (strcasecmp(e, "exact") == 0) arith = BF_TSDF_ARITH_EXACT;
         else if (strcasecmp(e, "fast") == 0) arith = BF_TSDF_ARITH_FAST;
-        else { set_error("BF_TSDF_ARITH must be 'fast' or 'exact' (got '%s')", e); bf_scene_destroy(s); *out = nullptr; return BF_ERR_INVALID_ARG; }
+        else { set_error("BF_TSDF_ARITH must be 'fast' or 'exact' (got '%s')", e); return BF_ERR_INVALID_ARG; }
     }
-    return bf_scene_set_arith(s, arith);
+    BF_TRY_RC(bf_scene_set_arith(s, arith));
+    *out = guard.dismiss();
+    return BF_OK;
 }
 
 // ---- multi-GPU allocation: collect on a band of pixel tiles, exchange, ingest (see Collect above)
@@ -2461,23 +2449,19 @@ int bf_scene_alloc_sync(bf_scene* s) {          // the allocation stream has dra
 int bf_scene_set_alloc_comm(bf_scene* s, bf_comm* comm, uint32_t capacity_keys) {
     BF_REQUIRE(s, "null scene");
     BF_TRY_RC(syncAll(s));
-    if (s->d_allocSend) { (void)hipFree(s->d_allocSend); s->d_allocSend = nullptr; }
-    if (s->d_allocRecv) { (void)hipFree(s->d_allocRecv); s->d_allocRecv = nullptr; }
-    if (s->d_allocSlots) { (void)hipFree(s->d_allocSlots); s->d_allocSlots = nullptr; }
-    if (s->d_batchSend) { (void)hipFree(s->d_batchSend); s->d_batchSend = nullptr; }
-    if (s->d_batchRecv) { (void)hipFree(s->d_batchRecv); s->d_batchRecv = nullptr; }
+    s->res.release(s->d_allocSend); s->res.release(s->d_allocRecv); s->res.release(s->d_allocSlots); s->res.release(s->d_batchSend); s->res.release(s->d_batchRecv);
     s->allocComm = nullptr; s->allocCap = 0;
     if (!comm) return BF_OK;
     BF_REQUIRE(capacity_keys >= 64, "capacity_keys too small");
     uint32_t world = 1, rank = 0;
     BF_TRY_RC(bf_comm_world(comm, &world, &rank));
     const uint64_t rec = 8 + 8ull * capacity_keys;
-    BF_HIP_TRY(BF_MALLOC((void**)&s->d_allocSend, rec));
-    BF_HIP_TRY(BF_MALLOC((void**)&s->d_allocRecv, rec * world));
-    BF_HIP_TRY(BF_MALLOC((void**)&s->d_allocSlots, sizeof(uint32_t) * capacity_keys));
+    BF_TRY_RC(s->res.device(&s->d_allocSend, rec));
+    BF_TRY_RC(s->res.device(&s->d_allocRecv, rec * world));
+    BF_TRY_RC(s->res.device(&s->d_allocSlots, capacity_keys));
     const uint64_t brec = 8 + sizeof(BatchRec) * (uint64_t)capacity_keys;
-    BF_HIP_TRY(BF_MALLOC((void**)&s->d_batchSend, brec));
-    BF_HIP_TRY(BF_MALLOC((void**)&s->d_batchRecv, brec * world));
+    BF_TRY_RC(s->res.device(&s->d_batchSend, brec));
+    BF_TRY_RC(s->res.device(&s->d_batchRecv, brec * world));
     s->allocComm = comm; s->allocCap = capacity_keys;
     return BF_OK;
 }
@@ -2503,21 +2487,7 @@ int bf_scene_get_arith(bf_scene* s, int* mode) {
 int bf_scene_destroy(bf_scene* s) {
     if (!s) return BF_OK;
     (void)syncAll(s);
-    for (void* q : s->allocations) hipFree(q);
-    for (uint2* t : s->texel) if (t) hipFree(t);
-    for (auto& set : s->btexel) for (uint2* t : set) if (t) hipFree(t);
     verifyDump(s);
-    for (bf_voxel* v : s->vshadow) if (v) hipFree(v);
-    if (s->vlog) hipHostFree(s->vlog);
-    if (s->d_allocSend) hipFree(s->d_allocSend);
-    if (s->d_allocRecv) hipFree(s->d_allocRecv);
-    if (s->d_allocSlots) hipFree(s->d_allocSlots);
-    if (s->d_batchSend) hipFree(s->d_batchSend);
-    if (s->d_batchRecv) hipFree(s->d_batchRecv);
-    for (auto& e : s->events) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
-    for (int b = 0; b < bf_scene::NBMAX; ++b) for (hipEvent_t e : {s->evPrep[b], s->evUpd[b]}) if (e) hipEventDestroy(e);
-    for (hipEvent_t e : {s->evBarrier, s->evTmp, s->evPlace}) if (e) hipEventDestroy(e);
-    if (s->prep) hipStreamDestroy(s->prep);
     delete s;
     return BF_OK;
 }

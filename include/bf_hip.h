@@ -55,6 +55,13 @@ BF_API int bf_device_synchronize(void);
 /* one stream only / a blocking copy whose direction follows from the pointers (hipMemcpyDefault): for all-gather callbacks of a host language (bf_comm.h) */
 BF_API int bf_stream_synchronize(void* hip_stream);
 BF_API int bf_memcpy(void* dst, const void* src, size_t bytes);
+/* Diagnostics of resource ownership.  Every handle keeps what it takes from the runtime (device memory, pinned host memory, events, streams) in one owner, counted
+ * process-wide: out = { live owners (== live handles that own anything), live device allocations, live device bytes, live pinned allocations + events + streams,
+ * acquisitions so far, release calls that returned an error }.
+ * bf_debug_fail_acquire(nth): the nth acquisition from this call on, of any handle, fails as out-of-memory without reaching the runtime (bf_last_error says that it was
+ * injected); it fires once and disarms itself, 0 switches it off.  A host-side error return: the create or grow path that meets it unwinds, no kernel sees it. */
+BF_API int bf_debug_live_resources(uint64_t out[6]);
+BF_API int bf_debug_fail_acquire(uint64_t nth);
 
 /* ------------------------------------------------------------------------- */
 /* Voxel-hash TSDF:  DepthSensing/CUDASceneRepHashSDF.h                       */
