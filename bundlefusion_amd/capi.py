@@ -1445,6 +1445,14 @@ class Pipeline:
         check(lib.bf_pipeline_save_mesh(self._h, str(filename).encode(), T, C.byref(nv), C.byref(nf), C.byref(nt)))
         return nv.value, nf.value, nt.value
 
+    def save_point_cloud(self, filename, frame_stride=None, cell_size=0.005, max_depth=3.5, max_points=0):
+        """bf_pipeline_save_point_cloud: the stored frames on the stride under the optimised trajectory as a thinned point cloud PLY, built on the device.
+        frame_stride None: s_submapSize (the key frames).  Returns (points, frames used)."""
+        n, used = C.c_uint32(), C.c_uint32()
+        stride = int(self.gbs.s_submapSize) if frame_stride is None else int(frame_stride)
+        check(lib.bf_pipeline_save_point_cloud(self._h, str(filename).encode(), stride, C.c_float(cell_size), C.c_float(max_depth), int(max_points), C.byref(n), C.byref(used)))
+        return n.value, used.value
+
     def set_record_state(self, state, threads=0, tmp_prefix=None):
         """bf_pipeline_set_record_state: before the first frame; with state.s_recordData every accepted frame is recorded (include/bf_record.h)"""
         check(lib.bf_pipeline_set_record_state(self._h, C.byref(state), int(threads), str(tmp_prefix).encode() if tmp_prefix is not None else None))
@@ -1909,3 +1917,97 @@ class FrameRenderer:
         t = C.c_void_p(); r = C.c_void_p()
         check(lib.bf_frame_renderer_get_images(self._h, C.byref(t), C.byref(r)))
         return _d2h(t.value, self.w * self.h * 16).view("<f4").reshape(self.h, self.w, 4).copy()
+
+
+# --------------------------------------------------------------------------- the point cloud (include/bf_pointcloud.h)
+class PointCloudParams(C.Structure):
+    _fields_ = [("maxPoints", C.c_uint32), ("maxFramePixels", C.c_uint32), ("cellSize", C.c_float), ("maxDepth", C.c_float)]
+
+
+class PointCloudView(C.Structure):
+    _fields_ = [("d_positions", C.c_void_p), ("d_normals", C.c_void_p), ("d_colors", C.c_void_p), ("numPoints", C.c_uint32)]
+
+
+def write_ply_points(filename, positions, normals, colors):
+    """bf_write_ply_points: positions / normals [n,3] float32, colours [n,4] uint8.  Host-only."""
+    pos = np.ascontiguousarray(positions, np.float32).reshape(-1, 3); nrm = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    col = np.ascontiguousarray(colors, np.uint8).reshape(-1, 4)
+    assert len(pos) == len(nrm) == len(col)
+    check(lib.bf_write_ply_points(str(filename).encode(), pos.ctypes.data_as(C.c_void_p), nrm.ctypes.data_as(C.c_void_p), col.ctypes.data_as(C.c_void_p), len(pos)))
+
+
+def point_cloud_build_host(depths, colors, transforms, intrinsics_inv, cell_size=0.005, max_depth=3.5, capacity=None):
+    """bf_point_cloud_build_host: the definition as the sequential loop on one core (no device).  depths: float32 (h, w) arrays, colors: uint8 (h, w, 4),
+    transforms: (n, 4, 4).  Returns (positions, normals, colours, count); with a capacity below the count the arrays hold the first `capacity` points."""
+    ds = [np.ascontiguousarray(d, np.float32) for d in depths]; cs = [np.ascontiguousarray(c, np.uint8) for c in colors]
+    n = len(ds)
+    assert len(cs) == n
+    h, w = ds[0].shape if n else (0, 0)
+    assert all(d.shape == (h, w) for d in ds) and all(c.shape == (h, w, 4) for c in cs)
+    T = np.ascontiguousarray(transforms, np.float32).reshape(-1, 16)
+    assert len(T) == n
+    dp = (C.c_void_p * max(n, 1))(*[d.ctypes.data for d in ds]); cp = (C.c_void_p * max(n, 1))(*[c.ctypes.data for c in cs])
+    cnt = C.c_uint32()
+    args = (dp, cp, n, w, h, _f16(intrinsics_inv), T.ctypes.data_as(C.c_void_p), C.c_float(cell_size), C.c_float(max_depth))
+    if capacity is None:
+        check(lib.bf_point_cloud_build_host(*args, 0, None, None, None, C.byref(cnt)))
+        capacity = cnt.value
+    pos = np.zeros((capacity, 3), np.float32); nrm = np.zeros((capacity, 3), np.float32); col = np.zeros((capacity, 4), np.uint8)
+    check(lib.bf_point_cloud_build_host(*args, int(capacity), pos.ctypes.data_as(C.c_void_p), nrm.ctypes.data_as(C.c_void_p), col.ctypes.data_as(C.c_void_p), C.byref(cnt)))
+    m = min(capacity, cnt.value)
+    return pos[:m], nrm[:m], col[:m], cnt.value
+
+
+class PointCloud:
+    """Python view of `bf_point_cloud`: RGBDSensor::recordPointCloud per frame, thinned on the device to one point per cell as it grows."""
+
+    def __init__(self, max_points, max_frame_pixels, cell_size=0.005, max_depth=3.5, stream=0):
+        self._h = C.c_void_p()
+        self.params = PointCloudParams(int(max_points), int(max_frame_pixels), float(cell_size), float(max_depth))
+        check(lib.bf_point_cloud_create(C.byref(self.params), C.byref(self._h)))
+        if stream:
+            check(lib.bf_point_cloud_set_stream(self._h, C.c_void_p(stream)))
+
+    def close(self):
+        if self._h:
+            lib.bf_point_cloud_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        check(lib.bf_point_cloud_reset(self._h))
+
+    def add_frame(self, depth, color, intrinsics_inv, transform):
+        """depth: float32 cuda tensor (h, w); color: uint8 cuda tensor (h, w, 4).  Returns the number of points the frame appended."""
+        h, w = int(depth.shape[0]), int(depth.shape[1])
+        assert tuple(color.shape) == (h, w, 4) and depth.is_contiguous() and color.is_contiguous()
+        n = C.c_uint32()
+        check(lib.bf_point_cloud_add_frame(self._h, _p(depth), _p(color), w, h, _f16(intrinsics_inv), _f16(transform), C.byref(n)))
+        return n.value
+
+    def view(self):
+        v = PointCloudView()
+        check(lib.bf_point_cloud_get_gpu(self._h, C.byref(v)))
+        return v
+
+    def num_points(self):
+        return self.view().numPoints
+
+    def download(self):
+        """(positions (n, 3) float32, normals (n, 3) float32, colours (n, 4) uint8)"""
+        n = self.num_points()
+        pos = np.zeros((n, 3), np.float32); nrm = np.zeros((n, 3), np.float32); col = np.zeros((n, 4), np.uint8)
+        cnt = C.c_uint32()
+        check(lib.bf_point_cloud_download(self._h, pos.ctypes.data_as(C.c_void_p), nrm.ctypes.data_as(C.c_void_p), col.ctypes.data_as(C.c_void_p), n, C.byref(cnt)))
+        assert cnt.value == n
+        return pos, nrm, col
+
+    def save(self, filename):
+        n = C.c_uint32()
+        check(lib.bf_point_cloud_save(self._h, str(filename).encode(), C.byref(n)))
+        return n.value

@@ -26,6 +26,7 @@
 #include "../../include/bf_render.h"
 #include "../../include/bf_sensordata.h"
 #include "bf_device.h"
+#include "bf_pointcloud.h"
 #include "bf_resources.h"
 #include "bf_se3.h"
 #include "volume_queue.h"
@@ -2135,6 +2136,9 @@ struct bf_pipeline {
     bool volumeSharded = false, volumeComm = false;
     // The recording (bf_record.h): with s_recordData the pipeline owns a recorder, which the image manager feeds at every accepted frame
     bf_sens_recorder* recorder = nullptr; bf_record_state recordState;
+    // The point cloud (bf_pointcloud.h): the accumulator is created by the first bf_pipeline_save_point_cloud and kept; it runs on the ingest stream, which is idle
+    // between two calls of the loop.  The loop itself knows nothing about it
+    bf_point_cloud* pointCloud = nullptr;
     bool timings = false;
     hipEvent_t ev[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     bf_frame_timing last;
@@ -2654,6 +2658,45 @@ int bf_pipeline_save_recording(bf_pipeline* p, const char* filename, int overwri
     return bf_sens_recorder_finish(p->recorder, filename ? filename : p->recordState.s_recordDataFile, T.data(), recorded ? count : 0, overwrite, actualName, capacity, numFramesWritten);
 }
 
+// ---- the point cloud (bf_pointcloud.h): SiftVisualization::saveToPointCloud (SiftVisualization.cpp:607-644) over the stored integration frames
+int bf_pipeline_save_point_cloud(bf_pipeline* p, const char* filename, uint32_t frameStride, float cellSize, float maxDepth, uint32_t maxPoints, uint32_t* numPoints,
+                                 uint32_t* numFramesUsed) {
+    BF_REQUIRE(p && filename, "null argument");
+    BF_REQUIRE(frameStride >= 1, "the frame stride must be at least 1");
+    if (numPoints) *numPoints = 0;
+    if (numFramesUsed) *numFramesUsed = 0;
+    BF_TRY(plFlush(p));
+    bf_trajectory_manager* tm = nullptr;
+    BF_TRY(bf_online_bundler_get_trajectory_manager(p->ob, &tm));
+    uint32_t n = 0, count = 0;
+    BF_TRY(bf_trajectory_manager_get_num_optimized_frames(tm, &n));
+    std::vector<float> T((size_t)std::max(n, 1u) * 16);
+    if (n) BF_TRY(bf_trajectory_manager_get_optimized_transforms(tm, T.data(), n, &count));
+    count = std::min(count, p->im->currFrame);
+    bf_point_cloud_params pp;
+    pp.maxPoints = maxPoints ? maxPoints : (4u << 20); pp.maxFramePixels = p->im->wInt * p->im->hInt; pp.cellSize = cellSize; pp.maxDepth = maxDepth;
+    if (p->pointCloud && memcmp(&p->pointCloud->params, &pp, sizeof pp) != 0) { bf_point_cloud_destroy(p->pointCloud); p->pointCloud = nullptr; }
+    if (!p->pointCloud) {
+        BF_TRY(bf_point_cloud_create(&pp, &p->pointCloud));
+        BF_TRY(bf_point_cloud_set_stream(p->pointCloud, p->sIngest));
+    }
+    BF_TRY(bf_point_cloud_reset(p->pointCloud));
+    // registered depth lives in the colour camera (DepthSensing.cpp:285-288), as for the integration
+    const m44& Kinv = p->im->calib ? p->im->colorIntrinsicsInv : p->im->depthIntrinsicsInv;
+    uint32_t used = 0;
+    for (uint32_t f = 0; f < count; f += frameStride) {
+        const float* Tf = T.data() + 16 * (size_t)f;
+        if (Tf[0] != Tf[0] || Tf[0] == NINF) continue;
+        const float* d_depth = nullptr; const uint8_t* d_color = nullptr;
+        BF_TRY(bf_image_manager_get_integrate_frame_gpu(p->im, f, &d_depth, &d_color));
+        BF_TRY(bf_point_cloud_add_frame(p->pointCloud, d_depth, d_color, p->im->wInt, p->im->hInt, Kinv.e, Tf, nullptr));
+        ++used;
+    }
+    BF_TRY(bf_point_cloud_save(p->pointCloud, filename, numPoints));
+    if (numFramesUsed) *numFramesUsed = used;
+    return BF_OK;
+}
+
 int bf_pipeline_destroy(bf_pipeline* p) {
     if (!p) return BF_OK;
     p->vol.stop();
@@ -2661,6 +2704,7 @@ int bf_pipeline_destroy(bf_pipeline* p) {
     bf_marching_cubes_destroy(p->marchingCubes);
     if (p->im) p->im->recorder = nullptr;
     bf_sens_recorder_destroy(p->recorder);
+    bf_point_cloud_destroy(p->pointCloud);
     bf_ray_cast_destroy(p->rayCast); bf_frame_renderer_destroy(p->renderer); bf_frame_renderer_destroy(p->inputRenderer);
     if (!p->tracePath.empty() && !p->trace.empty()) {
         if (FILE* f = fopen(p->tracePath.c_str(), "a")) {

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../bf_pipeline.h"
+#include "../bf_pointcloud.h"
 #include "../bf_record.h"
 #include "../bf_render.h"
 #include "../bf_sensordata.h"
@@ -882,6 +883,55 @@ private:
     bf_frame_renderer* m_h = nullptr;
     unsigned int m_width, m_height;
     std::vector<unsigned char> m_host;
+};
+
+// ---- SiftVisualization::saveToPointCloud (SiftVisualization.cpp:607-644): every skip-th frame with a valid pose as a coloured, oriented point cloud, thinned to one
+// point per cell (sparsifyUniform(0.005f, true)) and written as a PLY - bf_pointcloud.h states the definition.  Three forms: the reference's own over host images
+// (the sequential host route), over a CUDAImageManager's stored frames (the device accumulator, straight from HBM), and from a bf_pipeline's frame loop.
+class SiftVisualization {
+public:
+    // depthImages: width x height float metres; colorImages: RGBX8 of the same size (the reference's vec3uc images carry the same three bytes).  Returns the points
+    static unsigned int saveToPointCloud(const std::string& filename, const std::vector<const float*>& depthImages, const std::vector<const unsigned char*>& colorImages,
+                                         const std::vector<mat4f>& trajectory, const mat4f& depthIntrinsicsInv, unsigned int width, unsigned int height, unsigned int skip = 1,
+                                         unsigned int numFrames = (unsigned int)-1, float maxDepth = 3.5f, float cellSize = 0.005f) {
+        if (numFrames == (unsigned int)-1) numFrames = (unsigned int)std::min(depthImages.size(), trajectory.size());          // :612
+        std::vector<const float*> d; std::vector<const uint8_t*> c; std::vector<float> T;
+        for (unsigned int i = 0; i < numFrames; i += std::max(skip, 1u)) { d.push_back(depthImages[i]); c.push_back(colorImages[i]); T.insert(T.end(), trajectory[i].m, trajectory[i].m + 16); }
+        uint32_t n = 0;
+        check(bf_point_cloud_build_host(d.data(), c.data(), (uint32_t)d.size(), width, height, depthIntrinsicsInv.m, T.data(), cellSize, maxDepth, 0, nullptr, nullptr, nullptr, &n));
+        std::vector<float> pos(3 * (size_t)std::max(n, 1u)), nrm(3 * (size_t)std::max(n, 1u)); std::vector<uint8_t> col(4 * (size_t)std::max(n, 1u));
+        check(bf_point_cloud_build_host(d.data(), c.data(), (uint32_t)d.size(), width, height, depthIntrinsicsInv.m, T.data(), cellSize, maxDepth, n, pos.data(), nrm.data(), col.data(), &n));
+        check(bf_write_ply_points(filename.c_str(), pos.data(), nrm.data(), col.data(), n));
+        return n;
+    }
+    // the frames a CUDAImageManager keeps (storeFramesOnGPU: nothing is uploaded again); maxPoints bounds the cloud
+    static unsigned int saveToPointCloud(const std::string& filename, CUDAImageManager& imageManager, const std::vector<mat4f>& trajectory, const mat4f& depthIntrinsicsInv,
+                                         unsigned int skip = 1, unsigned int numFrames = (unsigned int)-1, float maxDepth = 3.5f, float cellSize = 0.005f,
+                                         unsigned int maxPoints = 4u << 20) {
+        const unsigned int w = imageManager.getIntegrationWidth(), h = imageManager.getIntegrationHeight();
+        if (numFrames == (unsigned int)-1) numFrames = (unsigned int)trajectory.size();
+        bf_point_cloud_params pp; pp.maxPoints = maxPoints; pp.maxFramePixels = w * h; pp.cellSize = cellSize; pp.maxDepth = maxDepth;
+        bf_point_cloud* pc = nullptr;
+        check(bf_point_cloud_create(&pp, &pc));
+        int rc = BF_OK; uint32_t n = 0;
+        for (unsigned int i = 0; i < numFrames && rc == BF_OK; i += std::max(skip, 1u)) {
+            const float* d = nullptr; const uint8_t* c = nullptr;
+            rc = bf_image_manager_get_integrate_frame_gpu(imageManager.handle(), i, &d, &c);
+            if (rc == BF_OK) rc = bf_point_cloud_add_frame(pc, d, c, w, h, depthIntrinsicsInv.m, trajectory[i].m, nullptr);
+        }
+        if (rc == BF_OK) rc = bf_point_cloud_save(pc, filename.c_str(), &n);
+        bf_point_cloud_destroy(pc);
+        check(rc);
+        return n;
+    }
+    // from the frame loop: the optimised trajectory and the stored frames of `pipeline` (bf_pipeline_save_point_cloud); skip 0: s_submapSize, the key frames
+    static unsigned int saveToPointCloud(const std::string& filename, bf_pipeline* pipeline, unsigned int skip = 0, float maxDepth = 3.5f, float cellSize = 0.005f,
+                                         unsigned int maxPoints = 0, unsigned int* numFramesUsed = nullptr) {
+        uint32_t n = 0, used = 0;
+        check(bf_pipeline_save_point_cloud(pipeline, filename.c_str(), skip ? skip : GlobalBundlingState::get().s_submapSize, cellSize, maxDepth, maxPoints, &n, &used));
+        if (numFramesUsed) *numFramesUsed = used;
+        return n;
+    }
 };
 
 // ---- CorrespondenceEvaluator (CorrespondenceEvaluator.h:10-141)

@@ -5,6 +5,9 @@ usage: python tools/run_sens.py sequence.sens [--voxel 0.01] [--app zParametersD
                                 [--ingest host|device] [--decode-threads N] [--camera-calibration] [--mesh scan.ply] [--mesh-host scan_host.ply]
 --mesh: the scan's mesh after the end of the sequence, extracted and welded on the device (bf_pipeline_save_mesh); --mesh-host: the same file by the host route
 (bf_marching_cubes_extract + bf_marching_cubes_save_mesh).  Both print the vertex, face and triangle counts and the seconds spent.
+--point-cloud FILE [--point-cloud-stride N --point-cloud-cell M]: the stored frames on the stride (default s_submapSize: the key frames) under the optimised
+trajectory as a coloured, oriented point cloud, one point per cell of M metres (default 0.005), thinned on the device (bf_pipeline_save_point_cloud);
+--point-cloud-host FILE: the same file by the host route on one core.  Both print frame and point counts and the seconds spent.
 --camera-calibration: s_bUseCameraCalibration = true - register every frame's depth to the colour camera with the extrinsics and intrinsics of the file's
 header (a file whose depth extrinsics are the identity has nothing to register; the line below says whether it is active).
 --ingest host (default): frames are decoded on the host and handed over as host buffers (the PCIe path of bf_pipeline_process_frame).
@@ -21,7 +24,7 @@ import numpy as np
 
 import bundlefusion_amd as bf
 from bundlefusion_amd import sensordata as sdm
-from tools import mesh_out
+from tools import mesh_out, point_cloud_out
 
 
 def main():
@@ -42,6 +45,7 @@ def main():
     ap.add_argument("--record", default=None, metavar="FILE", help="s_recordData: record every accepted frame and save FILE with the optimised trajectory (bf_pipeline_save_recording)")
     ap.add_argument("--record-threads", type=int, default=4, help="encode threads of --record (1 .. 12)")
     mesh_out.add_arguments(ap)
+    point_cloud_out.add_arguments(ap)
     a = ap.parse_args()
     sd = sdm.SensorData(a.sens, use_pillow=a.ingest == "host" and a.decoder == "auto")        # (the player's workers decode with the library's own decoder)
     n = len(sd) if a.frames <= 0 else min(a.frames, len(sd))
@@ -99,6 +103,7 @@ def main():
         name, frames = p.save_recording(a.record)
         print("recorded %d frames to %s (%.3f s to drain and save)" % (frames, name, time.time() - t1))
     mesh_out.write(p, a)
+    point_cloud_out.write(p, a)
 
 
 if __name__ == "__main__":

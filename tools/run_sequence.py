@@ -1,6 +1,7 @@
 """Run the headless BundleFusion frame loop on a synthetic S2 stream and report poses / timings.
 
 usage: python tools/run_sequence.py [--frames N] [--voxel 0.01] [--host] [--timings] [--mesh scan.ply] [--mesh-host scan_host.ply]
+                                     [--point-cloud cloud.ply [--point-cloud-stride N --point-cloud-cell M]] [--point-cloud-host cloud_host.ply]
 """
 import argparse
 import sys
@@ -14,7 +15,7 @@ import torch
 import bundlefusion_amd as bf
 from bundlefusion_amd import synth
 from bundlefusion_amd.capi import intrinsics_matrix
-from tools import mesh_out
+from tools import mesh_out, point_cloud_out
 
 
 def main():
@@ -36,6 +37,7 @@ def main():
     ap.add_argument("--record", default=None, metavar="FILE", help="s_recordData: record every accepted frame and save FILE with the optimised trajectory (bf_pipeline_save_recording)")
     ap.add_argument("--record-threads", type=int, default=4, help="encode threads of --record (1 .. 12)")
     mesh_out.add_arguments(ap)
+    point_cloud_out.add_arguments(ap)
     a = ap.parse_args()
     W, H = a.width, a.height
     idx = [a.first + k * a.stride for k in range(a.frames)]
@@ -105,6 +107,7 @@ def main():
         name, nrec = p.save_recording(a.record)
         print("recorded %d frames to %s (%.3f s to drain and save)" % (nrec, name, time.time() - t1))
     mesh_out.write(p, a)
+    point_cloud_out.write(p, a)
     if tl:
         keys = [k for k in tl[0].keys() if k != "frame"]
         for name, sel in (("all frames", lambda f: True), ("chunk-end frames", lambda f: f % 10 == 9), ("other frames", lambda f: f % 10 != 9)):
