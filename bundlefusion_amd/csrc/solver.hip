@@ -766,7 +766,7 @@ __global__ __launch_bounds__(1024) void k_pcg(Dev d, uint32_t nLin, uint32_t gnI
 // no second exchange is needed.  The result does not depend on G (row arithmetic is per row, reductions are per 256 threads).
 // Exchanged data and the barrier counter use relaxed agent-scope atomics (sc1 accesses: coherent across the 8 XCD L2s) and an
 // explicit s_waitcnt instead of fences, so no L2 write-back / invalidate disturbs the voxel kernels running beside it.
-constexpr uint32_t COOP_THREADS = 256, COOP_THREADS_SMALL = 1024, COOP_MAX_GROUPS = 64, COOP_ROWS_PER_GROUP = 8, COOP_SPIN_LIMIT = 1u << 22;
+constexpr uint32_t COOP_THREADS = 256, COOP_MAX_GROUPS = 64, COOP_ROWS_PER_GROUP = 8, COOP_SPIN_LIMIT = 1u << 22;
 
 BF_DEV void coopPublish(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 BF_DEV float coopRead(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -788,9 +788,8 @@ BF_DEV bool gridBarrier(uint32_t* counter, uint32_t target, int* shFail) {
     return *shFail == 0;
 }
 
-// THREADS: 256; 1024 for ONE workgroup over a small problem (6 N <= 256: every vector element has a thread of its own under both widths and the wave
-// partials beyond the first four are zeros, so the sums - and every bit of the result - are those of the 256-thread form): the row products, one wave per row,
-// take N / 16 instead of N / 4 trips - the single-workgroup solves of a chunk (11 frames) and of the first ~40 key frames are latency chains of 100 - 150 iterations.
+// THREADS: 256.  ONE workgroup over a small problem (6 N <= 256) takes k_pcg_small below instead, which gives the bits of this kernel (BF_PCG_WIDE=0 keeps
+// this one for every problem: the bit reference of that form).
 // vecGlobal: the workgroup's private copies of the five vectors and of the row offsets live in global memory (d.coopVec, one region per
 // workgroup, L2-resident) instead of LDS - the form for problems whose vectors do not fit (31 N floats: N > ~1300 key frames; round 2 fell
 // back to ONE workgroup there, 79 us per iteration at N = 2000).  Same arithmetic, same order.
@@ -919,6 +918,205 @@ __global__ __launch_bounds__(THREADS) void k_pcg_coop(Dev d, uint32_t nLin, uint
     }
     mx = blockMax(mx, sh);
     if (threadIdx.x == 0) {
+        d.flags[FL_GN_ITERS] = (int)gnIter + 1;
+        d.flags[FL_PCG_ITERS + gnIter] = (int)it;
+        if (!lastGN && mx < 0.005f) d.flags[FL_DONE] = 1;                         // :1204-1210
+    }
+}
+
+// ONE workgroup over a small problem (6 N <= 256: a chunk's 11 frames, the first key frames): the 256-thread form of k_pcg_coop gives every vector
+// element 6 + t a thread t of its own, and an iteration there is a chain of six workgroup barriers and two serial 4-deep LDS sums.  Here every WAVE
+// carries the whole CG state redundantly in registers: register j of lane l holds element 6 + 64 j + l of p, r, delta, M^-1 and Ap (NJ registers
+// cover 6 N - 6 elements) - what thread 64 j + l of the 256-thread form owns.  A dot product is wave_sum over each register (the partial of wave j
+// there) and ((((0 + p0) + p1) + p2) + p3) over the partials (its blockSum; partials past NJ are exact zeros there): the same bits without leaving
+// the wave, and alpha, beta and the early-out agree across waves without an exchange, as they do across the workgroups of k_pcg_coop.  The row
+// products (one wave per block row, same lanes, same order) read p by column, so each wave keeps a private copy of p in LDS that it alone writes
+// (no barrier orders it), and they write Ap to LDS for all waves: double-buffered by iteration parity, so ONE barrier per iteration is all that
+// is left - a wave writes buffer b again only behind the next barrier, which every wave passes after its reads of b.  A wave's rows are fixed for
+// the launch (at most SMALL_TRIPS of them), so their diagonal blocks and the first eight slots of each stay in registers too; per iteration a
+// wave reads p (12 floats per row), Ap (NJ floats per lane) and writes its rows of Ap and its copy of p - nothing else.
+constexpr uint32_t SMALL_MAX_WAVES = 16, SMALL_TRIPS = 3, SMALL_VEC = 256;       // 41 rows over 16 waves: three trips at the most
+static_assert(SMALL_MAX_WAVES * SMALL_TRIPS * 6 >= COOP_THREADS - 6 && SMALL_VEC >= COOP_THREADS, "every row of a 6 N <= 256 problem has a wave and a trip");
+
+// lane ^ O of a full wave on the vector ALU (DPP moves, v_permlane16/32_swap): __shfl_xor is a ds_bpermute_b32, and with every wave reducing for itself the
+// 12 x NJ of them per wave and iteration queue up at the workgroup's one LDS (profiles/pcg_small.md).  The same lanes exchange the same values.
+template <int CTRL> BF_DEV float dppMov(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true)); }
+template <int O> BF_DEV float laneXor(float v) {
+    if constexpr (O == 1) return dppMov<0xB1>(v);                                 // quad_perm:[1,0,3,2]
+    else if constexpr (O == 2) return dppMov<0x4E>(v);                            // quad_perm:[2,3,0,1]
+    else if constexpr (O == 4) return dppMov<0x1B>(dppMov<0x141>(v));             // row_half_mirror (lane ^ 7), then quad_perm:[3,2,1,0] (lane ^ 3)
+    else if constexpr (O == 8) return dppMov<0x128>(v);                           // row_ror:8
+    else if constexpr (O == 16) {                                                 // odd 16-lane rows of the first operand <-> even rows of the second
+        const uint32_t u = __builtin_bit_cast(uint32_t, v);
+        const auto r = __builtin_amdgcn_permlane16_swap(u, u, false, false);
+        return __builtin_bit_cast(float, (threadIdx.x & 16) ? r[0] : r[1]);
+    } else {                                                                      // upper half of the first operand <-> lower half of the second
+        static_assert(O == 32, "lane distance");
+        const uint32_t u = __builtin_bit_cast(uint32_t, v);
+        const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+        return __builtin_bit_cast(float, (threadIdx.x & 32) ? r[0] : r[1]);
+    }
+}
+BF_DEV float waveSumAlu(float v) {                                                // wave_sum (bf_device.h): the butterfly 32, 16, 8, 4, 2, 1
+    v += laneXor<32>(v); v += laneXor<16>(v); v += laneXor<8>(v); v += laneXor<4>(v); v += laneXor<2>(v); v += laneXor<1>(v);
+    return v;
+}
+
+template <uint32_t NJ>
+__global__ __launch_bounds__(SMALL_MAX_WAVES * 64) void k_pcg_small(Dev d, uint32_t nLin, uint32_t gnIter, int lastGN, uint32_t ldsFloats) {
+    if (d.flags[FL_DONE]) return;
+    extern __shared__ __align__(16) float smallLds[];
+    const uint32_t N = d.N, n6 = 6 * N;
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nWaves = blockDim.x >> 6;
+    float* const PW = smallLds + wave * SMALL_VEC;                                // this wave's copy of p
+    float* const APB = smallLds + nWaves * SMALL_VEC;                             // Ap, two buffers
+    float* const OL = APB + 2 * SMALL_VEC;                                        // off-diagonal blocks (16-byte aligned), then one column index per slot
+    // The matrix does not change between iterations: the wave keeps what its rows (1 + wave + k nWaves, k < SMALL_TRIPS) need of it in registers -
+    // lane a < 6 of group g8 row a of the row's slot g8 and that slot's column, lanes 0 .. 5 the rows of the diagonal block.  Lanes without a slot
+    // hold zeros and column 0, whose p is the fixed frame's zeros: their product is the + 0 the slot loop starts from.
+    const uint32_t g8 = lane >> 3, a = lane & 7;
+    uint32_t rowI[SMALL_TRIPS], sNext[SMALL_TRIPS], sStop[SMALL_TRIPS], col0[SMALL_TRIPS];
+    float o0[SMALL_TRIPS][6], dg[SMALL_TRIPS][6];
+    bool more = false;
+#pragma unroll
+    for (uint32_t k = 0; k < SMALL_TRIPS; ++k) {
+        const uint32_t i = 1 + wave + k * nWaves;
+        rowI[k] = i; sNext[k] = sStop[k] = 0; col0[k] = 0;
+#pragma unroll
+        for (int b = 0; b < 6; ++b) { o0[k][b] = 0.0f; dg[k][b] = 0.0f; }
+        if (i < N) {
+            const uint32_t s = d.rowStart[i] + g8, s1 = d.rowStart[i + 1];
+            if (a < 6 && s < s1) {
+                const float* O = d.slotO + (size_t)s * 36 + a * 6;
+#pragma unroll
+                for (int b = 0; b < 6; ++b) o0[k][b] = O[b];
+                col0[k] = d.slotCol[s];
+                sNext[k] = s + 8; sStop[k] = s1;
+                more |= s + 8 < s1;
+            }
+            if (lane < 6) {
+                const float* A = d.diagA + (size_t)i * 36 + lane * 6;
+#pragma unroll
+                for (int b = 0; b < 6; ++b) dg[k][b] = A[b];
+            }
+        }
+    }
+    // rows of more than 8 slots take the rest from LDS (from global memory what does not fit, as in k_pcg_coop); staged only where there is such a row
+    const uint32_t sBase = d.rowStart[1], sEnd = d.rowStart[N];
+    const bool longRows = __syncthreads_or(more) != 0;
+    const uint32_t ldsSlots = longRows ? min(sEnd - sBase, (ldsFloats - (uint32_t)(OL - smallLds)) / 37u) : 0u;
+    uint32_t* const CL = reinterpret_cast<uint32_t*>(OL + (size_t)ldsSlots * 36);
+    {
+        const float4* src = reinterpret_cast<const float4*>(d.slotO + (size_t)sBase * 36);
+        float4* dst = reinterpret_cast<float4*>(OL);
+        for (uint32_t t = threadIdx.x; t < ldsSlots * 9; t += blockDim.x) dst[t] = src[t];
+        for (uint32_t t = threadIdx.x; t < ldsSlots; t += blockDim.x) CL[t] = d.slotCol[sBase + t];
+    }
+    // Initialization (SolverBundling.cu:755-794): r = -J^T F, p = M^-1 r, delta = 0
+    bool own[NJ];
+    float m[NJ], r[NJ], x[NJ], p[NJ], ap[NJ];
+#pragma unroll
+    for (uint32_t j = 0; j < NJ; ++j) {
+        const uint32_t t = 6 + 64 * j + lane;
+        own[j] = t < n6;
+        m[j] = own[j] ? d.prec[t] : 0.0f;
+        r[j] = own[j] ? d.rhs[t] : 0.0f;
+        p[j] = m[j] * r[j]; x[j] = 0.0f;
+        if (own[j]) PW[t] = p[j];
+    }
+    if (lane < 6) PW[lane] = 0.0f;
+    // this one sum runs over t = thread, not 6 + thread, in the 256-thread form: its wave partials are over elements 64 j + l
+    float rzOld = 0.0f;
+#pragma unroll
+    for (uint32_t j = 0; j < (NJ < 4 ? NJ + 1 : 4); ++j) {
+        const uint32_t t = 64 * j + lane;
+        const bool var = t >= 6 && t < n6;
+        const float rr = var ? d.rhs[t] : 0.0f;
+        const float pp = var ? d.prec[t] * rr : 0.0f;
+        rzOld += waveSumAlu(0.0f + rr * pp);
+    }
+    __syncthreads();                                                               // the blocks are staged
+    uint32_t it = 0;
+    for (uint32_t lin = 0; lin < nLin; ++lin) {
+        bool last = (lin == nLin - 1);
+        ++it;
+        float* const out = APB + (lin & 1) * SMALL_VEC;
+        // Ap: one wave per row, 8 lanes per off-diagonal block (lane a < 6 = row a of the 6x6 block), the sums in the order of k_pcg_coop
+#pragma unroll
+        for (uint32_t k = 0; k < SMALL_TRIPS; ++k) {
+            const uint32_t i = rowI[k];
+            if (i >= N) break;
+            const float* pj = PW + 6 * col0[k];
+            float acc = 0.0f;
+            acc += ((((o0[k][0] * pj[0] + o0[k][1] * pj[1]) + o0[k][2] * pj[2]) + o0[k][3] * pj[3]) + o0[k][4] * pj[4]) + o0[k][5] * pj[5];
+            if (longRows) {
+                uint32_t s = sNext[k];
+                const uint32_t s1 = sStop[k], sLds = min(s1, sBase + ldsSlots);
+                for (; s < sLds; s += 8) {
+                    const uint32_t ls = s - sBase;
+                    const float* O = OL + (size_t)ls * 36 + a * 6;
+                    const float* q = PW + 6 * CL[ls];
+                    acc += ((((O[0] * q[0] + O[1] * q[1]) + O[2] * q[2]) + O[3] * q[3]) + O[4] * q[4]) + O[5] * q[5];
+                }
+                for (; s < s1; s += 8) {
+                    const float* O = d.slotO + (size_t)s * 36 + a * 6;
+                    const float* q = PW + 6 * d.slotCol[s];
+                    acc += ((((O[0] * q[0] + O[1] * q[1]) + O[2] * q[2]) + O[3] * q[3]) + O[4] * q[4]) + O[5] * q[5];
+                }
+            }
+            acc += laneXor<8>(acc); acc += laneXor<16>(acc); acc += laneXor<32>(acc);
+            const float* pi = PW + 6 * i;
+            float v = 0.0f;
+#pragma unroll
+            for (int b = 0; b < 6; ++b) v += dg[k][b] * pi[b];
+            if (lane < 6) out[6 * i + lane] = v + acc;
+        }
+        __syncthreads();
+        float pAp = 0.0f;
+#pragma unroll
+        for (uint32_t j = 0; j < NJ; ++j) ap[j] = out[6 + 64 * j + lane];          // (lanes past 6 N read what lies behind the vector, and drop it)
+#pragma unroll
+        for (uint32_t j = 0; j < NJ; ++j) {
+            ap[j] = own[j] ? ap[j] : 0.0f;
+            pAp += waveSumAlu(0.0f + p[j] * ap[j]);                                  // PCGStep_Kernel1b
+        }
+        const float alpha = pAp > FLOAT_EPSILON ? rzOld / pAp : 0.0f;             // PCGStep_Kernel2 :948-983
+        float rzNew = 0.0f;
+#pragma unroll
+        for (uint32_t j = 0; j < NJ; ++j) {
+            const float xx = x[j] + alpha * p[j];
+            const float rr = r[j] - alpha * ap[j];
+            x[j] = own[j] ? xx : 0.0f; r[j] = own[j] ? rr : 0.0f;               // lanes past 6 N stay zeros (alpha may be anything)
+            rzNew += waveSumAlu(0.0f + (m[j] * r[j]) * r[j]);
+        }
+        if (fabsf(pAp) < 5e-7f) last = true;                                      // :1088-1093
+        const float beta = rzOld > FLOAT_EPSILON ? rzNew / rzOld : 0.0f;          // PCGStep_Kernel3 :985-1022
+        rzOld = rzNew;
+#pragma unroll
+        for (uint32_t j = 0; j < NJ; ++j) {
+            const float pp = m[j] * r[j] + beta * p[j];
+            p[j] = own[j] ? pp : 0.0f;
+            if (own[j]) PW[6 + 64 * j + lane] = p[j];
+        }
+        if (last) break;
+    }
+    if (wave != 0) return;
+    // Lie update (computeLieUpdate, LieDerivUtil.h:301-307) + GN convergence (EvalGNConvergence :694-749): the N - 1 <= 41 frames are wave 0's
+#pragma unroll
+    for (uint32_t j = 0; j < NJ; ++j) if (own[j]) PW[6 + 64 * j + lane] = x[j];
+    const float* const X = PW;
+    float mx = 0.0f;
+    const uint32_t i = 1 + lane;
+    if (i < N) {
+        const f3 dT = ld3(X + 6 * i), dW = ld3(X + 6 * i + 3);
+        f3 nw, nt;
+        lieUpdate(dW, dT, ld3(d.xRot + 3 * i), ld3(d.xTrans + 3 * i), nw, nt);
+        d.xRot[3 * i] = nw.x; d.xRot[3 * i + 1] = nw.y; d.xRot[3 * i + 2] = nw.z;
+        d.xTrans[3 * i] = nt.x; d.xTrans[3 * i + 1] = nt.y; d.xTrans[3 * i + 2] = nt.z;
+        if (d.valid[i] != 0) mx = fmaxf(mx, fmaxf(fmaxf(fmaxf(fabsf(dW.x), fabsf(dT.x)), fmaxf(fabsf(dW.y), fabsf(dT.y))), fmaxf(fabsf(dW.z), fabsf(dT.z))));
+    }
+    mx = fmaxf(0.0f, wave_max(mx));                                               // blockMax over 256 threads: waves 1 - 3 hold zeros
+    if (lane == 0) {
         d.flags[FL_GN_ITERS] = (int)gnIter + 1;
         d.flags[FL_PCG_ITERS + gnIter] = (int)it;
         if (!lastGN && mx < 0.005f) d.flags[FL_DONE] = 1;                         // :1204-1210
@@ -1066,7 +1264,10 @@ int bf_solver_create(uint32_t maxNumberOfImages, uint32_t maxNumResiduals, const
     s->maxImages = maxNumberOfImages; s->maxResiduals = maxNumResiduals;
     BF_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pcg<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)PCG_LDS_MAX));
     BF_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pcg_coop<COOP_THREADS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)PCG_LDS_MAX));
-    BF_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pcg_coop<COOP_THREADS_SMALL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)PCG_LDS_MAX));
+    BF_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pcg_small<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)PCG_LDS_MAX));
+    BF_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pcg_small<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)PCG_LDS_MAX));
+    BF_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pcg_small<3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)PCG_LDS_MAX));
+    BF_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pcg_small<4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)PCG_LDS_MAX));
     if (const char* e = getenv("BF_PCG_WIDE")) s->pcgWide = atoi(e) != 0;
     if (const char* e = getenv("BF_PCG_GROUPS")) s->pcgGroups = atoi(e);        // 0: single-workgroup kernel, n > 0: force n groups
     if (const char* e = getenv("BF_PCG_VEC_GLOBAL")) s->forceVecGlobal = atoi(e) != 0;      // tests: the large-N form (vectors in global memory) on a small problem
@@ -1182,8 +1383,21 @@ int bf_solver_solve(bf_solver* s, bf_entry_j* d_corr, uint32_t numCorr, const in
             const bool vecFits = !vecGlobal || (size_t)G * (((size_t)31 * N + 1 + 3) & ~(size_t)3) <= s->coopVecFloats;
             if (s->pcgGroups != 0 && nNonLin <= 32 && vecFits && baseFloats + 37 * 8 <= PCG_LDS_MAX / 4)
             {
-                if (s->pcgWide && G == 1 && 6 * N <= COOP_THREADS)
-                    hipLaunchKernelGGL(k_pcg_coop<COOP_THREADS_SMALL>, dim3(G), dim3(COOP_THREADS_SMALL), ldsFloats * 4, st, d, nLin, it, (int)(it == nNonLin - 1), (uint32_t)ldsFloats, vecGlobal);
+                if (s->pcgWide && G == 1 && 6 * N <= COOP_THREADS && !vecGlobal) {
+                    // Every wave repeats the vector part of an iteration, so more waves are more work for the four SIMDs and fewer waves more trips of the row
+                    // part: the fewest waves that cover the rows in SMALL_TRIPS trips, in whole waves per SIMD, eight at least (measured: profiles/pcg_small.md)
+                    const uint32_t waves = std::min(SMALL_MAX_WAVES, std::max(8u, 4u * div_up(div_up(N - 1, SMALL_TRIPS), 4u)));
+                    const size_t smallBase = (size_t)(waves + 2) * SMALL_VEC;            // the waves' copies of p, two Ap buffers; then the slots of rows longer than 8 (and 8 floats the last Ap read may touch)
+                    const uint32_t smallLds = (uint32_t)std::min<size_t>(PCG_LDS_MAX / 4, smallBase + std::max<size_t>(8, (size_t)(N - 1) * (N - 1) * 37));
+                    const dim3 block(waves * 64);
+                    const int lastGN = (int)(it == nNonLin - 1);
+                    switch (div_up(6 * N - 6, 64)) {                                     // registers per vector
+                        case 1: hipLaunchKernelGGL(k_pcg_small<1>, dim3(1), block, smallLds * 4, st, d, nLin, it, lastGN, smallLds); break;
+                        case 2: hipLaunchKernelGGL(k_pcg_small<2>, dim3(1), block, smallLds * 4, st, d, nLin, it, lastGN, smallLds); break;
+                        case 3: hipLaunchKernelGGL(k_pcg_small<3>, dim3(1), block, smallLds * 4, st, d, nLin, it, lastGN, smallLds); break;
+                        default: hipLaunchKernelGGL(k_pcg_small<4>, dim3(1), block, smallLds * 4, st, d, nLin, it, lastGN, smallLds); break;
+                    }
+                }
                 else
                     hipLaunchKernelGGL(k_pcg_coop<COOP_THREADS>, dim3(G), dim3(COOP_THREADS), ldsFloats * 4, st, d, nLin, it, (int)(it == nNonLin - 1), (uint32_t)ldsFloats, vecGlobal);
             }
