@@ -1445,6 +1445,14 @@ class Pipeline:
         check(lib.bf_pipeline_save_mesh(self._h, str(filename).encode(), T, C.byref(nv), C.byref(nf), C.byref(nt)))
         return nv.value, nf.value, nt.value
 
+    def save_mesh_clean(self, filename, transform=None, min_faces=0, largest=False, normals=False):
+        """bf_pipeline_save_mesh_clean: save_mesh with the mesh cleaned on the device between the weld and the file (components below min_faces faces dropped, only
+        the largest kept, per-vertex normals written).  Returns (stats dict, triangles)."""
+        p = MeshCleanParams(int(min_faces), int(bool(largest)), int(bool(normals))); st = MeshCleanStats(); nt = C.c_uint32()
+        T = mat16(transform) if transform is not None else None
+        check(lib.bf_pipeline_save_mesh_clean(self._h, str(filename).encode(), T, C.byref(p), C.byref(st), C.byref(nt)))
+        return st.as_dict(), nt.value
+
     def save_point_cloud(self, filename, frame_stride=None, cell_size=0.005, max_depth=3.5, max_points=0):
         """bf_pipeline_save_point_cloud: the stored frames on the stride under the optimised trajectory as a thinned point cloud PLY, built on the device.
         frame_stride None: s_submapSize (the key frames).  Returns (points, frames used)."""
@@ -1660,8 +1668,82 @@ class MarchingCubesHashSDF:
         return nv.value, nf.value
 
 
+    # ---- MI355X additions: the indexed mesh cleaned in HBM (csrc/meshclean.hip)
+    def clean(self, mesh=None, min_faces=0, largest=False, normals=False):
+        """bf_marching_cubes_clean + download: (positions, colours, normals or None, faces, stats dict).  mesh: (positions [nv,3] float32, colours [nv,3] float32,
+        faces [nf,3] uint32) as contiguous torch cuda tensors, or None for the last weld."""
+        p = MeshCleanParams(int(min_faces), int(bool(largest)), int(bool(normals)))
+        out = CleanMesh(); st = MeshCleanStats()
+        if mesh is None:
+            check(lib.bf_marching_cubes_clean(self._h, None, C.byref(p), C.byref(out), C.byref(st)))
+        else:
+            pos, col, faces = mesh
+            assert pos.is_contiguous() and col.is_contiguous() and faces.is_contiguous() and pos.numel() == col.numel() and pos.numel() % 3 == 0 and faces.numel() % 3 == 0
+            m = IndexedMesh(pos.data_ptr() or None, col.data_ptr() or None, faces.data_ptr() or None, pos.numel() // 3, faces.numel() // 3)
+            check(lib.bf_marching_cubes_clean(self._h, C.byref(m), C.byref(p), C.byref(out), C.byref(st)))
+        nv, nf = out.numVertices, out.numFaces
+        hp = np.zeros((nv, 3), np.float32); hc = np.zeros((nv, 3), np.float32); hf = np.zeros((nf, 3), np.uint32)
+        hn = np.zeros((nv, 3), np.float32) if normals else None
+        check(lib.bf_marching_cubes_download_clean(self._h, hp.ctypes.data_as(C.c_void_p), hc.ctypes.data_as(C.c_void_p), hn.ctypes.data_as(C.c_void_p) if normals else None,
+                                                   hf.ctypes.data_as(C.c_void_p)))
+        return hp, hc, hn, hf, st.as_dict()
+
+    def clean_labels(self, num_vertices):
+        """the component label of the first num_vertices input vertices of the last clean (uint32)"""
+        out = np.zeros(int(num_vertices), np.uint32)
+        check(lib.bf_marching_cubes_clean_labels(self._h, out.ctypes.data_as(C.c_void_p), len(out)))
+        return out
+
+    def save_mesh_clean(self, filename, transform=None, min_faces=0, largest=False, normals=False):
+        """weld of the last extraction + clean on the device + PLY (with normals: bf_write_ply_indexed_normals): the stats dict"""
+        p = MeshCleanParams(int(min_faces), int(bool(largest)), int(bool(normals))); st = MeshCleanStats()
+        T = mat16(transform) if transform is not None else None
+        check(lib.bf_marching_cubes_save_mesh_clean(self._h, str(filename).encode(), T, C.byref(p), C.byref(st)))
+        return st.as_dict()
+
+
 class IndexedMesh(C.Structure):
     _fields_ = [("d_positions", C.c_void_p), ("d_colors", C.c_void_p), ("d_faces", C.c_void_p), ("numVertices", C.c_uint32), ("numFaces", C.c_uint32)]
+
+
+class CleanMesh(C.Structure):
+    _fields_ = [("d_positions", C.c_void_p), ("d_colors", C.c_void_p), ("d_normals", C.c_void_p), ("d_faces", C.c_void_p), ("numVertices", C.c_uint32), ("numFaces", C.c_uint32)]
+
+
+class MeshCleanParams(C.Structure):
+    _fields_ = [("minComponentFaces", C.c_uint32), ("keepLargestOnly", C.c_int32), ("computeNormals", C.c_int32)]
+
+
+class MeshCleanStats(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("numVerticesIn", "numFacesIn", "numVerticesOut", "numFacesOut", "numComponents", "numComponentsKept", "numIsolatedVertices",
+                                          "largestComponentFaces")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+def mesh_clean_host(positions, colors, faces, min_faces=0, largest=False, normals=False):
+    """bf_mesh_clean_host, the definition on one core: (positions, colours, normals or None, faces, stats dict, labels).  Host-only."""
+    pos = np.ascontiguousarray(positions, np.float32).reshape(-1, 3); col = np.ascontiguousarray(colors, np.float32).reshape(-1, 3)
+    fc = np.ascontiguousarray(faces, np.uint32).reshape(-1, 3)
+    assert len(pos) == len(col)
+    p = MeshCleanParams(int(min_faces), int(bool(largest)), int(bool(normals))); st = MeshCleanStats()
+    op = np.zeros_like(pos); oc = np.zeros_like(col); on = np.zeros_like(pos); of = np.zeros_like(fc); lab = np.zeros(len(pos), np.uint32)
+    check(lib.bf_mesh_clean_host(pos.ctypes.data_as(C.c_void_p), col.ctypes.data_as(C.c_void_p), fc.ctypes.data_as(C.c_void_p), len(pos), len(fc), C.byref(p),
+                                 op.ctypes.data_as(C.c_void_p), oc.ctypes.data_as(C.c_void_p), on.ctypes.data_as(C.c_void_p), of.ctypes.data_as(C.c_void_p),
+                                 lab.ctypes.data_as(C.c_void_p), len(pos), len(fc), C.byref(st)))
+    nv, nf = st.numVerticesOut, st.numFacesOut
+    return op[:nv].copy(), oc[:nv].copy(), (on[:nv].copy() if normals else None), of[:nf].copy(), st.as_dict(), lab
+
+
+def write_ply_indexed_normals(filename, positions, normals, colors, faces):
+    """bf_write_ply_indexed_normals: the PLY of an indexed mesh with per-vertex normals ([nv,3] float32; None: the file of write_ply_indexed).  Host-only."""
+    pos = np.ascontiguousarray(positions, np.float32).reshape(-1, 3); col = np.ascontiguousarray(colors, np.float32).reshape(-1, 3)
+    fc = np.ascontiguousarray(faces, np.uint32).reshape(-1, 3)
+    nrm = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    assert len(pos) == len(col) and (nrm is None or len(nrm) == len(pos))
+    check(lib.bf_write_ply_indexed_normals(str(filename).encode(), pos.ctypes.data_as(C.c_void_p), None if nrm is None else nrm.ctypes.data_as(C.c_void_p),
+                                           col.ctypes.data_as(C.c_void_p), fc.ctypes.data_as(C.c_void_p), len(pos), len(fc)))
 
 
 def write_ply_indexed(filename, positions, colors, faces):

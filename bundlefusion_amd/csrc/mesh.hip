@@ -32,6 +32,7 @@
 #include "bf_device.h"
 #include "bf_resources.h"
 #include "bf_meshweld.h"
+#include "bf_meshclean.h"
 #include "bf_volume.h"
 
 using namespace bf;
@@ -312,7 +313,8 @@ struct bf_marching_cubes {
     uint32_t numTrianglesFound = 0;     // before clamping
     std::vector<bf_mc_triangle> mesh;   // m_meshData: triangles accumulated by copyTrianglesToCPU
     MeshWeld weld;                      // the indexed mesh of the last bf_marching_cubes_weld, in HBM (meshweld.hip)
-    bf::Resources res;                  // owns every buffer above, the weld's included
+    MeshClean clean;                    // the cleaned mesh of the last bf_marching_cubes_clean, in HBM (meshclean.hip)
+    bf::Resources res;                  // owns every buffer above, the weld's and the clean's included
 };
 
 extern "C" {
@@ -516,6 +518,48 @@ int bf_marching_cubes_save_mesh_gpu(bf_marching_cubes* m, const char* filename, 
     if (numVertices) *numVertices = im.numVertices;
     if (numFaces) *numFaces = im.numFaces;
     return BF_OK;
+}
+
+// Components, keep rule, compaction and normals over an indexed mesh in HBM (meshclean.hip); in null: the last weld.  On the object's stream.
+int bf_marching_cubes_clean(bf_marching_cubes* m, const bf_indexed_mesh* in, const bf_mesh_clean_params* params, bf_clean_mesh* out, bf_mesh_clean_stats* stats) {
+    BF_REQUIRE(m && params, "null argument");
+    bf_indexed_mesh last;
+    last.d_positions = m->weld.d_positions; last.d_colors = m->weld.d_colors; last.d_faces = m->weld.d_faces; last.numVertices = m->weld.numVertices; last.numFaces = m->weld.numFaces;
+    BF_TRY(meshclean_run(m->clean, m->res, m->stream, in ? *in : last, *params, stats));
+    const MeshClean& c = m->clean;
+    if (out) { out->d_positions = c.d_positions; out->d_colors = c.d_colors; out->d_normals = c.hasNormals ? c.d_normals : nullptr; out->d_faces = c.d_faces; out->numVertices = c.numVertices; out->numFaces = c.numFaces; }
+    return BF_OK;
+}
+
+int bf_marching_cubes_clean_labels(bf_marching_cubes* m, uint32_t* h_labels, uint32_t capacity) {
+    BF_REQUIRE(m && (h_labels || capacity == 0), "null argument");
+    const uint32_t n = std::min(capacity, m->clean.numVerticesIn);
+    if (n) BF_HIP_TRY(hipMemcpyAsync(h_labels, m->clean.d_label, 4 * (size_t)n, hipMemcpyDeviceToHost, m->stream));
+    BF_HIP_TRY(hipStreamSynchronize(m->stream));
+    return BF_OK;
+}
+
+int bf_marching_cubes_download_clean(bf_marching_cubes* m, float* h_positions, float* h_colors, float* h_normals, uint32_t* h_faces) {
+    BF_REQUIRE(m, "null argument");
+    const MeshClean& c = m->clean;
+    if (h_positions && c.numVertices) BF_HIP_TRY(hipMemcpyAsync(h_positions, c.d_positions, 12 * (size_t)c.numVertices, hipMemcpyDeviceToHost, m->stream));
+    if (h_colors && c.numVertices) BF_HIP_TRY(hipMemcpyAsync(h_colors, c.d_colors, 12 * (size_t)c.numVertices, hipMemcpyDeviceToHost, m->stream));
+    if (h_normals && c.hasNormals && c.numVertices) BF_HIP_TRY(hipMemcpyAsync(h_normals, c.d_normals, 12 * (size_t)c.numVertices, hipMemcpyDeviceToHost, m->stream));
+    if (h_faces && c.numFaces) BF_HIP_TRY(hipMemcpyAsync(h_faces, c.d_faces, 12 * (size_t)c.numFaces, hipMemcpyDeviceToHost, m->stream));
+    BF_HIP_TRY(hipStreamSynchronize(m->stream));
+    return BF_OK;
+}
+
+// weld of the last extraction + clean + download + the PLY writer; m_meshData is not touched
+int bf_marching_cubes_save_mesh_clean(bf_marching_cubes* m, const char* filename, const float transform[16], const bf_mesh_clean_params* params, bf_mesh_clean_stats* stats) {
+    BF_REQUIRE(m && filename && params, "null argument");
+    BF_TRY(bf_marching_cubes_weld(m, nullptr, 0, transform, nullptr));
+    bf_clean_mesh cm;
+    BF_TRY(bf_marching_cubes_clean(m, nullptr, params, &cm, stats));
+    std::vector<float> pos(3 * (size_t)cm.numVertices), col(3 * (size_t)cm.numVertices), nrm(cm.d_normals ? 3 * (size_t)cm.numVertices : 0);
+    std::vector<uint32_t> faces(3 * (size_t)cm.numFaces);
+    BF_TRY(bf_marching_cubes_download_clean(m, pos.data(), col.data(), nrm.data(), faces.data()));
+    return bf_write_ply_indexed_normals(filename, pos.data(), cm.d_normals ? nrm.data() : nullptr, col.data(), faces.data(), cm.numVertices, cm.numFaces);
 }
 
 }  // extern "C"

@@ -35,7 +35,8 @@ typedef enum bf_status {
     BF_ERR_NO_DEVICE = -3,     /* no gfx950 device / extension unusable          */
     BF_ERR_CAPACITY = -4,      /* a fixed-capacity buffer overflowed             */
     BF_ERR_STATE = -5,         /* call order violated (e.g. GC before compactify) */
-    BF_ERR_NOT_ON_DEVICE = -6  /* a valid input that only the host path handles (bf_jpeg_*): decode on the host instead */
+    BF_ERR_NOT_ON_DEVICE = -6, /* a valid input that only the host path handles (bf_jpeg_*): decode on the host instead */
+    BF_ERR_INTERNAL = -7       /* a bounded device loop ran out of steps (bf_marching_cubes_clean): a bug in the library, never a hung card */
 } bf_status;
 
 BF_API const char* bf_last_error(void);
@@ -712,6 +713,40 @@ BF_API int bf_marching_cubes_save_mesh_gpu(bf_marching_cubes* m, const char* fil
 /* the PLY writer of both routes (host only): binary little-endian, vertex = 3 floats + RGBA bytes ((uint8)max(0, min(255, c * 255.0f + 0.5f)), alpha 255),
  * face = count byte 3 + 3 int32 */
 BF_API int bf_write_ply_indexed(const char* filename, const float* h_positions, const float* h_colors, const uint32_t* h_faces, uint32_t numVertices, uint32_t numFaces);
+/* ---- MI355X additions: the indexed mesh cleaned in HBM (csrc/meshclean.hip; DESIGN.md "Mesh cleaning: the definition") ----
+ * Vertices that share a face are adjacent; a component is a connected set of vertices, its label its lowest vertex id, its size its number of faces; a vertex in
+ * no face is an isolated vertex (a component of size 0).  A component passes iff size >= max(1, minComponentFaces); with keepLargestOnly != 0 only the passing
+ * component of greatest size stays (equal sizes: the lowest label).  The output holds the vertices of the kept components in increasing old id, positions and
+ * colours copied bit for bit, and their faces in their old order and winding with the ids remapped.  computeNormals != 0: per output vertex the area-weighted
+ * normal - the faces' unnormalised cross products (P[b] - P[a]) x (P[c] - P[a]) summed once per corner in increasing corner number 3f + c, binary32 op by op,
+ * divided by its length sqrt((x*x + y*y) + z*z); (0, 0, 0) where the length is zero or not finite.  No result depends on the order in which threads run. */
+typedef struct bf_mesh_clean_params { uint32_t minComponentFaces; int32_t keepLargestOnly; int32_t computeNormals; } bf_mesh_clean_params;
+/* numComponents counts the components of size >= 1, largestComponentFaces is the greatest size among them (0 without faces) */
+typedef struct bf_mesh_clean_stats {
+    uint32_t numVerticesIn, numFacesIn, numVerticesOut, numFacesOut, numComponents, numComponentsKept, numIsolatedVertices, largestComponentFaces;
+} bf_mesh_clean_stats;
+/* the cleaned mesh in HBM: positions, colours and normals numVertices x 3 float (d_normals NULL without computeNormals), faces numFaces x 3 uint32; owned by the
+ * object, valid until its next extract, weld, clean or destroy */
+typedef struct bf_clean_mesh { const float* d_positions; const float* d_colors; const float* d_normals; const uint32_t* d_faces; uint32_t numVertices, numFaces; } bf_clean_mesh;
+/* Cleans the indexed mesh `in` (device arrays of any origin; NULL: the last weld) on the object's stream and waits for it twice (the refusal below, then the counts).  A face id
+ * >= numVertices or more than 300 000 000 faces: BF_ERR_INVALID_ARG, the last result stays as it was.  out and stats may be NULL. */
+BF_API int bf_marching_cubes_clean(bf_marching_cubes* m, const bf_indexed_mesh* in, const bf_mesh_clean_params* params, bf_clean_mesh* out, bf_mesh_clean_stats* stats);
+/* the component label of every INPUT vertex of the last clean (at most `capacity` of them), for tests and inspection */
+BF_API int bf_marching_cubes_clean_labels(bf_marching_cubes* m, uint32_t* h_labels, uint32_t capacity);
+/* host copies of the last clean's arrays (any of them may be NULL; h_normals is left alone where the clean computed none) */
+BF_API int bf_marching_cubes_download_clean(bf_marching_cubes* m, float* h_positions, float* h_colors, float* h_normals, uint32_t* h_faces);
+/* weld of the last extraction (with the transform, so normals are those of the transformed mesh) + clean + download + PLY: bf_write_ply_indexed_normals with
+ * computeNormals, bf_write_ply_indexed without; m_meshData is not touched */
+BF_API int bf_marching_cubes_save_mesh_clean(bf_marching_cubes* m, const char* filename, const float transform[16], const bf_mesh_clean_params* params, bf_mesh_clean_stats* stats);
+/* The definition on one core (needs no device): host arrays in, host arrays out.  h_labelsOut: numVertices labels; the other outputs hold up to vertexCapacity
+ * vertices / faceCapacity faces (BF_ERR_CAPACITY, with *stats filled in, where the result is larger; nothing but stats is written then).  Any output may be NULL. */
+BF_API int bf_mesh_clean_host(const float* h_positions, const float* h_colors, const uint32_t* h_faces, uint32_t numVertices, uint32_t numFaces, const bf_mesh_clean_params* params,
+                              float* h_positionsOut, float* h_colorsOut, float* h_normalsOut, uint32_t* h_facesOut, uint32_t* h_labelsOut, uint32_t vertexCapacity,
+                              uint32_t faceCapacity, bf_mesh_clean_stats* stats);
+/* the PLY of an indexed mesh with normals (host only): vertex = x y z nx ny nz float + RGBA bytes as in bf_write_ply_indexed (28 bytes, the field order of
+ * bf_write_ply_points), the same face records; h_normals NULL: exactly bf_write_ply_indexed */
+BF_API int bf_write_ply_indexed_normals(const char* filename, const float* h_positions, const float* h_normals, const float* h_colors, const uint32_t* h_faces, uint32_t numVertices,
+                                        uint32_t numFaces);
 /* the generated case tables (edge mask per case, up to 5 triangles of edge indices, -1 terminated), for inspection / tests */
 BF_API int bf_marching_cubes_tables(uint16_t edgeTable[256], int8_t triTable[256 * 16]);
 

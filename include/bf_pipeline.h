@@ -396,6 +396,11 @@ BF_API int bf_pipeline_synchronize(bf_pipeline* p);
  * on first use (thresholds of parametersFromGlobalAppState, factor 10) and sizes the triangle buffer to the volume: *numTriangles is the full count, never clamped.
  * transform: row-major 4x4 applied to the welded vertices, or NULL; the three counts may be NULL.  With a volume shard or a communicator set it is an error. */
 BF_API int bf_pipeline_save_mesh(bf_pipeline* p, const char* filename, const float* transform, uint32_t* numVertices, uint32_t* numFaces, uint32_t* numTriangles);
+/* The same command with bf_marching_cubes_clean between the weld and the file (bf_marching_cubes_save_mesh_clean; bf_hip.h has the definition): small
+ * components dropped, optionally only the largest kept, optionally per-vertex normals in the file.  stats->numFacesIn is bf_pipeline_save_mesh's face count for
+ * the same state.  params must not be NULL; stats and numTriangles may be.  The same refusal for a sharded volume; the reconstruction is left alone. */
+BF_API int bf_pipeline_save_mesh_clean(bf_pipeline* p, const char* filename, const float* transform, const bf_mesh_clean_params* params, bf_mesh_clean_stats* stats,
+                                       uint32_t* numTriangles);
 BF_API int bf_pipeline_get_scene(bf_pipeline* p, bf_scene** out);
 BF_API int bf_pipeline_get_image_manager(bf_pipeline* p, bf_image_manager** out);
 BF_API int bf_pipeline_get_online_bundler(bf_pipeline* p, bf_online_bundler** out);

@@ -807,6 +807,11 @@ public:
         if (numVertices) *numVertices = nv;
         if (numFaces) *numFaces = nf;
     }
+    // saveMeshGPU with the welded mesh cleaned on the device before the file is written (bf_marching_cubes_clean): components below minComponentFaces faces and
+    // vertices no face uses are dropped, keepLargestOnly keeps the largest component only, computeNormals adds per-vertex normals to the PLY.
+    void saveMeshClean(const std::string& filename, const bf_mesh_clean_params& params, const mat4f* transform = nullptr, bf_mesh_clean_stats* stats = nullptr) {
+        check(bf_marching_cubes_save_mesh_clean(m_h, filename.c_str(), transform ? transform->m : nullptr, &params, stats));
+    }
     bf_marching_cubes* handle() const { return m_h; }
 private:
     MarchingCubesParams m_params;

@@ -1,6 +1,7 @@
 """--mesh / --mesh-host of tools/run_sens.py and tools/run_sequence.py: the scan's PLY after the end of the sequence, by the frame loop's own command
 (bf_pipeline_save_mesh: extraction and weld on the device) or by the host route (bf_marching_cubes_extract + bf_marching_cubes_save_mesh), with the counts
-and the seconds of each so that the two can be put side by side."""
+and the seconds of each so that the two can be put side by side.  --mesh-min-faces / --mesh-largest / --mesh-normals clean the mesh before it is written
+(bf_pipeline_save_mesh_clean on the device route, bf_mesh_clean_host on the host route) and print the cleaning's stats."""
 import ctypes as C
 import time
 
@@ -12,9 +13,22 @@ import bundlefusion_amd as bf
 def add_arguments(ap):
     ap.add_argument("--mesh", default=None, metavar="PATH", help="write the mesh as a PLY after the end of the sequence (bf_pipeline_save_mesh: welded on the device)")
     ap.add_argument("--mesh-host", default=None, metavar="PATH", help="the same file by the host route (extract + save_mesh on one core), for comparison")
+    ap.add_argument("--mesh-min-faces", type=int, default=0, metavar="N", help="drop connected pieces of the mesh with fewer than N faces, and vertices no face uses")
+    ap.add_argument("--mesh-largest", action="store_true", help="keep only the largest connected piece of the mesh")
+    ap.add_argument("--mesh-normals", action="store_true", help="write area-weighted per-vertex normals into the PLY")
 
 
-def _device_stages(p, path):
+def _cleaning(a):
+    return a.mesh_min_faces > 0 or a.mesh_largest or a.mesh_normals
+
+
+def _stats_line(st):
+    return ("%d -> %d vertices, %d -> %d faces; %d components, %d kept, largest %d faces, %d isolated vertices"
+            % (st["numVerticesIn"], st["numVerticesOut"], st["numFacesIn"], st["numFacesOut"], st["numComponents"], st["numComponentsKept"], st["largestComponentFaces"],
+               st["numIsolatedVertices"]))
+
+
+def _device_stages(p, path, a):
     """the stages of the device route one by one, on an object of their own over the pipeline's scene (the same file again)"""
     lib, check = bf.capi.lib, bf.capi.check
     mc = bf.capi.MarchingCubesHashSDF.from_global_app_state(p.gas)
@@ -25,15 +39,28 @@ def _device_stages(p, path):
     m = bf.capi.IndexedMesh()
     check(lib.bf_marching_cubes_weld(mc._h, None, 0, None, C.byref(m)))          # (waits for its stream)
     t2 = time.perf_counter()
-    pos = np.empty((m.numVertices, 3), np.float32); col = np.empty((m.numVertices, 3), np.float32); faces = np.empty((m.numFaces, 3), np.uint32)
-    check(lib.bf_marching_cubes_download_indexed(mc._h, pos.ctypes.data_as(C.c_void_p), col.ctypes.data_as(C.c_void_p), faces.ctypes.data_as(C.c_void_p)))
-    bf.capi.write_ply_indexed(path, pos, col, faces)
-    t3 = time.perf_counter()
+    if not _cleaning(a):
+        pos = np.empty((m.numVertices, 3), np.float32); col = np.empty((m.numVertices, 3), np.float32); faces = np.empty((m.numFaces, 3), np.uint32)
+        check(lib.bf_marching_cubes_download_indexed(mc._h, pos.ctypes.data_as(C.c_void_p), col.ctypes.data_as(C.c_void_p), faces.ctypes.data_as(C.c_void_p)))
+        bf.capi.write_ply_indexed(path, pos, col, faces)
+        t3 = time.perf_counter()
+        print("mesh (device route, stage by stage): extract %.4f s, weld %.4f s, download + write %.4f s" % (t1 - t0, t2 - t1, t3 - t2))
+    else:
+        prm = bf.capi.MeshCleanParams(a.mesh_min_faces, int(a.mesh_largest), int(a.mesh_normals)); cm = bf.capi.CleanMesh(); st = bf.capi.MeshCleanStats()
+        check(lib.bf_marching_cubes_clean(mc._h, None, C.byref(prm), C.byref(cm), C.byref(st)))
+        check(lib.bf_marching_cubes_clean_labels(mc._h, None, 0))                # waits for the object's stream: the clean's last kernels have ended
+        t3 = time.perf_counter()
+        pos = np.empty((cm.numVertices, 3), np.float32); col = np.empty((cm.numVertices, 3), np.float32); faces = np.empty((cm.numFaces, 3), np.uint32)
+        nrm = np.empty((cm.numVertices, 3), np.float32) if a.mesh_normals else None
+        check(lib.bf_marching_cubes_download_clean(mc._h, pos.ctypes.data_as(C.c_void_p), col.ctypes.data_as(C.c_void_p), nrm.ctypes.data_as(C.c_void_p) if a.mesh_normals else None,
+                                                   faces.ctypes.data_as(C.c_void_p)))
+        bf.capi.write_ply_indexed_normals(path, pos, nrm, col, faces)
+        t4 = time.perf_counter()
+        print("mesh (device route, stage by stage): extract %.4f s, weld %.4f s, clean %.4f s, download + write %.4f s" % (t1 - t0, t2 - t1, t3 - t2, t4 - t3))
     mc.close()
-    print("mesh (device route, stage by stage): extract %.4f s, weld %.4f s, download + write %.4f s" % (t1 - t0, t2 - t1, t3 - t2))
 
 
-def _host(p, path):
+def _host(p, path, a):
     sc = p.scene()
     cap = 3000000                                            # s_marchingCubesMaxNumTriangles; a host has to guess, and to ask again if the volume holds more
     while True:
@@ -46,17 +73,30 @@ def _host(p, path):
         mc.close(); cap = found
     nv, nf = mc.save_mesh(path)
     t2 = time.perf_counter()
-    mc.close()
     print("mesh (host route) %s: %d vertices, %d faces, %d triangles; extract + copy %.3f s, weld + write %.3f s, total %.3f s" % (path, nv, nf, found, t1 - t0, t2 - t1, t2 - t0))
+    if _cleaning(a):
+        pos, col, faces = mc.weld()                          # the arrays of the host weld (the device weld of the same extraction holds the same bits)
+        t3 = time.perf_counter()
+        cp, cc, cn, cf, st, _ = bf.capi.mesh_clean_host(pos, col, faces, a.mesh_min_faces, a.mesh_largest, a.mesh_normals)
+        t4 = time.perf_counter()
+        bf.capi.write_ply_indexed_normals(path, cp, cn, cc, cf)
+        t5 = time.perf_counter()
+        print("mesh (host route) cleaned on one core: %s; clean %.3f s, write %.3f s" % (_stats_line(st), t4 - t3, t5 - t4))
+    mc.close()
 
 
 def write(p, a):
     """p: the Pipeline after process_end_of_sequence / synchronize; a: the parsed arguments"""
     if a.mesh:
         t0 = time.perf_counter()
-        nv, nf, nt = p.save_mesh(a.mesh)
-        dt = time.perf_counter() - t0
-        print("mesh (device route) %s: %d vertices, %d faces, %d triangles; bf_pipeline_save_mesh %.3f s" % (a.mesh, nv, nf, nt, dt))
-        _device_stages(p, a.mesh)
+        if _cleaning(a):
+            st, nt = p.save_mesh_clean(a.mesh, None, a.mesh_min_faces, a.mesh_largest, a.mesh_normals)
+            dt = time.perf_counter() - t0
+            print("mesh (device route) %s: %d triangles; %s; bf_pipeline_save_mesh_clean %.3f s" % (a.mesh, nt, _stats_line(st), dt))
+        else:
+            nv, nf, nt = p.save_mesh(a.mesh)
+            dt = time.perf_counter() - t0
+            print("mesh (device route) %s: %d vertices, %d faces, %d triangles; bf_pipeline_save_mesh %.3f s" % (a.mesh, nv, nf, nt, dt))
+        _device_stages(p, a.mesh, a)
     if a.mesh_host:
-        _host(p, a.mesh_host)
+        _host(p, a.mesh_host, a)

@@ -5,6 +5,9 @@ usage: python tools/run_sens.py sequence.sens [--voxel 0.01] [--app zParametersD
                                 [--ingest host|device] [--decode-threads N] [--camera-calibration] [--mesh scan.ply] [--mesh-host scan_host.ply]
 --mesh: the scan's mesh after the end of the sequence, extracted and welded on the device (bf_pipeline_save_mesh); --mesh-host: the same file by the host route
 (bf_marching_cubes_extract + bf_marching_cubes_save_mesh).  Both print the vertex, face and triangle counts and the seconds spent.
+--mesh-min-faces N / --mesh-largest / --mesh-normals: clean the mesh before it is written - connected pieces below N faces and unused vertices dropped, only the
+largest piece kept, per-vertex normals added to the PLY - on the device with --mesh (bf_pipeline_save_mesh_clean), on one core with --mesh-host
+(bf_mesh_clean_host); both print the cleaning's stats.
 --point-cloud FILE [--point-cloud-stride N --point-cloud-cell M]: the stored frames on the stride (default s_submapSize: the key frames) under the optimised
 trajectory as a coloured, oriented point cloud, one point per cell of M metres (default 0.005), thinned on the device (bf_pipeline_save_point_cloud);
 --point-cloud-host FILE: the same file by the host route on one core.  Both print frame and point counts and the seconds spent.
