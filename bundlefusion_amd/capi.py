@@ -1453,6 +1453,15 @@ class Pipeline:
         check(lib.bf_pipeline_save_mesh_clean(self._h, str(filename).encode(), T, C.byref(p), C.byref(st), C.byref(nt)))
         return st.as_dict(), nt.value
 
+    def save_mesh_simplified(self, filename, cell_size, transform=None, min_faces=0, largest=False, normals=False):
+        """bf_pipeline_save_mesh_simplified: save_mesh_clean with the cleaned mesh's vertices clustered on a grid of cell_size metres on the device before the file
+        is written.  Returns (clean stats dict, simplify stats dict, triangles)."""
+        p = MeshCleanParams(int(min_faces), int(bool(largest)), int(bool(normals))); sp = MeshSimplifyParams(float(cell_size), int(bool(normals)))
+        st = MeshCleanStats(); sst = MeshSimplifyStats(); nt = C.c_uint32()
+        T = mat16(transform) if transform is not None else None
+        check(lib.bf_pipeline_save_mesh_simplified(self._h, str(filename).encode(), T, C.byref(p), C.byref(sp), C.byref(st), C.byref(sst), C.byref(nt)))
+        return st.as_dict(), sst.as_dict(), nt.value
+
     def save_point_cloud(self, filename, frame_stride=None, cell_size=0.005, max_depth=3.5, max_points=0):
         """bf_pipeline_save_point_cloud: the stored frames on the stride under the optimised trajectory as a thinned point cloud PLY, built on the device.
         frame_stride None: s_submapSize (the key frames).  Returns (points, frames used)."""
@@ -1701,6 +1710,43 @@ class MarchingCubesHashSDF:
         check(lib.bf_marching_cubes_save_mesh_clean(self._h, str(filename).encode(), T, C.byref(p), C.byref(st)))
         return st.as_dict()
 
+    # ---- MI355X additions: the indexed mesh simplified in HBM by vertex clustering (csrc/meshsimplify.hip)
+    def simplify(self, mesh=None, cell_size=0.01, normals=False):
+        """bf_marching_cubes_simplify + download: (positions, colours, normals or None, faces, stats dict).  mesh: (positions [nv,3] float32, colours [nv,3] float32,
+        faces [nf,3] uint32) as contiguous torch cuda tensors, or None for the result of the last clean."""
+        p = MeshSimplifyParams(float(cell_size), int(bool(normals)))
+        out = CleanMesh(); st = MeshSimplifyStats()
+        if mesh is None:
+            check(lib.bf_marching_cubes_simplify(self._h, None, C.byref(p), C.byref(out), C.byref(st)))
+        else:
+            pos, col, faces = mesh
+            assert pos.is_contiguous() and col.is_contiguous() and faces.is_contiguous() and pos.numel() == col.numel() and pos.numel() % 3 == 0 and faces.numel() % 3 == 0
+            m = IndexedMesh(pos.data_ptr() or None, col.data_ptr() or None, faces.data_ptr() or None, pos.numel() // 3, faces.numel() // 3)
+            check(lib.bf_marching_cubes_simplify(self._h, C.byref(m), C.byref(p), C.byref(out), C.byref(st)))
+        return self.download_simplified(out.numVertices, out.numFaces, normals) + (st.as_dict(),)
+
+    def download_simplified(self, nv, nf, normals=False):
+        """bf_marching_cubes_download_simplified: (positions, colours, normals or None, faces) of the last simplify, whose counts the caller knows"""
+        hp = np.zeros((nv, 3), np.float32); hc = np.zeros((nv, 3), np.float32); hf = np.zeros((nf, 3), np.uint32)
+        hn = np.zeros((nv, 3), np.float32) if normals else None
+        check(lib.bf_marching_cubes_download_simplified(self._h, hp.ctypes.data_as(C.c_void_p), hc.ctypes.data_as(C.c_void_p), hn.ctypes.data_as(C.c_void_p) if normals else None,
+                                                        hf.ctypes.data_as(C.c_void_p)))
+        return hp, hc, hn, hf
+
+    def simplify_map(self, num_vertices):
+        """per input vertex of the last simplify (the first num_vertices of them) its output id, or 0xFFFFFFFF where its cluster is not in the output (uint32)"""
+        out = np.zeros(int(num_vertices), np.uint32)
+        check(lib.bf_marching_cubes_simplify_map(self._h, out.ctypes.data_as(C.c_void_p), len(out)))
+        return out
+
+    def save_mesh_simplified(self, filename, cell_size, transform=None, min_faces=0, largest=False, normals=False):
+        """weld of the last extraction + clean + simplify on the device + PLY (with normals: bf_write_ply_indexed_normals): (clean stats dict, simplify stats dict)"""
+        p = MeshCleanParams(int(min_faces), int(bool(largest)), int(bool(normals))); sp = MeshSimplifyParams(float(cell_size), int(bool(normals)))
+        st = MeshCleanStats(); sst = MeshSimplifyStats()
+        T = mat16(transform) if transform is not None else None
+        check(lib.bf_marching_cubes_save_mesh_simplified(self._h, str(filename).encode(), T, C.byref(p), C.byref(sp), C.byref(st), C.byref(sst)))
+        return st.as_dict(), sst.as_dict()
+
 
 class IndexedMesh(C.Structure):
     _fields_ = [("d_positions", C.c_void_p), ("d_colors", C.c_void_p), ("d_faces", C.c_void_p), ("numVertices", C.c_uint32), ("numFaces", C.c_uint32)]
@@ -1720,6 +1766,31 @@ class MeshCleanStats(C.Structure):
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class MeshSimplifyParams(C.Structure):
+    _fields_ = [("cellSize", C.c_float), ("computeNormals", C.c_int32)]
+
+
+class MeshSimplifyStats(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("numVerticesIn", "numFacesIn", "numClusters", "numVerticesOut", "numFacesOut", "numFacesCollapsed", "numFacesDuplicate", "largestCluster")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+def mesh_simplify_host(positions, colors, faces, cell_size, normals=False):
+    """bf_mesh_simplify_host, the definition on one core: (positions, colours, normals or None, faces, stats dict, map).  Host-only."""
+    pos = np.ascontiguousarray(positions, np.float32).reshape(-1, 3); col = np.ascontiguousarray(colors, np.float32).reshape(-1, 3)
+    fc = np.ascontiguousarray(faces, np.uint32).reshape(-1, 3)
+    assert len(pos) == len(col)
+    p = MeshSimplifyParams(float(cell_size), int(bool(normals))); st = MeshSimplifyStats()
+    op = np.zeros_like(pos); oc = np.zeros_like(col); on = np.zeros_like(pos); of = np.zeros_like(fc); mp = np.zeros(len(pos), np.uint32)
+    check(lib.bf_mesh_simplify_host(pos.ctypes.data_as(C.c_void_p), col.ctypes.data_as(C.c_void_p), fc.ctypes.data_as(C.c_void_p), len(pos), len(fc), C.byref(p),
+                                    op.ctypes.data_as(C.c_void_p), oc.ctypes.data_as(C.c_void_p), on.ctypes.data_as(C.c_void_p), of.ctypes.data_as(C.c_void_p),
+                                    mp.ctypes.data_as(C.c_void_p), len(pos), len(fc), C.byref(st)))
+    nv, nf = st.numVerticesOut, st.numFacesOut
+    return op[:nv].copy(), oc[:nv].copy(), (on[:nv].copy() if normals else None), of[:nf].copy(), st.as_dict(), mp
 
 
 def mesh_clean_host(positions, colors, faces, min_faces=0, largest=False, normals=False):

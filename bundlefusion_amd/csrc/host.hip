@@ -2572,7 +2572,11 @@ int bf_pipeline_render_top_down(bf_pipeline* p, uint8_t* h_out) {
 // ---- the mesh: StopScanningAndExtractIsoSurfaceMC (DepthSensing.cpp:335-368) from inside the frame loop, welded on the device
 namespace {
 
-struct PlMeshJob { bf_pipeline* p; const char* filename; const float* transform; uint32_t nv, nf, nt; const bf_mesh_clean_params* clean; bf_mesh_clean_stats* stats; };      // clean null: the plain save
+// clean null: the plain save; simplify non-null (with clean): the simplified save
+struct PlMeshJob {
+    bf_pipeline* p; const char* filename; const float* transform; uint32_t nv, nf, nt; const bf_mesh_clean_params* clean; bf_mesh_clean_stats* stats;
+    const bf_mesh_simplify_params* simplify; bf_mesh_simplify_stats* simplifyStats;
+};
 
 // on the volume thread (timings: on the calling thread), between two batches.  The view's exclusive section is a render's: the preparation stream has finished
 // and starts nothing until the section ends, and the last rigid transform, the block lists and the heap are what they were - marching cubes reads the hash slots
@@ -2585,15 +2589,16 @@ int plMeshExec(void* ctx) {
     BF_TRY(bf_scene_begin_view(p->scene, I, &p->cam, &hd, &hp));
     int rc = bf_marching_cubes_extract_gpu(p->marchingCubes, &hd, &hp, nullptr, nullptr, 0);
     if (rc == BF_OK) rc = bf_marching_cubes_get_triangles_gpu(p->marchingCubes, nullptr, nullptr, &j.nt);
-    if (rc == BF_OK) rc = j.clean ? bf_marching_cubes_save_mesh_clean(p->marchingCubes, j.filename, j.transform, j.clean, j.stats)
-                                  : bf_marching_cubes_save_mesh_gpu(p->marchingCubes, j.filename, j.transform, &j.nv, &j.nf);          // waits for the volume stream
+    if (rc == BF_OK) rc = j.simplify ? bf_marching_cubes_save_mesh_simplified(p->marchingCubes, j.filename, j.transform, j.clean, j.simplify, j.stats, j.simplifyStats)
+                        : j.clean  ? bf_marching_cubes_save_mesh_clean(p->marchingCubes, j.filename, j.transform, j.clean, j.stats)
+                                   : bf_marching_cubes_save_mesh_gpu(p->marchingCubes, j.filename, j.transform, &j.nv, &j.nf);          // waits for the volume stream
     const int rc2 = bf_scene_end_view(p->scene);
     return rc != BF_OK ? rc : rc2;
 }
 
 }  // namespace
 
-// both saves: the command, with the marching-cubes object created on first use
+// the three saves: the command, with the marching-cubes object created on first use
 static int plSaveMesh(bf_pipeline* p, PlMeshJob& j) {
     BF_REQUIRE(!p->volumeSharded && !p->volumeComm, "the volume is sharded over ranks (bf_pipeline_set_volume_shard / _set_comm): a shard lacks its neighbours' blocks, meshing across ranks is not supported");
     BF_TRY(plFlush(p));          // every frame handed in so far reaches the volume before the mesh is taken
@@ -2606,13 +2611,13 @@ static int plSaveMesh(bf_pipeline* p, PlMeshJob& j) {
         BF_TRY(bf_marching_cubes_set_stream(p->marchingCubes, p->sVolume));
     }
     VolumeQueue::Cmd c;
-    c.op = VolumeQueue::Op::SaveMesh; c.render = plMeshExec; c.renderCtx = &j;
+    c.op = j.simplify ? VolumeQueue::Op::SaveMeshSimplified : VolumeQueue::Op::SaveMesh; c.render = plMeshExec; c.renderCtx = &j;
     return p->vol.postAndWait(c);
 }
 
 int bf_pipeline_save_mesh(bf_pipeline* p, const char* filename, const float* transform, uint32_t* numVertices, uint32_t* numFaces, uint32_t* numTriangles) {
     BF_REQUIRE(p && filename, "null argument");
-    PlMeshJob j = {p, filename, transform, 0, 0, 0, nullptr, nullptr};
+    PlMeshJob j = {p, filename, transform, 0, 0, 0, nullptr, nullptr, nullptr, nullptr};
     BF_TRY(plSaveMesh(p, j));
     if (numVertices) *numVertices = j.nv;
     if (numFaces) *numFaces = j.nf;
@@ -2623,7 +2628,17 @@ int bf_pipeline_save_mesh(bf_pipeline* p, const char* filename, const float* tra
 // the same command with bf_marching_cubes_clean between the weld and the file
 int bf_pipeline_save_mesh_clean(bf_pipeline* p, const char* filename, const float* transform, const bf_mesh_clean_params* params, bf_mesh_clean_stats* stats, uint32_t* numTriangles) {
     BF_REQUIRE(p && filename && params, "null argument");
-    PlMeshJob j = {p, filename, transform, 0, 0, 0, params, stats};
+    PlMeshJob j = {p, filename, transform, 0, 0, 0, params, stats, nullptr, nullptr};
+    BF_TRY(plSaveMesh(p, j));
+    if (numTriangles) *numTriangles = j.nt;
+    return BF_OK;
+}
+
+// ... and with bf_marching_cubes_simplify behind the clean (bf_marching_cubes_save_mesh_simplified)
+int bf_pipeline_save_mesh_simplified(bf_pipeline* p, const char* filename, const float* transform, const bf_mesh_clean_params* cleanParams, const bf_mesh_simplify_params* simplifyParams,
+                                     bf_mesh_clean_stats* cleanStats, bf_mesh_simplify_stats* simplifyStats, uint32_t* numTriangles) {
+    BF_REQUIRE(p && filename && cleanParams && simplifyParams, "null argument");
+    PlMeshJob j = {p, filename, transform, 0, 0, 0, cleanParams, cleanStats, simplifyParams, simplifyStats};
     BF_TRY(plSaveMesh(p, j));
     if (numTriangles) *numTriangles = j.nt;
     return BF_OK;

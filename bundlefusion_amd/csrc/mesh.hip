@@ -33,6 +33,7 @@
 #include "bf_resources.h"
 #include "bf_meshweld.h"
 #include "bf_meshclean.h"
+#include "bf_meshsimplify.h"
 #include "bf_volume.h"
 
 using namespace bf;
@@ -314,7 +315,8 @@ struct bf_marching_cubes {
     std::vector<bf_mc_triangle> mesh;   // m_meshData: triangles accumulated by copyTrianglesToCPU
     MeshWeld weld;                      // the indexed mesh of the last bf_marching_cubes_weld, in HBM (meshweld.hip)
     MeshClean clean;                    // the cleaned mesh of the last bf_marching_cubes_clean, in HBM (meshclean.hip)
-    bf::Resources res;                  // owns every buffer above, the weld's and the clean's included
+    MeshSimplify simplify;              // the simplified mesh of the last bf_marching_cubes_simplify, in HBM (meshsimplify.hip)
+    bf::Resources res;                  // owns every buffer above, the weld's, the clean's and the simplification's included
 };
 
 extern "C" {
@@ -527,7 +529,7 @@ int bf_marching_cubes_clean(bf_marching_cubes* m, const bf_indexed_mesh* in, con
     last.d_positions = m->weld.d_positions; last.d_colors = m->weld.d_colors; last.d_faces = m->weld.d_faces; last.numVertices = m->weld.numVertices; last.numFaces = m->weld.numFaces;
     BF_TRY(meshclean_run(m->clean, m->res, m->stream, in ? *in : last, *params, stats));
     const MeshClean& c = m->clean;
-    if (out) { out->d_positions = c.d_positions; out->d_colors = c.d_colors; out->d_normals = c.hasNormals ? c.d_normals : nullptr; out->d_faces = c.d_faces; out->numVertices = c.numVertices; out->numFaces = c.numFaces; }
+    if (out) { out->d_positions = c.d_positions; out->d_colors = c.d_colors; out->d_normals = c.hasNormals ? c.normals.d_normals : nullptr; out->d_faces = c.d_faces; out->numVertices = c.numVertices; out->numFaces = c.numFaces; }
     return BF_OK;
 }
 
@@ -544,7 +546,7 @@ int bf_marching_cubes_download_clean(bf_marching_cubes* m, float* h_positions, f
     const MeshClean& c = m->clean;
     if (h_positions && c.numVertices) BF_HIP_TRY(hipMemcpyAsync(h_positions, c.d_positions, 12 * (size_t)c.numVertices, hipMemcpyDeviceToHost, m->stream));
     if (h_colors && c.numVertices) BF_HIP_TRY(hipMemcpyAsync(h_colors, c.d_colors, 12 * (size_t)c.numVertices, hipMemcpyDeviceToHost, m->stream));
-    if (h_normals && c.hasNormals && c.numVertices) BF_HIP_TRY(hipMemcpyAsync(h_normals, c.d_normals, 12 * (size_t)c.numVertices, hipMemcpyDeviceToHost, m->stream));
+    if (h_normals && c.hasNormals && c.numVertices) BF_HIP_TRY(hipMemcpyAsync(h_normals, c.normals.d_normals, 12 * (size_t)c.numVertices, hipMemcpyDeviceToHost, m->stream));
     if (h_faces && c.numFaces) BF_HIP_TRY(hipMemcpyAsync(h_faces, c.d_faces, 12 * (size_t)c.numFaces, hipMemcpyDeviceToHost, m->stream));
     BF_HIP_TRY(hipStreamSynchronize(m->stream));
     return BF_OK;
@@ -560,6 +562,55 @@ int bf_marching_cubes_save_mesh_clean(bf_marching_cubes* m, const char* filename
     std::vector<uint32_t> faces(3 * (size_t)cm.numFaces);
     BF_TRY(bf_marching_cubes_download_clean(m, pos.data(), col.data(), nrm.data(), faces.data()));
     return bf_write_ply_indexed_normals(filename, pos.data(), cm.d_normals ? nrm.data() : nullptr, col.data(), faces.data(), cm.numVertices, cm.numFaces);
+}
+
+// Vertex clustering over an indexed mesh in HBM (meshsimplify.hip); in null: the last clean's result.  On the object's stream.
+int bf_marching_cubes_simplify(bf_marching_cubes* m, const bf_indexed_mesh* in, const bf_mesh_simplify_params* params, bf_clean_mesh* out, bf_mesh_simplify_stats* stats) {
+    BF_REQUIRE(m && params, "null argument");
+    BF_REQUIRE(in || m->clean.hasResult, "no input mesh and no result of a clean to take");
+    bf_indexed_mesh last;
+    last.d_positions = m->clean.d_positions; last.d_colors = m->clean.d_colors; last.d_faces = m->clean.d_faces; last.numVertices = m->clean.numVertices; last.numFaces = m->clean.numFaces;
+    BF_TRY(meshsimplify_run(m->simplify, m->res, m->stream, in ? *in : last, *params, stats));
+    const MeshSimplify& s = m->simplify;
+    if (out) { out->d_positions = s.d_positions; out->d_colors = s.d_colors; out->d_normals = s.hasNormals ? s.normals.d_normals : nullptr; out->d_faces = s.d_faces; out->numVertices = s.numVertices; out->numFaces = s.numFaces; }
+    return BF_OK;
+}
+
+int bf_marching_cubes_simplify_map(bf_marching_cubes* m, uint32_t* h_map, uint32_t capacity) {
+    BF_REQUIRE(m && (h_map || capacity == 0), "null argument");
+    const uint32_t n = std::min(capacity, m->simplify.numVerticesIn);
+    if (n) BF_HIP_TRY(hipMemcpyAsync(h_map, m->simplify.d_map, 4 * (size_t)n, hipMemcpyDeviceToHost, m->stream));
+    BF_HIP_TRY(hipStreamSynchronize(m->stream));
+    return BF_OK;
+}
+
+int bf_marching_cubes_download_simplified(bf_marching_cubes* m, float* h_positions, float* h_colors, float* h_normals, uint32_t* h_faces) {
+    BF_REQUIRE(m, "null argument");
+    const MeshSimplify& s = m->simplify;
+    if (h_positions && s.numVertices) BF_HIP_TRY(hipMemcpyAsync(h_positions, s.d_positions, 12 * (size_t)s.numVertices, hipMemcpyDeviceToHost, m->stream));
+    if (h_colors && s.numVertices) BF_HIP_TRY(hipMemcpyAsync(h_colors, s.d_colors, 12 * (size_t)s.numVertices, hipMemcpyDeviceToHost, m->stream));
+    if (h_normals && s.hasNormals && s.numVertices) BF_HIP_TRY(hipMemcpyAsync(h_normals, s.normals.d_normals, 12 * (size_t)s.numVertices, hipMemcpyDeviceToHost, m->stream));
+    if (h_faces && s.numFaces) BF_HIP_TRY(hipMemcpyAsync(h_faces, s.d_faces, 12 * (size_t)s.numFaces, hipMemcpyDeviceToHost, m->stream));
+    BF_HIP_TRY(hipStreamSynchronize(m->stream));
+    return BF_OK;
+}
+
+// weld of the last extraction + clean (without its normals) + simplify + download + the PLY writer; m_meshData is not touched
+int bf_marching_cubes_save_mesh_simplified(bf_marching_cubes* m, const char* filename, const float transform[16], const bf_mesh_clean_params* cleanParams,
+                                           const bf_mesh_simplify_params* simplifyParams, bf_mesh_clean_stats* cleanStats, bf_mesh_simplify_stats* simplifyStats) {
+    BF_REQUIRE(m && filename && cleanParams && simplifyParams, "null argument");
+    bf_mesh_clean_params cp = *cleanParams;
+    bf_mesh_simplify_params sp = *simplifyParams;
+    sp.computeNormals = (cp.computeNormals || sp.computeNormals) ? 1 : 0;          // once, on the mesh that is written
+    cp.computeNormals = 0;
+    BF_TRY(bf_marching_cubes_weld(m, nullptr, 0, transform, nullptr));
+    BF_TRY(bf_marching_cubes_clean(m, nullptr, &cp, nullptr, cleanStats));
+    bf_clean_mesh sm;
+    BF_TRY(bf_marching_cubes_simplify(m, nullptr, &sp, &sm, simplifyStats));
+    std::vector<float> pos(3 * (size_t)sm.numVertices), col(3 * (size_t)sm.numVertices), nrm(sm.d_normals ? 3 * (size_t)sm.numVertices : 0);
+    std::vector<uint32_t> faces(3 * (size_t)sm.numFaces);
+    BF_TRY(bf_marching_cubes_download_simplified(m, pos.data(), col.data(), nrm.data(), faces.data()));
+    return bf_write_ply_indexed_normals(filename, pos.data(), sm.d_normals ? nrm.data() : nullptr, col.data(), faces.data(), sm.numVertices, sm.numFaces);
 }
 
 }  // extern "C"

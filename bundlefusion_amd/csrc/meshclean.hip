@@ -20,6 +20,7 @@
 // workgroup, scatter.  The normals' vertex-to-corner incidence is in CSR form: integer degree count, an exclusive scan of the degrees (tile sums, the same scan of
 // the tile sums, a scan inside every tile), an atomic-cursor fill in whatever order, and the defined order restored per segment: a segment of at most 64 corners is
 // walked by one thread that picks the next higher corner number each time; a longer one is rank-sorted and then summed by one wave, 64 face normals at a time.
+// The normal pass is a function of its own (meshnormals_run, and meshnormals_host for the one-core route): the simplification (meshsimplify.hip) calls it too.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -43,7 +44,7 @@ constexpr uint32_t SHORT_SEGMENT = 64;          // corners of a vertex one threa
 constexpr uint32_t NO_CORNER = 0xFFFFFFFFu;
 
 // the control words (uint32, zeroed by k_clean_init)
-enum : uint32_t { W_ERR = 0, W_NV_OUT = 1, W_NF_OUT = 2, W_COMPONENTS = 3, W_PASSING = 4, W_ISOLATED = 5, W_LARGEST = 6, W_NUM_LONG = 7, W_BEST = 8 /* 64 bits */, NUM_WORDS = 16 };
+enum : uint32_t { W_ERR = 0, W_NV_OUT = 1, W_NF_OUT = 2, W_COMPONENTS = 3, W_PASSING = 4, W_ISOLATED = 5, W_LARGEST = 6, W_BEST = 8 /* 64 bits */, NUM_WORDS = 16 };
 constexpr uint32_t ERR_FACE_ID = 1u, ERR_LOOP = 2u;
 
 // ---- the arithmetic of the normals, shared by the kernels and bf_mesh_clean_host (the library is built without contraction: one rounding per operation)
@@ -303,11 +304,11 @@ __global__ __launch_bounds__(256) void k_clean_corner_fill(const uint32_t* __res
 // one thread per vertex: a short segment is summed in increasing corner number by picking the lowest corner above the last one each time; a long one is listed
 __global__ __launch_bounds__(256) void k_clean_normals_short(const float* __restrict__ P, const uint32_t* __restrict__ faces, uint32_t nf, uint32_t nv, const uint32_t* __restrict__ offset,
                                                              const uint32_t* __restrict__ corners, float* __restrict__ normals, uint32_t* __restrict__ longList, uint32_t longCapacity,
-                                                             uint32_t* words) {
+                                                             uint32_t* numLongWord) {
     for (uint32_t v = blockIdx.x * WG + threadIdx.x; v < nv; v += gridDim.x * WG) {
         const uint32_t s = offset[v], d = offset[v + 1] - s;
         if (d > SHORT_SEGMENT) {
-            const uint32_t at = atomicAdd(&words[W_NUM_LONG], 1u);
+            const uint32_t at = atomicAdd(numLongWord, 1u);
             if (at < longCapacity) longList[at] = v;
             continue;
         }
@@ -325,9 +326,9 @@ __global__ __launch_bounds__(256) void k_clean_normals_short(const float* __rest
     }
 }
 // one wave per long segment: the rank of a corner number is the count of lower ones in its segment (corner numbers are all different)
-__global__ __launch_bounds__(256) void k_clean_sort_long(const uint32_t* __restrict__ longList, const uint32_t* __restrict__ words, uint32_t longCapacity, uint32_t nv, const uint32_t* __restrict__ offset,
+__global__ __launch_bounds__(256) void k_clean_sort_long(const uint32_t* __restrict__ longList, const uint32_t* __restrict__ numLongWord, uint32_t longCapacity, uint32_t nv, const uint32_t* __restrict__ offset,
                                                          const uint32_t* __restrict__ corners, uint32_t* __restrict__ sorted) {
-    const uint32_t numLong = min(words[W_NUM_LONG], longCapacity);
+    const uint32_t numLong = min(*numLongWord, longCapacity);
     const uint32_t lane = threadIdx.x & 63, wave = blockIdx.x * (WG / 64) + (threadIdx.x >> 6), numWaves = gridDim.x * (WG / 64);
     for (uint32_t li = wave; li < numLong; li += numWaves) {
         const uint32_t v = longList[li];
@@ -343,9 +344,9 @@ __global__ __launch_bounds__(256) void k_clean_sort_long(const uint32_t* __restr
 }
 // after the sort kernel has ended: 64 face normals at a time, added lane by lane in every lane alike
 __global__ __launch_bounds__(256) void k_clean_normals_long(const float* __restrict__ P, const uint32_t* __restrict__ faces, uint32_t nf, uint32_t nv, const uint32_t* __restrict__ longList,
-                                                            const uint32_t* __restrict__ words, uint32_t longCapacity, const uint32_t* __restrict__ offset,
+                                                            const uint32_t* __restrict__ numLongWord, uint32_t longCapacity, const uint32_t* __restrict__ offset,
                                                             const uint32_t* __restrict__ sorted, float* __restrict__ normals) {
-    const uint32_t numLong = min(words[W_NUM_LONG], longCapacity);
+    const uint32_t numLong = min(*numLongWord, longCapacity);
     const uint32_t lane = threadIdx.x & 63, wave = blockIdx.x * (WG / 64) + (threadIdx.x >> 6), numWaves = gridDim.x * (WG / 64);
     for (uint32_t li = wave; li < numLong; li += numWaves) {
         const uint32_t v = longList[li];
@@ -417,7 +418,7 @@ int meshclean_run(MeshClean& c, Resources& res, hipStream_t st, const bf_indexed
     BF_HIP_TRY(hipGetLastError());
     BF_HIP_TRY(hipMemcpyAsync(words, c.d_words, sizeof words, hipMemcpyDeviceToHost, st));
     BF_HIP_TRY(hipStreamSynchronize(st));
-    c.numVertices = c.numFaces = 0; c.hasNormals = false;
+    c.numVertices = c.numFaces = 0; c.hasNormals = false; c.hasResult = false;
     if (words[W_ERR] & ERR_LOOP) { set_error("bf_marching_cubes_clean: a bounded loop of the labelling ran out of steps"); return BF_ERR_INTERNAL; }
     const uint32_t nvOut = words[W_NV_OUT], nfOut = words[W_NF_OUT];
     if (nvOut > nv || nfOut > nf) { set_error("bf_marching_cubes_clean: counts out of range"); return BF_ERR_INTERNAL; }
@@ -437,10 +438,16 @@ int meshclean_run(MeshClean& c, Resources& res, hipStream_t st, const bf_indexed
                        (const float*)nullptr, c.d_newId, (float*)nullptr, (float*)nullptr, c.d_faces);
     BF_HIP_TRY(hipGetLastError());
     c.numVertices = nvOut; c.numFaces = nfOut;
+    c.hasResult = true;
     if (!params.computeNormals) return BF_OK;
+    BF_TRY(meshnormals_run(c.normals, res, st, c.d_positions, c.d_faces, nvOut, nfOut));
+    c.hasNormals = true;
+    return BF_OK;
+}
 
-    // ---- normals
+int meshnormals_run(MeshNormals& c, Resources& res, hipStream_t st, const float* d_positions, const uint32_t* d_faces, uint32_t nvOut, uint32_t nfOut) {
     const uint32_t n = 3u * nfOut, tilesN = div_up(nvOut, TILE), longCap = n / (SHORT_SEGMENT + 1u) + 1u;
+    if (!c.d_numLong) BF_TRY(res.device(&c.d_numLong, 1));
     if (nvOut > c.capNormalVertices || !c.d_degree) {
         c.capNormalVertices = 0;
         BF_TRY(grow(res, &c.d_degree, nvOut)); BF_TRY(grow(res, &c.d_offset, (size_t)nvOut + 1)); BF_TRY(grow(res, &c.d_tilesN, tilesN));
@@ -452,22 +459,31 @@ int meshclean_run(MeshClean& c, Resources& res, hipStream_t st, const bf_indexed
         c.capNormalFaces = nfOut;
     }
     if (nvOut > c.capNormals || !c.d_normals) { c.capNormals = 0; BF_TRY(grow(res, &c.d_normals, 3 * (size_t)nvOut)); c.capNormals = nvOut; }
+    hipLaunchKernelGGL(k_clean_fill, dim3(1), dim3(WG), 0, st, c.d_numLong, 1u, 0u);
     hipLaunchKernelGGL(k_clean_fill, dim3(gridFor(nvOut)), dim3(WG), 0, st, c.d_degree, nvOut, 0u);
-    hipLaunchKernelGGL(k_clean_degree, dim3(gridFor(n)), dim3(WG), 0, st, (const uint32_t*)c.d_faces, n, nvOut, c.d_degree);
+    hipLaunchKernelGGL(k_clean_degree, dim3(gridFor(n)), dim3(WG), 0, st, d_faces, n, nvOut, c.d_degree);
     hipLaunchKernelGGL(k_clean_tile_sum, dim3(gridForTiles(tilesN)), dim3(WG), 0, st, (const uint32_t*)c.d_degree, nvOut, tilesN, c.d_tilesN);
     hipLaunchKernelGGL(k_clean_tile_scan, dim3(1), dim3(WG), 0, st, c.d_tilesN, tilesN, c.d_offset + nvOut);
     hipLaunchKernelGGL(k_clean_tile_exscan, dim3(gridForTiles(tilesN)), dim3(WG), 0, st, (const uint32_t*)c.d_degree, nvOut, tilesN, (const uint32_t*)c.d_tilesN, c.d_offset);
-    hipLaunchKernelGGL(k_clean_corner_fill, dim3(gridFor(n)), dim3(WG), 0, st, (const uint32_t*)c.d_faces, n, nvOut, c.d_degree, (const uint32_t*)c.d_offset, c.d_corners);
-    hipLaunchKernelGGL(k_clean_normals_short, dim3(gridFor(nvOut)), dim3(WG), 0, st, (const float*)c.d_positions, (const uint32_t*)c.d_faces, nfOut, nvOut, (const uint32_t*)c.d_offset,
-                       (const uint32_t*)c.d_corners, c.d_normals, c.d_long, longCap, c.d_words);
+    hipLaunchKernelGGL(k_clean_corner_fill, dim3(gridFor(n)), dim3(WG), 0, st, d_faces, n, nvOut, c.d_degree, (const uint32_t*)c.d_offset, c.d_corners);
+    hipLaunchKernelGGL(k_clean_normals_short, dim3(gridFor(nvOut)), dim3(WG), 0, st, d_positions, d_faces, nfOut, nvOut, (const uint32_t*)c.d_offset,
+                       (const uint32_t*)c.d_corners, c.d_normals, c.d_long, longCap, c.d_numLong);
     const uint32_t longGrid = std::max(1u, std::min(div_up(longCap, WG / 64), 2048u));
-    hipLaunchKernelGGL(k_clean_sort_long, dim3(longGrid), dim3(WG), 0, st, (const uint32_t*)c.d_long, (const uint32_t*)c.d_words, longCap, nvOut, (const uint32_t*)c.d_offset,
+    hipLaunchKernelGGL(k_clean_sort_long, dim3(longGrid), dim3(WG), 0, st, (const uint32_t*)c.d_long, (const uint32_t*)c.d_numLong, longCap, nvOut, (const uint32_t*)c.d_offset,
                        (const uint32_t*)c.d_corners, c.d_sorted);
-    hipLaunchKernelGGL(k_clean_normals_long, dim3(longGrid), dim3(WG), 0, st, (const float*)c.d_positions, (const uint32_t*)c.d_faces, nfOut, nvOut, (const uint32_t*)c.d_long,
-                       (const uint32_t*)c.d_words, longCap, (const uint32_t*)c.d_offset, (const uint32_t*)c.d_sorted, c.d_normals);
+    hipLaunchKernelGGL(k_clean_normals_long, dim3(longGrid), dim3(WG), 0, st, d_positions, d_faces, nfOut, nvOut, (const uint32_t*)c.d_long,
+                       (const uint32_t*)c.d_numLong, longCap, (const uint32_t*)c.d_offset, (const uint32_t*)c.d_sorted, c.d_normals);
     BF_HIP_TRY(hipGetLastError());
-    c.hasNormals = true;
     return BF_OK;
+}
+
+void meshnormals_host(const float* P, const uint32_t* F, uint32_t nvOut, uint32_t nfOut, float* nrmOut) {
+    std::vector<f3> S(nvOut, mk3(0.0f, 0.0f, 0.0f));
+    for (uint32_t f = 0; f < nfOut; ++f) {          // corners in increasing number 3f + c
+        const f3 N = faceNormal(P, F, f);
+        for (int d = 0; d < 3; ++d) { f3& s = S[F[3 * (size_t)f + d]]; s = s + N; }
+    }
+    for (uint32_t v = 0; v < nvOut; ++v) { const f3 nrm = unitOrZero(S[v]); nrmOut[3 * (size_t)v] = nrm.x; nrmOut[3 * (size_t)v + 1] = nrm.y; nrmOut[3 * (size_t)v + 2] = nrm.z; }
 }
 
 }  // namespace bf
@@ -522,14 +538,7 @@ extern "C" int bf_mesh_clean_host(const float* pos, const float* col, const uint
     }
     if (posOut && nvOut) memcpy(posOut, P.data(), 12 * (size_t)nvOut);
     if (facesOut && nfOut) memcpy(facesOut, F.data(), 12 * (size_t)nfOut);
-    if (nrmOut && params->computeNormals) {
-        std::vector<f3> S(nvOut, mk3(0.0f, 0.0f, 0.0f));
-        for (uint32_t f = 0; f < nfOut; ++f) {          // corners in increasing number 3f + c
-            const f3 N = faceNormal(P.data(), F.data(), f);
-            for (int d = 0; d < 3; ++d) { f3& s = S[F[3 * (size_t)f + d]]; s = s + N; }
-        }
-        for (uint32_t v = 0; v < nvOut; ++v) { const f3 nrm = unitOrZero(S[v]); nrmOut[3 * (size_t)v] = nrm.x; nrmOut[3 * (size_t)v + 1] = nrm.y; nrmOut[3 * (size_t)v + 2] = nrm.z; }
-    }
+    if (nrmOut && params->computeNormals) meshnormals_host(P.data(), F.data(), nvOut, nfOut, nrmOut);
     return BF_OK;
 }
 

@@ -726,7 +726,7 @@ typedef struct bf_mesh_clean_stats {
     uint32_t numVerticesIn, numFacesIn, numVerticesOut, numFacesOut, numComponents, numComponentsKept, numIsolatedVertices, largestComponentFaces;
 } bf_mesh_clean_stats;
 /* the cleaned mesh in HBM: positions, colours and normals numVertices x 3 float (d_normals NULL without computeNormals), faces numFaces x 3 uint32; owned by the
- * object, valid until its next extract, weld, clean or destroy */
+ * object, valid until its next extract, weld, clean or destroy (the same struct describes the result of bf_marching_cubes_simplify) */
 typedef struct bf_clean_mesh { const float* d_positions; const float* d_colors; const float* d_normals; const uint32_t* d_faces; uint32_t numVertices, numFaces; } bf_clean_mesh;
 /* Cleans the indexed mesh `in` (device arrays of any origin; NULL: the last weld) on the object's stream and waits for it twice (the refusal below, then the counts).  A face id
  * >= numVertices or more than 300 000 000 faces: BF_ERR_INVALID_ARG, the last result stays as it was.  out and stats may be NULL. */
@@ -747,6 +747,42 @@ BF_API int bf_mesh_clean_host(const float* h_positions, const float* h_colors, c
  * bf_write_ply_points), the same face records; h_normals NULL: exactly bf_write_ply_indexed */
 BF_API int bf_write_ply_indexed_normals(const char* filename, const float* h_positions, const float* h_normals, const float* h_colors, const uint32_t* h_faces, uint32_t numVertices,
                                         uint32_t numFaces);
+/* ---- MI355X additions: the indexed mesh simplified in HBM by vertex clustering on a uniform grid (csrc/meshsimplify.hip; DESIGN.md "Mesh simplification: the
+ * definition"; reference: none, the definition is the library's own) ----
+ * Cell of a vertex: per axis k = (int64)floor((double)p * (1.0 / (double)cellSize)), binary64, no contraction.  A cluster is the set of ALL input vertices of one
+ * cell, its leader its lowest vertex id.  With q(x) = (int64)floor((double)x * 1048576.0 + 0.5), a cluster of n members has the int64 sums SP[3], SC[3] of q over
+ * its members' positions and colours; its representative is the member itself, bit for bit, where n == 1, and per component
+ * (float)((double)S / ((double)n * 1048576.0)) otherwise.  Face ids are mapped to clusters; a face whose three clusters are not pairwise different is collapsed
+ * and dropped; among the others, faces with the same sorted triple keep the one with the lowest face index (the duplicates go); kept faces stay in face order with
+ * their winding.  Output vertices are the clusters a kept face uses, in increasing leader id; computeNormals != 0 adds the normals of bf_marching_cubes_clean's
+ * definition over the output mesh.  The map holds per input vertex its output id, or 0xFFFFFFFF where its cluster is not in the output.  No result depends on the
+ * order in which threads run.  Refused with BF_ERR_INVALID_ARG, the last result staying as it was: cellSize not finite or <= 0; a face id >= numVertices; a
+ * position or colour component that is not finite or has |x| >= 1024; a cell index with |k| >= 2^20; more than 300 000 000 faces. */
+typedef struct bf_mesh_simplify_params { float cellSize; int32_t computeNormals; } bf_mesh_simplify_params;
+/* numFacesIn == numFacesOut + numFacesCollapsed + numFacesDuplicate; numVerticesOut <= numClusters <= numVerticesIn; largestCluster: the most members of one cluster */
+typedef struct bf_mesh_simplify_stats {
+    uint32_t numVerticesIn, numFacesIn, numClusters, numVerticesOut, numFacesOut, numFacesCollapsed, numFacesDuplicate, largestCluster;
+} bf_mesh_simplify_stats;
+/* Simplifies the indexed mesh `in` (device arrays of any origin; NULL: the result of the last clean, BF_ERR_INVALID_ARG if there is none) on the object's stream
+ * and waits for it three times (the refusals, the cluster count, the output counts).  The result is owned by the object and valid until its next extract, weld,
+ * clean, simplify or destroy; out->d_normals is NULL without computeNormals.  out and stats may be NULL.  reference: none, the definition is the library's own */
+BF_API int bf_marching_cubes_simplify(bf_marching_cubes* m, const bf_indexed_mesh* in, const bf_mesh_simplify_params* params, bf_clean_mesh* out, bf_mesh_simplify_stats* stats);
+/* the map of the last simplify: per INPUT vertex its output id or 0xFFFFFFFF (at most `capacity` of them).  reference: none, the definition is the library's own */
+BF_API int bf_marching_cubes_simplify_map(bf_marching_cubes* m, uint32_t* h_map, uint32_t capacity);
+/* host copies of the last simplify's arrays (any of them may be NULL; h_normals is left alone where it computed none).  reference: none, the definition is the
+ * library's own */
+BF_API int bf_marching_cubes_download_simplified(bf_marching_cubes* m, float* h_positions, float* h_colors, float* h_normals, uint32_t* h_faces);
+/* weld of the last extraction (with the transform) + clean + simplify + download + PLY.  The clean's own normals are skipped: normals are computed once, on the
+ * simplified mesh, if either params struct asks for them (bf_write_ply_indexed_normals then, bf_write_ply_indexed otherwise); m_meshData is not touched.  Both
+ * stats may be NULL.  reference: none, the definition is the library's own */
+BF_API int bf_marching_cubes_save_mesh_simplified(bf_marching_cubes* m, const char* filename, const float transform[16], const bf_mesh_clean_params* cleanParams,
+                                                  const bf_mesh_simplify_params* simplifyParams, bf_mesh_clean_stats* cleanStats, bf_mesh_simplify_stats* simplifyStats);
+/* The definition on one core (needs no device): host arrays in, host arrays out.  h_mapOut: numVertices entries; the other outputs hold up to vertexCapacity
+ * vertices / faceCapacity faces (BF_ERR_CAPACITY, with *stats filled in, where the result is larger; nothing but stats is written then).  Any output may be NULL.
+ * reference: none, the definition is the library's own */
+BF_API int bf_mesh_simplify_host(const float* h_positions, const float* h_colors, const uint32_t* h_faces, uint32_t numVertices, uint32_t numFaces, const bf_mesh_simplify_params* params,
+                                 float* h_positionsOut, float* h_colorsOut, float* h_normalsOut, uint32_t* h_facesOut, uint32_t* h_mapOut, uint32_t vertexCapacity,
+                                 uint32_t faceCapacity, bf_mesh_simplify_stats* stats);
 /* the generated case tables (edge mask per case, up to 5 triangles of edge indices, -1 terminated), for inspection / tests */
 BF_API int bf_marching_cubes_tables(uint16_t edgeTable[256], int8_t triTable[256 * 16]);
 

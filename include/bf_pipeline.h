@@ -401,6 +401,13 @@ BF_API int bf_pipeline_save_mesh(bf_pipeline* p, const char* filename, const flo
  * the same state.  params must not be NULL; stats and numTriangles may be.  The same refusal for a sharded volume; the reconstruction is left alone. */
 BF_API int bf_pipeline_save_mesh_clean(bf_pipeline* p, const char* filename, const float* transform, const bf_mesh_clean_params* params, bf_mesh_clean_stats* stats,
                                        uint32_t* numTriangles);
+/* The same command with bf_marching_cubes_simplify behind the clean (bf_marching_cubes_save_mesh_simplified; bf_hip.h has the definition): the cleaned mesh's
+ * vertices clustered on a grid of simplifyParams->cellSize before the file is written; normals are computed once, on the simplified mesh, if either params struct
+ * asks for them.  Both params must not be NULL; both stats and numTriangles may be.  The same refusal for a sharded volume; the reconstruction is left alone.
+ * reference: none, the definition is the library's own */
+BF_API int bf_pipeline_save_mesh_simplified(bf_pipeline* p, const char* filename, const float* transform, const bf_mesh_clean_params* cleanParams,
+                                            const bf_mesh_simplify_params* simplifyParams, bf_mesh_clean_stats* cleanStats, bf_mesh_simplify_stats* simplifyStats,
+                                            uint32_t* numTriangles);
 BF_API int bf_pipeline_get_scene(bf_pipeline* p, bf_scene** out);
 BF_API int bf_pipeline_get_image_manager(bf_pipeline* p, bf_image_manager** out);
 BF_API int bf_pipeline_get_online_bundler(bf_pipeline* p, bf_online_bundler** out);

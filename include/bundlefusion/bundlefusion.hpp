@@ -812,6 +812,18 @@ public:
     void saveMeshClean(const std::string& filename, const bf_mesh_clean_params& params, const mat4f* transform = nullptr, bf_mesh_clean_stats* stats = nullptr) {
         check(bf_marching_cubes_save_mesh_clean(m_h, filename.c_str(), transform ? transform->m : nullptr, &params, stats));
     }
+    // The last clean's result (saveMeshClean, bf_marching_cubes_clean) simplified on the device by vertex clustering on a grid of params.cellSize
+    // (bf_marching_cubes_simplify): the simplified mesh in device memory, valid until the next extract, weld, clean, simplify or destruction.
+    bf_clean_mesh simplify(const bf_mesh_simplify_params& params, bf_mesh_simplify_stats* stats = nullptr) {
+        bf_clean_mesh out;
+        check(bf_marching_cubes_simplify(m_h, nullptr, &params, &out, stats));
+        return out;
+    }
+    // saveMeshClean with the cleaned mesh simplified on the device before the file is written; normals, if either params asks for them, are the simplified mesh's
+    void saveMeshSimplified(const std::string& filename, const bf_mesh_clean_params& cleanParams, const bf_mesh_simplify_params& simplifyParams, const mat4f* transform = nullptr,
+                            bf_mesh_clean_stats* cleanStats = nullptr, bf_mesh_simplify_stats* simplifyStats = nullptr) {
+        check(bf_marching_cubes_save_mesh_simplified(m_h, filename.c_str(), transform ? transform->m : nullptr, &cleanParams, &simplifyParams, cleanStats, simplifyStats));
+    }
     bf_marching_cubes* handle() const { return m_h; }
 private:
     MarchingCubesParams m_params;

@@ -1,7 +1,9 @@
 """--mesh / --mesh-host of tools/run_sens.py and tools/run_sequence.py: the scan's PLY after the end of the sequence, by the frame loop's own command
 (bf_pipeline_save_mesh: extraction and weld on the device) or by the host route (bf_marching_cubes_extract + bf_marching_cubes_save_mesh), with the counts
 and the seconds of each so that the two can be put side by side.  --mesh-min-faces / --mesh-largest / --mesh-normals clean the mesh before it is written
-(bf_pipeline_save_mesh_clean on the device route, bf_mesh_clean_host on the host route) and print the cleaning's stats."""
+(bf_pipeline_save_mesh_clean on the device route, bf_mesh_clean_host on the host route) and print the cleaning's stats.  --mesh-simplify-cell METRES clusters
+the cleaned mesh's vertices on a grid of that size before it is written (bf_pipeline_save_mesh_simplified on the device route, bf_mesh_simplify_host on the host
+route; normals, if asked for, are the simplified mesh's) and prints the simplification's stats and its time."""
 import ctypes as C
 import time
 
@@ -16,6 +18,7 @@ def add_arguments(ap):
     ap.add_argument("--mesh-min-faces", type=int, default=0, metavar="N", help="drop connected pieces of the mesh with fewer than N faces, and vertices no face uses")
     ap.add_argument("--mesh-largest", action="store_true", help="keep only the largest connected piece of the mesh")
     ap.add_argument("--mesh-normals", action="store_true", help="write area-weighted per-vertex normals into the PLY")
+    ap.add_argument("--mesh-simplify-cell", type=float, default=0.0, metavar="METRES", help="simplify the (cleaned) mesh before it is written: one vertex per grid cell of this size")
 
 
 def _cleaning(a):
@@ -26,6 +29,12 @@ def _stats_line(st):
     return ("%d -> %d vertices, %d -> %d faces; %d components, %d kept, largest %d faces, %d isolated vertices"
             % (st["numVerticesIn"], st["numVerticesOut"], st["numFacesIn"], st["numFacesOut"], st["numComponents"], st["numComponentsKept"], st["largestComponentFaces"],
                st["numIsolatedVertices"]))
+
+
+def _simplify_line(st):
+    return ("%d -> %d vertices, %d -> %d faces; %d clusters, largest %d vertices, %d faces collapsed, %d duplicate"
+            % (st["numVerticesIn"], st["numVerticesOut"], st["numFacesIn"], st["numFacesOut"], st["numClusters"], st["largestCluster"], st["numFacesCollapsed"],
+               st["numFacesDuplicate"]))
 
 
 def _device_stages(p, path, a):
@@ -39,7 +48,20 @@ def _device_stages(p, path, a):
     m = bf.capi.IndexedMesh()
     check(lib.bf_marching_cubes_weld(mc._h, None, 0, None, C.byref(m)))          # (waits for its stream)
     t2 = time.perf_counter()
-    if not _cleaning(a):
+    if a.mesh_simplify_cell > 0:
+        prm = bf.capi.MeshCleanParams(a.mesh_min_faces, int(a.mesh_largest), 0); st = bf.capi.MeshCleanStats()
+        check(lib.bf_marching_cubes_clean(mc._h, None, C.byref(prm), None, C.byref(st)))
+        check(lib.bf_marching_cubes_clean_labels(mc._h, None, 0))                # waits for the object's stream: the clean's last kernels have ended
+        t3 = time.perf_counter()
+        sp = bf.capi.MeshSimplifyParams(a.mesh_simplify_cell, int(a.mesh_normals)); sm = bf.capi.CleanMesh(); sst = bf.capi.MeshSimplifyStats()
+        check(lib.bf_marching_cubes_simplify(mc._h, None, C.byref(sp), C.byref(sm), C.byref(sst)))
+        check(lib.bf_marching_cubes_simplify_map(mc._h, None, 0))                # waits for the stream: the normals' kernels have ended
+        t4 = time.perf_counter()
+        pos, col, nrm, faces = mc.download_simplified(sm.numVertices, sm.numFaces, a.mesh_normals)
+        bf.capi.write_ply_indexed_normals(path, pos, nrm, col, faces)
+        t5 = time.perf_counter()
+        print("mesh (device route, stage by stage): extract %.4f s, weld %.4f s, clean %.4f s, simplify %.4f s, download + write %.4f s" % (t1 - t0, t2 - t1, t3 - t2, t4 - t3, t5 - t4))
+    elif not _cleaning(a):
         pos = np.empty((m.numVertices, 3), np.float32); col = np.empty((m.numVertices, 3), np.float32); faces = np.empty((m.numFaces, 3), np.uint32)
         check(lib.bf_marching_cubes_download_indexed(mc._h, pos.ctypes.data_as(C.c_void_p), col.ctypes.data_as(C.c_void_p), faces.ctypes.data_as(C.c_void_p)))
         bf.capi.write_ply_indexed(path, pos, col, faces)
@@ -74,7 +96,18 @@ def _host(p, path, a):
     nv, nf = mc.save_mesh(path)
     t2 = time.perf_counter()
     print("mesh (host route) %s: %d vertices, %d faces, %d triangles; extract + copy %.3f s, weld + write %.3f s, total %.3f s" % (path, nv, nf, found, t1 - t0, t2 - t1, t2 - t0))
-    if _cleaning(a):
+    if a.mesh_simplify_cell > 0:
+        pos, col, faces = mc.weld()
+        t3 = time.perf_counter()
+        cp, cc, _, cf, st, _ = bf.capi.mesh_clean_host(pos, col, faces, a.mesh_min_faces, a.mesh_largest, False)
+        t4 = time.perf_counter()
+        sp, sc_, sn, sf, sst, _ = bf.capi.mesh_simplify_host(cp, cc, cf, a.mesh_simplify_cell, a.mesh_normals)
+        t5 = time.perf_counter()
+        bf.capi.write_ply_indexed_normals(path, sp, sn, sc_, sf)
+        t6 = time.perf_counter()
+        print("mesh (host route) cleaned on one core: %s; clean %.3f s" % (_stats_line(st), t4 - t3))
+        print("mesh (host route) simplified on one core: %s; simplify %.3f s, write %.3f s" % (_simplify_line(sst), t5 - t4, t6 - t5))
+    elif _cleaning(a):
         pos, col, faces = mc.weld()                          # the arrays of the host weld (the device weld of the same extraction holds the same bits)
         t3 = time.perf_counter()
         cp, cc, cn, cf, st, _ = bf.capi.mesh_clean_host(pos, col, faces, a.mesh_min_faces, a.mesh_largest, a.mesh_normals)
@@ -89,7 +122,12 @@ def write(p, a):
     """p: the Pipeline after process_end_of_sequence / synchronize; a: the parsed arguments"""
     if a.mesh:
         t0 = time.perf_counter()
-        if _cleaning(a):
+        if a.mesh_simplify_cell > 0:
+            st, sst, nt = p.save_mesh_simplified(a.mesh, a.mesh_simplify_cell, None, a.mesh_min_faces, a.mesh_largest, a.mesh_normals)
+            dt = time.perf_counter() - t0
+            print("mesh (device route) %s: %d triangles; cleaned: %s; simplified at %g m: %s; bf_pipeline_save_mesh_simplified %.3f s"
+                  % (a.mesh, nt, _stats_line(st), a.mesh_simplify_cell, _simplify_line(sst), dt))
+        elif _cleaning(a):
             st, nt = p.save_mesh_clean(a.mesh, None, a.mesh_min_faces, a.mesh_largest, a.mesh_normals)
             dt = time.perf_counter() - t0
             print("mesh (device route) %s: %d triangles; %s; bf_pipeline_save_mesh_clean %.3f s" % (a.mesh, nt, _stats_line(st), dt))
