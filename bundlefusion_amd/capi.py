@@ -1462,6 +1462,53 @@ class Pipeline:
         check(lib.bf_pipeline_save_mesh_simplified(self._h, str(filename).encode(), T, C.byref(p), C.byref(sp), C.byref(st), C.byref(sst), C.byref(nt)))
         return st.as_dict(), sst.as_dict(), nt.value
 
+    def mesh_recolour_defaults(self):
+        """bf_pipeline_get_mesh_recolour_defaults: the MeshRecolourParams the pipeline uses where none are given"""
+        rp = MeshRecolourParams()
+        check(lib.bf_pipeline_get_mesh_recolour_defaults(self._h, C.byref(rp)))
+        return rp
+
+    def mesh_recolour_intrinsics(self):
+        """bf_pipeline_get_mesh_recolour_intrinsics: the [4,4] intrinsics save_mesh_recoloured projects with"""
+        K = (C.c_float * 16)()
+        check(lib.bf_pipeline_get_mesh_recolour_intrinsics(self._h, K))
+        return np.array(K[:], np.float32).reshape(4, 4)
+
+    def mesh_recolour_frames_host(self, frame_stride=None, transform=None, trajectory=None, images=True):
+        """what save_mesh_recoloured takes the colours from, as host arrays: (frames, intrinsics, width, height) with frames = [(depth, colour, meshToCamera,
+        cameraCentre, skipped)] of the stored frames 0, stride, 2 * stride, ... that have a valid optimised pose (trajectory None: the current one), camera to mesh
+        = transform * pose in binary32 with bf_device.h's product, through bf_mesh_recolour_frame_from_pose.  images False: the frame's number in place of its
+        two images, (frame, meshToCamera, cameraCentre, skipped)"""
+        stride = int(self.gbs.s_submapSize) if frame_stride is None else int(frame_stride)
+        T = self.optimized_trajectory() if trajectory is None else np.asarray(trajectory, np.float32).reshape(-1, 4, 4)
+        X = None if transform is None else np.asarray(transform, np.float32).reshape(4, 4)
+        frames = []
+        for f in range(0, len(T), stride):
+            if np.isnan(T[f, 0, 0]) or T[f, 0, 0] == -np.inf:
+                continue
+            M = T[f]
+            if X is not None:
+                with np.errstate(all="ignore"):
+                    M = ((X[:, 0:1] * M[0:1, :] + X[:, 1:2] * M[1:2, :]) + X[:, 2:3] * M[2:3, :]) + X[:, 3:4] * M[3:4, :]
+            frames.append((self.integrate_frame_cpu(f) if images else (f,)) + mesh_recolour_frame_from_pose(M))
+        im = C.c_void_p(); w = C.c_uint32(); h = C.c_uint32()
+        check(lib.bf_pipeline_get_image_manager(self._h, C.byref(im)))
+        check(lib.bf_image_manager_get_integration_size(im, C.byref(w), C.byref(h)))
+        return frames, self.mesh_recolour_intrinsics(), w.value, h.value
+
+    def save_mesh_recoloured(self, filename, transform=None, min_faces=0, largest=False, normals=False, params=None, frame_stride=None, cell_size=None):
+        """bf_pipeline_save_mesh_recoloured: save_mesh_clean with the cleaned mesh's vertex colours taken on the device from the stored frames on the stride under the
+        optimised trajectory, then (cell_size given) the simplification of the recoloured mesh.  params None: mesh_recolour_defaults(); frame_stride None:
+        s_submapSize (the key frames).  Returns (clean stats dict, recolour stats dict, simplify stats dict or None, triangles)."""
+        p = MeshCleanParams(int(min_faces), int(bool(largest)), int(bool(normals)))
+        sp = None if cell_size is None else MeshSimplifyParams(float(cell_size), int(bool(normals)))
+        st = MeshCleanStats(); rst = MeshRecolourStats(); sst = MeshSimplifyStats(); nt = C.c_uint32()
+        T = mat16(transform) if transform is not None else None
+        stride = int(self.gbs.s_submapSize) if frame_stride is None else int(frame_stride)
+        check(lib.bf_pipeline_save_mesh_recoloured(self._h, str(filename).encode(), T, C.byref(p), None if params is None else C.byref(params), stride,
+                                                   None if sp is None else C.byref(sp), C.byref(st), C.byref(rst), C.byref(sst), C.byref(nt)))
+        return st.as_dict(), rst.as_dict(), (None if sp is None else sst.as_dict()), nt.value
+
     def save_point_cloud(self, filename, frame_stride=None, cell_size=0.005, max_depth=3.5, max_points=0):
         """bf_pipeline_save_point_cloud: the stored frames on the stride under the optimised trajectory as a thinned point cloud PLY, built on the device.
         frame_stride None: s_submapSize (the key frames).  Returns (points, frames used)."""
@@ -1746,6 +1793,110 @@ class MarchingCubesHashSDF:
         T = mat16(transform) if transform is not None else None
         check(lib.bf_marching_cubes_save_mesh_simplified(self._h, str(filename).encode(), T, C.byref(p), C.byref(sp), C.byref(st), C.byref(sst)))
         return st.as_dict(), sst.as_dict()
+
+    # ---- MI355X additions: the mesh's vertex colours taken from the key frames in HBM (csrc/meshrecolour.hip)
+    def recolour(self, mesh, frames, width, height, intrinsics, params):
+        """bf_marching_cubes_recolour + download: (colours [nv,3] float32, views [nv] uint32, stats dict).  mesh: (positions, colours, normals, faces) as contiguous
+        torch cuda tensors (faces may be None), or None for the last clean (or the last simplify if later); frames: a recolour_frames() array whose images are
+        device pointers; params: a MeshRecolourParams."""
+        out = CleanMesh(); st = MeshRecolourStats()
+        K = mat16(intrinsics)
+        if mesh is None:
+            check(lib.bf_marching_cubes_recolour(self._h, None, frames, len(frames), int(width), int(height), K, C.byref(params), C.byref(out), C.byref(st)))
+        else:
+            pos, col, nrm, faces = mesh
+            assert pos.is_contiguous() and col.is_contiguous() and (nrm is None or nrm.is_contiguous()) and pos.numel() == col.numel() and pos.numel() % 3 == 0
+            m = CleanMesh(pos.data_ptr() or None, col.data_ptr() or None, None if nrm is None else (nrm.data_ptr() or None), None if faces is None else (faces.data_ptr() or None),
+                          pos.numel() // 3, 0 if faces is None else faces.numel() // 3)
+            check(lib.bf_marching_cubes_recolour(self._h, C.byref(m), frames, len(frames), int(width), int(height), K, C.byref(params), C.byref(out), C.byref(st)))
+        self._recoloured = out
+        return self.download_recoloured(out.numVertices, 0)[1], self.recolour_views(out.numVertices), st.as_dict()
+
+    def simplify_recoloured(self, cell_size=0.01, normals=False):
+        """bf_marching_cubes_simplify of the last recolour's mesh (its own colour array as the input's colours) + download, as simplify()"""
+        r = self._recoloured
+        m = IndexedMesh(r.d_positions, r.d_colors, r.d_faces, r.numVertices, r.numFaces)
+        p = MeshSimplifyParams(float(cell_size), int(bool(normals))); out = CleanMesh(); st = MeshSimplifyStats()
+        check(lib.bf_marching_cubes_simplify(self._h, C.byref(m), C.byref(p), C.byref(out), C.byref(st)))
+        return self.download_simplified(out.numVertices, out.numFaces, normals) + (st.as_dict(),)
+
+    def download_recoloured(self, nv, nf, normals=False):
+        """bf_marching_cubes_download_recoloured: (positions, colours, normals or None, faces) of the last recolour, whose counts the caller knows"""
+        hp = np.zeros((nv, 3), np.float32); hc = np.zeros((nv, 3), np.float32); hf = np.zeros((nf, 3), np.uint32)
+        hn = np.zeros((nv, 3), np.float32) if normals else None
+        check(lib.bf_marching_cubes_download_recoloured(self._h, hp.ctypes.data_as(C.c_void_p), hc.ctypes.data_as(C.c_void_p), hn.ctypes.data_as(C.c_void_p) if normals else None,
+                                                        hf.ctypes.data_as(C.c_void_p) if nf else None))
+        return hp, hc, hn, hf
+
+    def recolour_views(self, num_vertices):
+        """the number of views of the first num_vertices vertices of the last recolour (uint32)"""
+        out = np.zeros(int(num_vertices), np.uint32)
+        check(lib.bf_marching_cubes_recolour_views(self._h, out.ctypes.data_as(C.c_void_p), len(out)))
+        return out
+
+    def save_mesh_recoloured(self, filename, frames, width, height, intrinsics, params, transform=None, min_faces=0, largest=False, normals=False, cell_size=None):
+        """weld of the last extraction + clean + recolour (+ simplify on a grid of cell_size, if given) on the device + PLY: (clean stats dict, recolour stats dict,
+        simplify stats dict or None).  The frames' poses are camera to mesh: the transform already applied."""
+        p = MeshCleanParams(int(min_faces), int(bool(largest)), int(bool(normals)))
+        sp = None if cell_size is None else MeshSimplifyParams(float(cell_size), int(bool(normals)))
+        st = MeshCleanStats(); rst = MeshRecolourStats(); sst = MeshSimplifyStats()
+        T = mat16(transform) if transform is not None else None
+        check(lib.bf_marching_cubes_save_mesh_recoloured(self._h, str(filename).encode(), T, C.byref(p), frames, len(frames), int(width), int(height), mat16(intrinsics), C.byref(params),
+                                                         None if sp is None else C.byref(sp), C.byref(st), C.byref(rst), C.byref(sst)))
+        return st.as_dict(), rst.as_dict(), (None if sp is None else sst.as_dict())
+
+
+class MeshRecolourParams(C.Structure):
+    _fields_ = [("depthMin", C.c_float), ("depthMax", C.c_float), ("depthTolerance", C.c_float), ("depthToleranceLin", C.c_float), ("minCos", C.c_float), ("mode", C.c_int32)]
+
+
+class MeshRecolourStats(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("numVertices", "numRecoloured", "numUnseen", "numFramesUsed", "numFramesSkipped", "maxViews")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class MeshRecolourFrame(C.Structure):
+    _fields_ = [("d_depth", C.c_void_p), ("d_colorRGBX", C.c_void_p), ("meshToCamera", C.c_float * 16), ("cameraCentre", C.c_float * 3), ("skipped", C.c_int32)]
+
+
+# the rule codes of a (vertex, frame) pair, BF_RECOLOUR_* (the first rule that fails; 0: a view)
+RECOLOUR_CODES = ("VIEW", "NORMAL", "RANGE", "IMAGE", "FACING", "OCCLUDED", "COLOUR")
+
+
+def mesh_recolour_frame_from_pose(camera_to_mesh):
+    """bf_mesh_recolour_frame_from_pose: (meshToCamera [4,4] float32, cameraCentre [3] float32, skipped).  Host-only."""
+    f = MeshRecolourFrame()
+    check(lib.bf_mesh_recolour_frame_from_pose(mat16(camera_to_mesh), C.byref(f)))
+    return np.array(f.meshToCamera[:], np.float32).reshape(4, 4), np.array(f.cameraCentre[:], np.float32), bool(f.skipped)
+
+
+def recolour_frames(frames):
+    """a ctypes array of bf_mesh_recolour_frame from (depth pointer, colour pointer, meshToCamera, cameraCentre, skipped) tuples; the pointers are integers (device
+    pointers for the device route, host pointers for mesh_recolour_host) or None"""
+    arr = (MeshRecolourFrame * len(frames))()
+    for k, (d, c, W, o, skipped) in enumerate(frames):
+        arr[k].d_depth = d; arr[k].d_colorRGBX = c; arr[k].skipped = int(bool(skipped))
+        arr[k].meshToCamera[:] = np.asarray(W, np.float32).reshape(16).tolist(); arr[k].cameraCentre[:] = np.asarray(o, np.float32).reshape(3).tolist()
+    return arr
+
+
+def mesh_recolour_host(positions, normals, colors, frames, width, height, intrinsics, params, codes=False):
+    """bf_mesh_recolour_host, the definition on one core: (colours, views, stats dict[, codes [nv, K] uint8]).  frames: (depth [h,w] float32, colour [h,w,4] uint8,
+    meshToCamera, cameraCentre, skipped) tuples of host arrays.  Host-only."""
+    pos = np.ascontiguousarray(positions, np.float32).reshape(-1, 3); col = np.ascontiguousarray(colors, np.float32).reshape(-1, 3)
+    nrm = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    keep = [(np.ascontiguousarray(d, np.float32), np.ascontiguousarray(c, np.uint8)) for d, c, _, _, _ in frames]
+    for d, c in keep:
+        assert d.shape == (height, width) and c.shape == (height, width, 4)
+    fr = recolour_frames([(d.ctypes.data, c.ctypes.data, W, o, s) for (d, c), (_, _, W, o, s) in zip(keep, frames)])
+    oc = np.zeros_like(col); views = np.zeros(len(pos), np.uint32); st = MeshRecolourStats()
+    cd = np.full((len(pos), len(frames)), 255, np.uint8) if codes else None
+    check(lib.bf_mesh_recolour_host(pos.ctypes.data_as(C.c_void_p), None if nrm is None else nrm.ctypes.data_as(C.c_void_p), col.ctypes.data_as(C.c_void_p), len(pos), fr, len(frames),
+                                    int(width), int(height), mat16(intrinsics), C.byref(params), oc.ctypes.data_as(C.c_void_p), views.ctypes.data_as(C.c_void_p),
+                                    cd.ctypes.data_as(C.c_void_p) if codes else None, C.byref(st)))
+    return (oc, views, st.as_dict()) + ((cd,) if codes else ())
 
 
 class IndexedMesh(C.Structure):

@@ -2576,6 +2576,8 @@ namespace {
 struct PlMeshJob {
     bf_pipeline* p; const char* filename; const float* transform; uint32_t nv, nf, nt; const bf_mesh_clean_params* clean; bf_mesh_clean_stats* stats;
     const bf_mesh_simplify_params* simplify; bf_mesh_simplify_stats* simplifyStats;
+    // recolour non-null (with clean): the recoloured save, its frames resolved by the poster; simplify is optional behind it
+    const bf_mesh_recolour_params* recolour; bf_mesh_recolour_stats* recolourStats; const bf_mesh_recolour_frame* frames; uint32_t numFrames; const float* intrinsics;
 };
 
 // on the volume thread (timings: on the calling thread), between two batches.  The view's exclusive section is a render's: the preparation stream has finished
@@ -2589,7 +2591,10 @@ int plMeshExec(void* ctx) {
     BF_TRY(bf_scene_begin_view(p->scene, I, &p->cam, &hd, &hp));
     int rc = bf_marching_cubes_extract_gpu(p->marchingCubes, &hd, &hp, nullptr, nullptr, 0);
     if (rc == BF_OK) rc = bf_marching_cubes_get_triangles_gpu(p->marchingCubes, nullptr, nullptr, &j.nt);
-    if (rc == BF_OK) rc = j.simplify ? bf_marching_cubes_save_mesh_simplified(p->marchingCubes, j.filename, j.transform, j.clean, j.simplify, j.stats, j.simplifyStats)
+    if (rc == BF_OK && j.recolour)
+        rc = bf_marching_cubes_save_mesh_recoloured(p->marchingCubes, j.filename, j.transform, j.clean, j.frames, j.numFrames, p->im->wInt, p->im->hInt, j.intrinsics, j.recolour, j.simplify,
+                                                    j.stats, j.recolourStats, j.simplifyStats);
+    else if (rc == BF_OK) rc = j.simplify ? bf_marching_cubes_save_mesh_simplified(p->marchingCubes, j.filename, j.transform, j.clean, j.simplify, j.stats, j.simplifyStats)
                         : j.clean  ? bf_marching_cubes_save_mesh_clean(p->marchingCubes, j.filename, j.transform, j.clean, j.stats)
                                    : bf_marching_cubes_save_mesh_gpu(p->marchingCubes, j.filename, j.transform, &j.nv, &j.nf);          // waits for the volume stream
     const int rc2 = bf_scene_end_view(p->scene);
@@ -2611,13 +2616,13 @@ static int plSaveMesh(bf_pipeline* p, PlMeshJob& j) {
         BF_TRY(bf_marching_cubes_set_stream(p->marchingCubes, p->sVolume));
     }
     VolumeQueue::Cmd c;
-    c.op = j.simplify ? VolumeQueue::Op::SaveMeshSimplified : VolumeQueue::Op::SaveMesh; c.render = plMeshExec; c.renderCtx = &j;
+    c.op = j.recolour ? VolumeQueue::Op::SaveMeshRecoloured : j.simplify ? VolumeQueue::Op::SaveMeshSimplified : VolumeQueue::Op::SaveMesh; c.render = plMeshExec; c.renderCtx = &j;
     return p->vol.postAndWait(c);
 }
 
 int bf_pipeline_save_mesh(bf_pipeline* p, const char* filename, const float* transform, uint32_t* numVertices, uint32_t* numFaces, uint32_t* numTriangles) {
     BF_REQUIRE(p && filename, "null argument");
-    PlMeshJob j = {p, filename, transform, 0, 0, 0, nullptr, nullptr, nullptr, nullptr};
+    PlMeshJob j = {p, filename, transform, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr};
     BF_TRY(plSaveMesh(p, j));
     if (numVertices) *numVertices = j.nv;
     if (numFaces) *numFaces = j.nf;
@@ -2628,7 +2633,7 @@ int bf_pipeline_save_mesh(bf_pipeline* p, const char* filename, const float* tra
 // the same command with bf_marching_cubes_clean between the weld and the file
 int bf_pipeline_save_mesh_clean(bf_pipeline* p, const char* filename, const float* transform, const bf_mesh_clean_params* params, bf_mesh_clean_stats* stats, uint32_t* numTriangles) {
     BF_REQUIRE(p && filename && params, "null argument");
-    PlMeshJob j = {p, filename, transform, 0, 0, 0, params, stats, nullptr, nullptr};
+    PlMeshJob j = {p, filename, transform, 0, 0, 0, params, stats, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr};
     BF_TRY(plSaveMesh(p, j));
     if (numTriangles) *numTriangles = j.nt;
     return BF_OK;
@@ -2638,7 +2643,62 @@ int bf_pipeline_save_mesh_clean(bf_pipeline* p, const char* filename, const floa
 int bf_pipeline_save_mesh_simplified(bf_pipeline* p, const char* filename, const float* transform, const bf_mesh_clean_params* cleanParams, const bf_mesh_simplify_params* simplifyParams,
                                      bf_mesh_clean_stats* cleanStats, bf_mesh_simplify_stats* simplifyStats, uint32_t* numTriangles) {
     BF_REQUIRE(p && filename && cleanParams && simplifyParams, "null argument");
-    PlMeshJob j = {p, filename, transform, 0, 0, 0, cleanParams, cleanStats, simplifyParams, simplifyStats};
+    PlMeshJob j = {p, filename, transform, 0, 0, 0, cleanParams, cleanStats, simplifyParams, simplifyStats, nullptr, nullptr, nullptr, 0, nullptr};
+    BF_TRY(plSaveMesh(p, j));
+    if (numTriangles) *numTriangles = j.nt;
+    return BF_OK;
+}
+
+// The recolouring's defaults from the pipeline's own parameters: the depth range the integration accepts (s_sensorDepthMin .. s_SDFMaxIntegrationDistance), a depth
+// tolerance of 1 cm + 1 % of the depth, views within acos(0.3) of the normal, blend (DESIGN.md "Mesh colour from the key frames" has the reasons)
+int bf_pipeline_get_mesh_recolour_defaults(bf_pipeline* p, bf_mesh_recolour_params* params) {
+    BF_REQUIRE(p && params, "null argument");
+    params->depthMin = p->gas.s_sensorDepthMin; params->depthMax = p->gas.s_SDFMaxIntegrationDistance;
+    params->depthTolerance = 0.01f; params->depthToleranceLin = 0.01f; params->minCos = 0.3f; params->mode = 0;
+    return BF_OK;
+}
+
+// the intrinsics the recolouring projects with: registered depth lives in the colour camera (DepthSensing.cpp:285-288), as for the integration
+int bf_pipeline_get_mesh_recolour_intrinsics(bf_pipeline* p, float K[16]) {
+    BF_REQUIRE(p && K, "null argument");
+    memcpy(K, (p->im->calib ? p->im->colorIntrinsics : p->im->depthIntrinsics).e, 64);
+    return BF_OK;
+}
+
+// ... and with bf_marching_cubes_recolour behind the clean, the optional simplify behind that (bf_marching_cubes_save_mesh_recoloured).  The frames are chosen and
+// resolved here, on the calling thread: bf_pipeline_save_point_cloud's rule over the optimised trajectory.
+int bf_pipeline_save_mesh_recoloured(bf_pipeline* p, const char* filename, const float* transform, const bf_mesh_clean_params* cleanParams, const bf_mesh_recolour_params* recolourParams,
+                                     uint32_t frameStride, const bf_mesh_simplify_params* simplifyParams, bf_mesh_clean_stats* cleanStats, bf_mesh_recolour_stats* recolourStats,
+                                     bf_mesh_simplify_stats* simplifyStats, uint32_t* numTriangles) {
+    BF_REQUIRE(p && filename && cleanParams, "null argument");
+    BF_REQUIRE(frameStride >= 1, "the frame stride must be at least 1");
+    BF_REQUIRE(!p->volumeSharded && !p->volumeComm, "the volume is sharded over ranks (bf_pipeline_set_volume_shard / _set_comm): a shard lacks its neighbours' blocks, meshing across ranks is not supported");
+    bf_mesh_recolour_params rp;
+    if (recolourParams) rp = *recolourParams; else BF_TRY(bf_pipeline_get_mesh_recolour_defaults(p, &rp));
+    BF_TRY(plFlush(p));
+    bf_trajectory_manager* tm = nullptr;
+    BF_TRY(bf_online_bundler_get_trajectory_manager(p->ob, &tm));
+    uint32_t n = 0, count = 0;
+    BF_TRY(bf_trajectory_manager_get_num_optimized_frames(tm, &n));
+    std::vector<float> T((size_t)std::max(n, 1u) * 16);
+    if (n) BF_TRY(bf_trajectory_manager_get_optimized_transforms(tm, T.data(), n, &count));
+    count = std::min(count, p->im->currFrame);
+    m44 X = identity44();
+    if (transform) memcpy(X.e, transform, 64);
+    std::vector<bf_mesh_recolour_frame> frames;
+    for (uint32_t f = 0; f < count; f += frameStride) {
+        const float* Tf = T.data() + 16 * (size_t)f;
+        if (Tf[0] != Tf[0] || Tf[0] == NINF) continue;
+        bf_mesh_recolour_frame fr;
+        BF_TRY(bf_image_manager_get_integrate_frame_gpu(p->im, f, &fr.d_depth, &fr.d_colorRGBX));
+        m44 M; memcpy(M.e, Tf, 64);
+        if (transform) M = mul44(X, M);
+        BF_TRY(bf_mesh_recolour_frame_from_pose(M.e, &fr));
+        frames.push_back(fr);
+    }
+    float K[16];
+    BF_TRY(bf_pipeline_get_mesh_recolour_intrinsics(p, K));
+    PlMeshJob j = {p, filename, transform, 0, 0, 0, cleanParams, cleanStats, simplifyParams, simplifyStats, &rp, recolourStats, frames.data(), (uint32_t)frames.size(), K};
     BF_TRY(plSaveMesh(p, j));
     if (numTriangles) *numTriangles = j.nt;
     return BF_OK;

@@ -34,6 +34,7 @@
 #include "bf_meshweld.h"
 #include "bf_meshclean.h"
 #include "bf_meshsimplify.h"
+#include "bf_meshrecolour.h"
 #include "bf_volume.h"
 
 using namespace bf;
@@ -316,7 +317,9 @@ struct bf_marching_cubes {
     MeshWeld weld;                      // the indexed mesh of the last bf_marching_cubes_weld, in HBM (meshweld.hip)
     MeshClean clean;                    // the cleaned mesh of the last bf_marching_cubes_clean, in HBM (meshclean.hip)
     MeshSimplify simplify;              // the simplified mesh of the last bf_marching_cubes_simplify, in HBM (meshsimplify.hip)
-    bf::Resources res;                  // owns every buffer above, the weld's, the clean's and the simplification's included
+    MeshRecolour recolour;              // the colours of the last bf_marching_cubes_recolour, in HBM (meshrecolour.hip)
+    int lastMesh = 0;                   // bf_marching_cubes_recolour's default input: 0 none, 1 the last clean, 2 the last simplify (whichever ran later)
+    bf::Resources res;                  // owns every buffer above, the weld's, the clean's, the simplification's and the recolouring's included
 };
 
 extern "C" {
@@ -386,6 +389,7 @@ static int mcExtract(bf_marching_cubes* m, const bf_hash_data* hd, const bf_hash
     BF_HIP_TRY(hipMemcpyAsync(&nb, m->d_numBlocks, 4, hipMemcpyDeviceToHost, st));
     BF_HIP_TRY(hipStreamSynchronize(st));
     m->numTriangles = m->numTrianglesFound = 0;
+    m->recolour.numVertices = m->recolour.numFaces = 0;          // the last recolour's mesh is gone with the extraction it came from
     if (nb == 0) return BF_OK;
     const uint32_t grid = std::min(nb, 8192u);
     hipLaunchKernelGGL(k_mc_blocks<false>, dim3(grid), dim3(512), 0, st, a, (const McTables*)m->d_tables, (const uint32_t*)m->d_slots, (const uint32_t*)m->d_numBlocks,
@@ -493,6 +497,7 @@ int bf_marching_cubes_save_mesh(bf_marching_cubes* m, const char* filename, cons
 int bf_marching_cubes_weld(bf_marching_cubes* m, const bf_mc_triangle* d_triangles, uint32_t numTriangles, const float transform[16], bf_indexed_mesh* out) {
     BF_REQUIRE(m, "null argument");
     if (!d_triangles) { d_triangles = m->d_triangles; numTriangles = m->numTriangles; }
+    m->recolour.numVertices = m->recolour.numFaces = 0;          // a recolour's result ends here: the arrays it points into may be regrown
     BF_TRY(meshweld_run(m->weld, m->res, m->stream, d_triangles, numTriangles, transform));
     if (out) { out->d_positions = m->weld.d_positions; out->d_colors = m->weld.d_colors; out->d_faces = m->weld.d_faces; out->numVertices = m->weld.numVertices; out->numFaces = m->weld.numFaces; }
     return BF_OK;
@@ -527,7 +532,9 @@ int bf_marching_cubes_clean(bf_marching_cubes* m, const bf_indexed_mesh* in, con
     BF_REQUIRE(m && params, "null argument");
     bf_indexed_mesh last;
     last.d_positions = m->weld.d_positions; last.d_colors = m->weld.d_colors; last.d_faces = m->weld.d_faces; last.numVertices = m->weld.numVertices; last.numFaces = m->weld.numFaces;
+    m->recolour.numVertices = m->recolour.numFaces = 0;          // (as the weld)
     BF_TRY(meshclean_run(m->clean, m->res, m->stream, in ? *in : last, *params, stats));
+    m->lastMesh = 1;
     const MeshClean& c = m->clean;
     if (out) { out->d_positions = c.d_positions; out->d_colors = c.d_colors; out->d_normals = c.hasNormals ? c.normals.d_normals : nullptr; out->d_faces = c.d_faces; out->numVertices = c.numVertices; out->numFaces = c.numFaces; }
     return BF_OK;
@@ -571,6 +578,7 @@ int bf_marching_cubes_simplify(bf_marching_cubes* m, const bf_indexed_mesh* in, 
     bf_indexed_mesh last;
     last.d_positions = m->clean.d_positions; last.d_colors = m->clean.d_colors; last.d_faces = m->clean.d_faces; last.numVertices = m->clean.numVertices; last.numFaces = m->clean.numFaces;
     BF_TRY(meshsimplify_run(m->simplify, m->res, m->stream, in ? *in : last, *params, stats));
+    m->lastMesh = 2;
     const MeshSimplify& s = m->simplify;
     if (out) { out->d_positions = s.d_positions; out->d_colors = s.d_colors; out->d_normals = s.hasNormals ? s.normals.d_normals : nullptr; out->d_faces = s.d_faces; out->numVertices = s.numVertices; out->numFaces = s.numFaces; }
     return BF_OK;
@@ -611,6 +619,77 @@ int bf_marching_cubes_save_mesh_simplified(bf_marching_cubes* m, const char* fil
     std::vector<uint32_t> faces(3 * (size_t)sm.numFaces);
     BF_TRY(bf_marching_cubes_download_simplified(m, pos.data(), col.data(), nrm.data(), faces.data()));
     return bf_write_ply_indexed_normals(filename, pos.data(), sm.d_normals ? nrm.data() : nullptr, col.data(), faces.data(), sm.numVertices, sm.numFaces);
+}
+
+// Vertex colours from the key frames over a mesh in HBM (meshrecolour.hip); in null: the last clean's result, or the last simplify's if that ran later.  On the object's stream.
+int bf_marching_cubes_recolour(bf_marching_cubes* m, const bf_clean_mesh* in, const bf_mesh_recolour_frame* frames, uint32_t numFrames, uint32_t width, uint32_t height,
+                               const float intrinsics[16], const bf_mesh_recolour_params* params, bf_clean_mesh* out, bf_mesh_recolour_stats* stats) {
+    BF_REQUIRE(m && params && intrinsics, "null argument");
+    BF_REQUIRE(in || m->lastMesh, "no input mesh and no result of a clean or a simplify to take");
+    bf_clean_mesh last;
+    if (m->lastMesh == 2) {
+        const MeshSimplify& s = m->simplify;
+        last.d_positions = s.d_positions; last.d_colors = s.d_colors; last.d_normals = s.hasNormals ? s.normals.d_normals : nullptr; last.d_faces = s.d_faces; last.numVertices = s.numVertices; last.numFaces = s.numFaces;
+    } else {
+        const MeshClean& c = m->clean;
+        last.d_positions = c.d_positions; last.d_colors = c.d_colors; last.d_normals = c.hasNormals ? c.normals.d_normals : nullptr; last.d_faces = c.d_faces; last.numVertices = c.numVertices; last.numFaces = c.numFaces;
+    }
+    const bf_clean_mesh& src = in ? *in : last;
+    BF_TRY(meshrecolour_run(m->recolour, m->res, m->stream, src, frames, numFrames, width, height, intrinsics, *params, stats));
+    if (out) { *out = src; out->d_colors = m->recolour.d_colors; }
+    return BF_OK;
+}
+
+int bf_marching_cubes_recolour_views(bf_marching_cubes* m, uint32_t* h_views, uint32_t capacity) {
+    BF_REQUIRE(m && (h_views || capacity == 0), "null argument");
+    const uint32_t n = std::min(capacity, m->recolour.numVertices);
+    if (n) BF_HIP_TRY(hipMemcpyAsync(h_views, m->recolour.d_views, 4 * (size_t)n, hipMemcpyDeviceToHost, m->stream));
+    BF_HIP_TRY(hipStreamSynchronize(m->stream));
+    return BF_OK;
+}
+
+int bf_marching_cubes_download_recoloured(bf_marching_cubes* m, float* h_positions, float* h_colors, float* h_normals, uint32_t* h_faces) {
+    BF_REQUIRE(m, "null argument");
+    const MeshRecolour& r = m->recolour;
+    if (h_positions && r.numVertices) BF_HIP_TRY(hipMemcpyAsync(h_positions, r.d_positions, 12 * (size_t)r.numVertices, hipMemcpyDeviceToHost, m->stream));
+    if (h_colors && r.numVertices) BF_HIP_TRY(hipMemcpyAsync(h_colors, r.d_colors, 12 * (size_t)r.numVertices, hipMemcpyDeviceToHost, m->stream));
+    if (h_normals && r.numVertices) BF_HIP_TRY(hipMemcpyAsync(h_normals, r.d_normals, 12 * (size_t)r.numVertices, hipMemcpyDeviceToHost, m->stream));
+    if (h_faces && r.numFaces) BF_HIP_TRY(hipMemcpyAsync(h_faces, r.d_faces, 12 * (size_t)r.numFaces, hipMemcpyDeviceToHost, m->stream));
+    BF_HIP_TRY(hipStreamSynchronize(m->stream));
+    return BF_OK;
+}
+
+// weld of the last extraction + clean (with its normals, which the recolouring needs) + recolour + the optional simplify of the recoloured mesh + download + the
+// PLY writer; m_meshData is not touched.  The file has normals - the written mesh's - if either params struct asks for them.
+int bf_marching_cubes_save_mesh_recoloured(bf_marching_cubes* m, const char* filename, const float transform[16], const bf_mesh_clean_params* cleanParams,
+                                           const bf_mesh_recolour_frame* frames, uint32_t numFrames, uint32_t width, uint32_t height, const float intrinsics[16],
+                                           const bf_mesh_recolour_params* recolourParams, const bf_mesh_simplify_params* simplifyParams, bf_mesh_clean_stats* cleanStats,
+                                           bf_mesh_recolour_stats* recolourStats, bf_mesh_simplify_stats* simplifyStats) {
+    BF_REQUIRE(m && filename && cleanParams && recolourParams && intrinsics, "null argument");
+    bf_mesh_clean_params cp = *cleanParams;
+    const bool wantNormals = cp.computeNormals || (simplifyParams && simplifyParams->computeNormals);
+    cp.computeNormals = 1;
+    BF_TRY(bf_marching_cubes_weld(m, nullptr, 0, transform, nullptr));
+    BF_TRY(bf_marching_cubes_clean(m, nullptr, &cp, nullptr, cleanStats));
+    bf_clean_mesh rm;
+    BF_TRY(bf_marching_cubes_recolour(m, nullptr, frames, numFrames, width, height, intrinsics, recolourParams, &rm, recolourStats));
+    std::vector<float> pos, col, nrm;
+    std::vector<uint32_t> faces;
+    uint32_t nv = rm.numVertices, nf = rm.numFaces;
+    if (simplifyParams) {
+        bf_mesh_simplify_params sp = *simplifyParams;
+        sp.computeNormals = wantNormals ? 1 : 0;
+        bf_indexed_mesh im; im.d_positions = rm.d_positions; im.d_colors = rm.d_colors; im.d_faces = rm.d_faces; im.numVertices = nv; im.numFaces = nf;
+        bf_clean_mesh sm;
+        BF_TRY(bf_marching_cubes_simplify(m, &im, &sp, &sm, simplifyStats));
+        nv = sm.numVertices; nf = sm.numFaces;
+        pos.resize(3 * (size_t)nv); col.resize(3 * (size_t)nv); nrm.resize(wantNormals ? 3 * (size_t)nv : 0); faces.resize(3 * (size_t)nf);
+        BF_TRY(bf_marching_cubes_download_simplified(m, pos.data(), col.data(), nrm.data(), faces.data()));
+    } else {
+        pos.resize(3 * (size_t)nv); col.resize(3 * (size_t)nv); nrm.resize(wantNormals ? 3 * (size_t)nv : 0); faces.resize(3 * (size_t)nf);
+        BF_TRY(bf_marching_cubes_download_recoloured(m, pos.data(), col.data(), wantNormals ? nrm.data() : nullptr, faces.data()));
+    }
+    return bf_write_ply_indexed_normals(filename, pos.data(), wantNormals ? nrm.data() : nullptr, col.data(), faces.data(), nv, nf);
 }
 
 }  // extern "C"

@@ -783,6 +783,58 @@ BF_API int bf_marching_cubes_save_mesh_simplified(bf_marching_cubes* m, const ch
 BF_API int bf_mesh_simplify_host(const float* h_positions, const float* h_colors, const uint32_t* h_faces, uint32_t numVertices, uint32_t numFaces, const bf_mesh_simplify_params* params,
                                  float* h_positionsOut, float* h_colorsOut, float* h_normalsOut, uint32_t* h_facesOut, uint32_t* h_mapOut, uint32_t vertexCapacity,
                                  uint32_t faceCapacity, bf_mesh_simplify_stats* stats);
+/* ---- MI355X additions: the mesh's vertex colours taken from the key frames in HBM (csrc/meshrecolour.hip; DESIGN.md "Mesh colour from the key frames: the
+ * definition"; reference: none, the definition is the library's own) ----
+ * Arithmetic: binary32, one rounding per operation, IEEE division and square root; dot(r, a, b, c, d) = ((r0*a + r1*b) + r2*c) + r3*d.  Intrinsics (4x4
+ * row-major, shared by the frames): fx = K[0], fy = K[5], cx = K[2], cy = K[6].  A (vertex, frame) pair is tested by six rules in order, and the first that fails
+ * names the pair's code (BF_RECOLOUR_*): NORMAL - P and N finite and (N.x*N.x + N.y*N.y) + N.z*N.z > 0; RANGE - p_j = dot(meshToCamera row j, P.x, P.y, P.z, 1),
+ * z = p_2, depthMin <= z <= depthMax; IMAGE - u = (p_0 * fx) / z + cx, v = (p_1 * fy) / z + cy, 0 <= u < (float)(w - 1), 0 <= v < (float)(h - 1), x0 = (int)u,
+ * y0 = (int)v, a = u - (float)x0, b = v - (float)y0, the texels (x0, y0), (x0+1, y0), (x0, y0+1), (x0+1, y0+1); FACING - c = cameraCentre - P,
+ * l = sqrt((c.x*c.x + c.y*c.y) + c.z*c.z) finite and > 0, cosv = BF_RECOLOUR_NORMAL_SIGN * (((N.x*c.x + N.y*c.y) + N.z*c.z) / l) >= minCos; OCCLUDED - with
+ * tol = depthTolerance + depthToleranceLin * z every one of the four depths d is finite, > 0 and has fabsf(d - z) <= tol; COLOUR - none of the four texels has
+ * r == g == b == 0.  A pair that passes all six is a view (code BF_RECOLOUR_VIEW) of weight wgt = (cosv * cosv) / (z * z) and, per channel on the bytes as
+ * floats, sample top = c00 + a * (c10 - c00), bot = c01 + a * (c11 - c01), val = top + b * (bot - top).  Per vertex over the frames in the order given: mode 0
+ * starts from S = (+0, +0, +0), SW = +0, every view does S_c = S_c + wgt * val_c, SW = SW + wgt, and with at least one view and SW finite and > 0 the colour is
+ * (S_c / SW) / 255.0f; mode 1 takes the view of greatest wgt (strictly greater replaces) and the colour is val_c / 255.0f.  A vertex without a view keeps its
+ * input colour bit for bit.  Positions, normals and faces are never written.  No result depends on the order in which threads run. */
+#define BF_RECOLOUR_NORMAL_SIGN (1.0f)       /* the clean's normals point to the side of the cameras that saw the surface (DESIGN.md has the finding) */
+enum { BF_RECOLOUR_VIEW = 0, BF_RECOLOUR_NORMAL = 1, BF_RECOLOUR_RANGE = 2, BF_RECOLOUR_IMAGE = 3, BF_RECOLOUR_FACING = 4, BF_RECOLOUR_OCCLUDED = 5, BF_RECOLOUR_COLOUR = 6 };
+typedef struct bf_mesh_recolour_params { float depthMin, depthMax, depthTolerance, depthToleranceLin, minCos; int32_t mode; } bf_mesh_recolour_params;
+/* numRecoloured + numUnseen == numVertices; numFramesUsed + numFramesSkipped == the frames given; maxViews: the most views of one vertex */
+typedef struct bf_mesh_recolour_stats { uint32_t numVertices, numRecoloured, numUnseen, numFramesUsed, numFramesSkipped, maxViews; } bf_mesh_recolour_stats;
+/* one frame: depth (w x h float, metres) and colour (w x h RGBX8) in device memory (host memory for bf_mesh_recolour_host), mesh to camera (4x4 row-major), the
+ * camera centre in mesh coordinates; skipped != 0: the frame adds nothing (and its pointers are not read) */
+typedef struct bf_mesh_recolour_frame { const float* d_depth; const uint8_t* d_colorRGBX; float meshToCamera[16]; float cameraCentre[3]; int32_t skipped; } bf_mesh_recolour_frame;
+/* Fills meshToCamera = inverse44(cameraToMesh) (the cofactor inverse of the kernels' bf_device.h, evaluated on the host), cameraCentre = (M[3], M[7], M[11]) and
+ * skipped: 1 where M[0] is NaN or -inf (the reference's invalid pose) or any value produced is not finite, 0 otherwise.  The image pointers are left alone.
+ * Host only.  reference: none, the definition is the library's own */
+BF_API int bf_mesh_recolour_frame_from_pose(const float cameraToMesh[16], bf_mesh_recolour_frame* frame);
+/* Recolours the mesh `in` (device arrays of any origin, normals required; NULL: the result of the last clean, or of the last simplify if that is later) from
+ * `frames` on the object's stream, one thread per vertex, and waits for it once.  out: the input's pointers and counts with d_colors replaced by the object's own
+ * colour array, valid until its next extract, weld, clean, simplify, recolour or destroy (no simplify takes it as scratch: a recoloured mesh is a legal input of
+ * bf_marching_cubes_simplify).  Refused with BF_ERR_INVALID_ARG, nothing written and the last result staying: null normals; width or height < 2; a parameter
+ * that is not finite; depthMin <= 0; depthMax < depthMin; a negative tolerance; minCos outside (0, 1]; mode not 0 or 1.  Zero frames or zero vertices give the
+ * input's colours back.  out and stats may be NULL.  reference: none, the definition is the library's own */
+BF_API int bf_marching_cubes_recolour(bf_marching_cubes* m, const bf_clean_mesh* in, const bf_mesh_recolour_frame* frames, uint32_t numFrames, uint32_t width, uint32_t height,
+                                      const float intrinsics[16], const bf_mesh_recolour_params* params, bf_clean_mesh* out, bf_mesh_recolour_stats* stats);
+/* the number of views of every vertex of the last recolour (at most `capacity` of them).  reference: none, the definition is the library's own */
+BF_API int bf_marching_cubes_recolour_views(bf_marching_cubes* m, uint32_t* h_views, uint32_t capacity);
+/* host copies of the last recolour's mesh (any of them may be NULL; h_normals and h_faces come from the input's arrays, which must still be valid).  reference:
+ * none, the definition is the library's own */
+BF_API int bf_marching_cubes_download_recoloured(bf_marching_cubes* m, float* h_positions, float* h_colors, float* h_normals, uint32_t* h_faces);
+/* weld of the last extraction (with the transform) + clean with its normals forced on + recolour + (simplifyParams non-NULL) simplify of the recoloured mesh +
+ * download + PLY.  The file carries normals (those of the mesh that is written) if either params struct asks for them.  The frames' poses are camera to MESH:
+ * the caller has applied the transform to them.  Any stats may be NULL.  reference: none, the definition is the library's own */
+BF_API int bf_marching_cubes_save_mesh_recoloured(bf_marching_cubes* m, const char* filename, const float transform[16], const bf_mesh_clean_params* cleanParams,
+                                                  const bf_mesh_recolour_frame* frames, uint32_t numFrames, uint32_t width, uint32_t height, const float intrinsics[16],
+                                                  const bf_mesh_recolour_params* recolourParams, const bf_mesh_simplify_params* simplifyParams, bf_mesh_clean_stats* cleanStats,
+                                                  bf_mesh_recolour_stats* recolourStats, bf_mesh_simplify_stats* simplifyStats);
+/* The definition on one core (needs no device): host arrays in (the frames' image pointers are host pointers), h_colorsOut numVertices x 3, h_viewsOut
+ * numVertices, h_codesOut numVertices x numFrames rule codes (BF_RECOLOUR_*; a skipped frame's pairs are left alone).  Any output may be NULL.  reference: none,
+ * the definition is the library's own */
+BF_API int bf_mesh_recolour_host(const float* h_positions, const float* h_normals, const float* h_colors, uint32_t numVertices, const bf_mesh_recolour_frame* frames, uint32_t numFrames,
+                                 uint32_t width, uint32_t height, const float intrinsics[16], const bf_mesh_recolour_params* params, float* h_colorsOut, uint32_t* h_viewsOut,
+                                 uint8_t* h_codesOut, bf_mesh_recolour_stats* stats);
 /* the generated case tables (edge mask per case, up to 5 triangles of edge indices, -1 terminated), for inspection / tests */
 BF_API int bf_marching_cubes_tables(uint16_t edgeTable[256], int8_t triTable[256 * 16]);
 

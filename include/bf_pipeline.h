@@ -408,6 +408,23 @@ BF_API int bf_pipeline_save_mesh_clean(bf_pipeline* p, const char* filename, con
 BF_API int bf_pipeline_save_mesh_simplified(bf_pipeline* p, const char* filename, const float* transform, const bf_mesh_clean_params* cleanParams,
                                             const bf_mesh_simplify_params* simplifyParams, bf_mesh_clean_stats* cleanStats, bf_mesh_simplify_stats* simplifyStats,
                                             uint32_t* numTriangles);
+/* The same command with bf_marching_cubes_recolour behind the clean (bf_marching_cubes_save_mesh_recoloured; bf_hip.h has the definition): the vertices' colours
+ * are taken from the stored integration frames 0, frameStride, 2 * frameStride, ... that have a valid optimised pose (bf_pipeline_save_point_cloud's rule), under
+ * the optimised trajectory: camera to mesh is transform * pose (bf_device.h's product; the pose alone without a transform), the intrinsics are those the
+ * integration uses (the colour camera's with the calibration on).  Order: weld with the transform, clean with its normals forced on, recolour, then - with
+ * simplifyParams - the simplification of the recoloured mesh, whose clusters average the sharper colours; the file has normals (those of the mesh that is written)
+ * if either params struct asks for them.  recolourParams NULL: bf_pipeline_get_mesh_recolour_defaults.  The frames are chosen and resolved on the calling thread
+ * after the flush; the command itself is a typed command of the volume thread's queue like the simplified save's.  cleanParams must not be NULL; simplifyParams,
+ * the stats and numTriangles may be.  The same refusal for a sharded volume; the reconstruction is left alone.  reference: none, the definition is the library's own */
+BF_API int bf_pipeline_save_mesh_recoloured(bf_pipeline* p, const char* filename, const float* transform, const bf_mesh_clean_params* cleanParams,
+                                            const bf_mesh_recolour_params* recolourParams, uint32_t frameStride, const bf_mesh_simplify_params* simplifyParams,
+                                            bf_mesh_clean_stats* cleanStats, bf_mesh_recolour_stats* recolourStats, bf_mesh_simplify_stats* simplifyStats, uint32_t* numTriangles);
+/* the recolouring's defaults for this pipeline: depthMin = s_sensorDepthMin, depthMax = s_SDFMaxIntegrationDistance, depthTolerance = 0.01, depthToleranceLin =
+ * 0.01, minCos = 0.3, mode 0 (blend).  reference: none, the definition is the library's own */
+BF_API int bf_pipeline_get_mesh_recolour_defaults(bf_pipeline* p, bf_mesh_recolour_params* params);
+/* the intrinsics (4x4 row-major, at integration resolution) bf_pipeline_save_mesh_recoloured projects with: the colour camera's with the calibration on, the
+ * depth camera's otherwise.  reference: none, the definition is the library's own */
+BF_API int bf_pipeline_get_mesh_recolour_intrinsics(bf_pipeline* p, float K[16]);
 BF_API int bf_pipeline_get_scene(bf_pipeline* p, bf_scene** out);
 BF_API int bf_pipeline_get_image_manager(bf_pipeline* p, bf_image_manager** out);
 BF_API int bf_pipeline_get_online_bundler(bf_pipeline* p, bf_online_bundler** out);

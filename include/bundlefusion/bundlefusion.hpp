@@ -824,6 +824,23 @@ public:
                             bf_mesh_clean_stats* cleanStats = nullptr, bf_mesh_simplify_stats* simplifyStats = nullptr) {
         check(bf_marching_cubes_save_mesh_simplified(m_h, filename.c_str(), transform ? transform->m : nullptr, &cleanParams, &simplifyParams, cleanStats, simplifyStats));
     }
+    // The last clean's (or, if later, the last simplify's) result with its vertex colours taken on the device from `frames` (bf_marching_cubes_recolour; a frame
+    // is filled from its camera-to-mesh pose by bf_mesh_recolour_frame_from_pose): the input's arrays with the object's own colour array, valid until the next
+    // extract, weld, clean, simplify, recolour or destruction.  The mesh needs normals (computeNormals of the clean).
+    bf_clean_mesh recolour(const bf_mesh_recolour_frame* frames, unsigned int numFrames, unsigned int width, unsigned int height, const mat4f& intrinsics,
+                           const bf_mesh_recolour_params& params, bf_mesh_recolour_stats* stats = nullptr) {
+        bf_clean_mesh out;
+        check(bf_marching_cubes_recolour(m_h, nullptr, frames, numFrames, width, height, intrinsics.m, &params, &out, stats));
+        return out;
+    }
+    // saveMeshClean with the cleaned mesh recoloured from `frames` (poses: camera to the TRANSFORMED mesh) and, with simplifyParams, simplified afterwards
+    void saveMeshRecoloured(const std::string& filename, const bf_mesh_clean_params& cleanParams, const bf_mesh_recolour_frame* frames, unsigned int numFrames, unsigned int width,
+                            unsigned int height, const mat4f& intrinsics, const bf_mesh_recolour_params& recolourParams, const bf_mesh_simplify_params* simplifyParams = nullptr,
+                            const mat4f* transform = nullptr, bf_mesh_clean_stats* cleanStats = nullptr, bf_mesh_recolour_stats* recolourStats = nullptr,
+                            bf_mesh_simplify_stats* simplifyStats = nullptr) {
+        check(bf_marching_cubes_save_mesh_recoloured(m_h, filename.c_str(), transform ? transform->m : nullptr, &cleanParams, frames, numFrames, width, height, intrinsics.m, &recolourParams,
+                                                     simplifyParams, cleanStats, recolourStats, simplifyStats));
+    }
     bf_marching_cubes* handle() const { return m_h; }
 private:
     MarchingCubesParams m_params;

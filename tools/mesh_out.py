@@ -3,7 +3,10 @@
 and the seconds of each so that the two can be put side by side.  --mesh-min-faces / --mesh-largest / --mesh-normals clean the mesh before it is written
 (bf_pipeline_save_mesh_clean on the device route, bf_mesh_clean_host on the host route) and print the cleaning's stats.  --mesh-simplify-cell METRES clusters
 the cleaned mesh's vertices on a grid of that size before it is written (bf_pipeline_save_mesh_simplified on the device route, bf_mesh_simplify_host on the host
-route; normals, if asked for, are the simplified mesh's) and prints the simplification's stats and its time."""
+route; normals, if asked for, are the simplified mesh's) and prints the simplification's stats and its time.  --mesh-recolour takes the cleaned mesh's vertex
+colours from the stored frames on --mesh-recolour-stride under the optimised trajectory (bf_pipeline_save_mesh_recoloured on the device route,
+bf_mesh_recolour_host on the host route; --mesh-recolour-best: the best view in place of the blend), before the simplification if one is asked for, and prints
+the recolouring's stats, its time and the mean absolute colour difference across the cleaned mesh's edges before and after, for both modes."""
 import ctypes as C
 import time
 
@@ -19,6 +22,9 @@ def add_arguments(ap):
     ap.add_argument("--mesh-largest", action="store_true", help="keep only the largest connected piece of the mesh")
     ap.add_argument("--mesh-normals", action="store_true", help="write area-weighted per-vertex normals into the PLY")
     ap.add_argument("--mesh-simplify-cell", type=float, default=0.0, metavar="METRES", help="simplify the (cleaned) mesh before it is written: one vertex per grid cell of this size")
+    ap.add_argument("--mesh-recolour", action="store_true", help="take the (cleaned) mesh's vertex colours from the stored frames under the optimised trajectory")
+    ap.add_argument("--mesh-recolour-stride", type=int, default=0, metavar="N", help="recolour from every Nth frame (default: s_submapSize, the key frames)")
+    ap.add_argument("--mesh-recolour-best", action="store_true", help="each vertex takes its best view (greatest weight) instead of the weighted blend of all views")
 
 
 def _cleaning(a):
@@ -35,6 +41,93 @@ def _simplify_line(st):
     return ("%d -> %d vertices, %d -> %d faces; %d clusters, largest %d vertices, %d faces collapsed, %d duplicate"
             % (st["numVerticesIn"], st["numVerticesOut"], st["numFacesIn"], st["numFacesOut"], st["numClusters"], st["largestCluster"], st["numFacesCollapsed"],
                st["numFacesDuplicate"]))
+
+
+def _recolour_line(st):
+    return ("%d of %d vertices recoloured, %d unseen; %d frames used, %d skipped, at most %d views"
+            % (st["numRecoloured"], st["numVertices"], st["numUnseen"], st["numFramesUsed"], st["numFramesSkipped"], st["maxViews"]))
+
+
+def _recolour_params(p, a, mode=None):
+    rp = p.mesh_recolour_defaults()
+    rp.mode = (1 if a.mesh_recolour_best else 0) if mode is None else mode
+    return rp
+
+
+def _stride(p, a):
+    return a.mesh_recolour_stride if a.mesh_recolour_stride > 0 else int(p.gbs.s_submapSize)
+
+
+def edge_colour_difference(col, faces):
+    """the mean over the mesh's edges (every face's three, shared ones once) and the three channels of |colour(a) - colour(b)|"""
+    e = np.concatenate([faces[:, [0, 1]], faces[:, [1, 2]], faces[:, [2, 0]]]).astype(np.int64)
+    e.sort(axis=1)
+    e = np.unique(e, axis=0)
+    return float(np.abs(col[e[:, 0]].astype(np.float64) - col[e[:, 1]].astype(np.float64)).mean()) if len(e) else 0.0
+
+
+def _device_frames(p, a):
+    """the frames bf_pipeline_save_mesh_recoloured uses, as a table of device pointers: (table, intrinsics, width, height)"""
+    lib, check = bf.capi.lib, bf.capi.check
+    host, K, w, h = p.mesh_recolour_frames_host(_stride(p, a), images=False)
+    im = C.c_void_p()
+    check(lib.bf_pipeline_get_image_manager(p._h, C.byref(im)))
+    rows = []
+    for f, W, o, skipped in host:
+        d, c = C.c_void_p(), C.c_void_p()
+        check(lib.bf_image_manager_get_integrate_frame_gpu(im, f, C.byref(d), C.byref(c)))
+        rows.append((d.value, c.value, W, o, skipped))
+    return bf.capi.recolour_frames(rows), K, w, h
+
+
+def _device_stages_recolour(p, path, a):
+    """the stages of the recoloured device route one by one, on an object of their own over the pipeline's scene (the same file again), and the claim: the colour
+    difference across the cleaned mesh's edges before and after, for both modes"""
+    lib, check = bf.capi.lib, bf.capi.check
+    mc = bf.capi.MarchingCubesHashSDF.from_global_app_state(p.gas)
+    t0 = time.perf_counter()
+    mc.extract_gpu(p.scene())
+    t1 = time.perf_counter()
+    check(lib.bf_marching_cubes_weld(mc._h, None, 0, None, None))
+    t2 = time.perf_counter()
+    prm = bf.capi.MeshCleanParams(a.mesh_min_faces, int(a.mesh_largest), 1); cm = bf.capi.CleanMesh(); st = bf.capi.MeshCleanStats()
+    check(lib.bf_marching_cubes_clean(mc._h, None, C.byref(prm), C.byref(cm), C.byref(st)))
+    check(lib.bf_marching_cubes_clean_labels(mc._h, None, 0))                    # waits for the object's stream: the normals' kernels have ended
+    t3 = time.perf_counter()
+    frames, K, w, h = _device_frames(p, a)
+    t4 = time.perf_counter()
+    rm = bf.capi.CleanMesh(); rst = bf.capi.MeshRecolourStats(); rp = _recolour_params(p, a)
+    check(lib.bf_marching_cubes_recolour(mc._h, None, frames, len(frames), w, h, bf.capi.mat16(K), C.byref(rp), C.byref(rm), C.byref(rst)))          # (waits for its stream)
+    t5 = time.perf_counter()
+    pos, col, nrm, faces = mc.download_recoloured(rm.numVertices, rm.numFaces, True)
+    old = np.empty((cm.numVertices, 3), np.float32)
+    check(lib.bf_marching_cubes_download_clean(mc._h, None, old.ctypes.data_as(C.c_void_p), None, None))
+    other = bf.capi.CleanMesh(); orp = _recolour_params(p, a, 1 - rp.mode)
+    check(lib.bf_marching_cubes_recolour(mc._h, None, frames, len(frames), w, h, bf.capi.mat16(K), C.byref(orp), C.byref(other), None))
+    ocol = mc.download_recoloured(rm.numVertices, 0)[1]
+    names = ("blend", "best view")
+    print("mesh colour difference across the cleaned mesh's edges (mean |difference| per channel, colours in [0, 1]): voxel colours %.6f, recoloured (%s) %.6f, recoloured (%s) %.6f"
+          % (edge_colour_difference(old, faces), names[rp.mode], edge_colour_difference(col, faces), names[1 - rp.mode], edge_colour_difference(ocol, faces)))
+    both = faces[(mc.recolour_views(rm.numVertices) > 0)[faces].all(1)]          # (the views of the other mode's run: the same pairs are views in both modes)
+    print("  ... over the edges of the faces whose three vertices have a view: voxel colours %.6f, recoloured (%s) %.6f, recoloured (%s) %.6f"
+          % (edge_colour_difference(old, both), names[rp.mode], edge_colour_difference(col, both), names[1 - rp.mode], edge_colour_difference(ocol, both)))
+    t6 = time.perf_counter()
+    check(lib.bf_marching_cubes_recolour(mc._h, None, frames, len(frames), w, h, bf.capi.mat16(K), C.byref(rp), C.byref(rm), None))
+    t7 = time.perf_counter()
+    if a.mesh_simplify_cell > 0:
+        mc._recoloured = rm
+        spos, scol, snrm, sfaces, sst = mc.simplify_recoloured(a.mesh_simplify_cell, a.mesh_normals)
+        t8 = time.perf_counter()
+        bf.capi.write_ply_indexed_normals(path, spos, snrm, scol, sfaces)
+        t9 = time.perf_counter()
+        print("mesh (device route, stage by stage): extract %.4f s, weld %.4f s, clean + normals %.4f s, frame table %.4f s, recolour %.4f s (again %.4f s), simplify + download %.4f s, write %.4f s"
+              % (t1 - t0, t2 - t1, t3 - t2, t4 - t3, t5 - t4, t7 - t6, t8 - t7, t9 - t8))
+    else:
+        bf.capi.write_ply_indexed_normals(path, pos, nrm if a.mesh_normals else None, col, faces)
+        t8 = time.perf_counter()
+        print("mesh (device route, stage by stage): extract %.4f s, weld %.4f s, clean + normals %.4f s, frame table %.4f s, recolour %.4f s (again %.4f s), write %.4f s"
+              % (t1 - t0, t2 - t1, t3 - t2, t4 - t3, t5 - t4, t7 - t6, t8 - t7))
+    mc.close()
 
 
 def _device_stages(p, path, a):
@@ -96,7 +189,26 @@ def _host(p, path, a):
     nv, nf = mc.save_mesh(path)
     t2 = time.perf_counter()
     print("mesh (host route) %s: %d vertices, %d faces, %d triangles; extract + copy %.3f s, weld + write %.3f s, total %.3f s" % (path, nv, nf, found, t1 - t0, t2 - t1, t2 - t0))
-    if a.mesh_simplify_cell > 0:
+    if a.mesh_recolour:
+        pos, col, faces = mc.weld()
+        t3 = time.perf_counter()
+        cp, cc, cn, cf, st, _ = bf.capi.mesh_clean_host(pos, col, faces, a.mesh_min_faces, a.mesh_largest, True)
+        t4 = time.perf_counter()
+        frames, K, w, h = p.mesh_recolour_frames_host(_stride(p, a))
+        t5 = time.perf_counter()
+        rc, _, rst = bf.capi.mesh_recolour_host(cp, cn, cc, frames, w, h, K, _recolour_params(p, a))
+        t6 = time.perf_counter()
+        print("mesh (host route) cleaned on one core: %s; clean %.3f s" % (_stats_line(st), t4 - t3))
+        print("mesh (host route) recoloured on one core: %s; frames to the host %.3f s, recolour %.3f s" % (_recolour_line(rst), t5 - t4, t6 - t5))
+        if a.mesh_simplify_cell > 0:
+            sp, sc_, sn, sf, sst, _ = bf.capi.mesh_simplify_host(cp, rc, cf, a.mesh_simplify_cell, a.mesh_normals)
+            t7 = time.perf_counter()
+            bf.capi.write_ply_indexed_normals(path, sp, sn, sc_, sf)
+            print("mesh (host route) simplified on one core: %s; simplify %.3f s, write %.3f s" % (_simplify_line(sst), t7 - t6, time.perf_counter() - t7))
+        else:
+            bf.capi.write_ply_indexed_normals(path, cp, cn if a.mesh_normals else None, rc, cf)
+            print("mesh (host route) write %.3f s" % (time.perf_counter() - t6))
+    elif a.mesh_simplify_cell > 0:
         pos, col, faces = mc.weld()
         t3 = time.perf_counter()
         cp, cc, _, cf, st, _ = bf.capi.mesh_clean_host(pos, col, faces, a.mesh_min_faces, a.mesh_largest, False)
@@ -122,6 +234,16 @@ def write(p, a):
     """p: the Pipeline after process_end_of_sequence / synchronize; a: the parsed arguments"""
     if a.mesh:
         t0 = time.perf_counter()
+        if a.mesh_recolour:
+            st, rst, sst, nt = p.save_mesh_recoloured(a.mesh, None, a.mesh_min_faces, a.mesh_largest, a.mesh_normals, _recolour_params(p, a), _stride(p, a),
+                                                      a.mesh_simplify_cell if a.mesh_simplify_cell > 0 else None)
+            dt = time.perf_counter() - t0
+            print("mesh (device route) %s: %d triangles; cleaned: %s; recoloured: %s;%s bf_pipeline_save_mesh_recoloured %.3f s"
+                  % (a.mesh, nt, _stats_line(st), _recolour_line(rst), " simplified at %g m: %s;" % (a.mesh_simplify_cell, _simplify_line(sst)) if sst else "", dt))
+            _device_stages_recolour(p, a.mesh, a)
+            if a.mesh_host:
+                _host(p, a.mesh_host, a)
+            return
         if a.mesh_simplify_cell > 0:
             st, sst, nt = p.save_mesh_simplified(a.mesh, a.mesh_simplify_cell, None, a.mesh_min_faces, a.mesh_largest, a.mesh_normals)
             dt = time.perf_counter() - t0

@@ -10,6 +10,9 @@ largest piece kept, per-vertex normals added to the PLY - on the device with --m
 (bf_mesh_clean_host); both print the cleaning's stats.
 --mesh-simplify-cell METRES: simplify the cleaned mesh before it is written, one vertex per grid cell of that size (bf_pipeline_save_mesh_simplified with --mesh,
 bf_mesh_simplify_host with --mesh-host); both print the simplification's stats and its time.
+--mesh-recolour [--mesh-recolour-stride N] [--mesh-recolour-best]: take the cleaned mesh's vertex colours from the stored frames on the stride (default
+s_submapSize: the key frames) under the optimised trajectory, before the simplification if there is one (bf_pipeline_save_mesh_recoloured with --mesh,
+bf_mesh_recolour_host with --mesh-host); both print the recolouring's stats and its time.
 --point-cloud FILE [--point-cloud-stride N --point-cloud-cell M]: the stored frames on the stride (default s_submapSize: the key frames) under the optimised
 trajectory as a coloured, oriented point cloud, one point per cell of M metres (default 0.005), thinned on the device (bf_pipeline_save_point_cloud);
 --point-cloud-host FILE: the same file by the host route on one core.  Both print frame and point counts and the seconds spent.
