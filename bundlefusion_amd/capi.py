@@ -711,6 +711,16 @@ class SiftManager:
     def match(self, cur, start, num, dist_max=0.7, ratio_max=0.8):
         check(lib.bf_siftmgr_match(self._h, cur, start, num, C.c_float(dist_max), C.c_float(ratio_max)))
 
+    def set_pair_stage(self, set, stream_ptr=None, speculative=0):
+        """The pair kernels issued from now on work on result set `set` (0 / 1) and on the HIP stream `stream_ptr` (None: the manager's stream); speculative:
+        they do not consult the valid flags of the previous images (commit_pairs clears those pairs afterwards).  The accessors of the per-pair lists name the
+        selected set; ordering between the two streams is the caller's.  (0, None, 0) is the reference's behaviour."""
+        check(lib.bf_siftmgr_set_pair_stage(self._h, int(set), None if stream_ptr is None else C.c_void_p(stream_ptr), int(speculative)))
+
+    def commit_pairs(self, cur, start, num):
+        """On the manager's stream: zero the raw and filtered match counts (of the selected set) of the invalid previous images in [start, num)."""
+        check(lib.bf_siftmgr_commit_pairs(self._h, cur, start, num))
+
     def filter_keypoint_matches(self, cur, start, num, Kinv, min_matches=5, max_res2=0.0004):
         check(lib.bf_siftmgr_filter_keypoint_matches(self._h, cur, start, num, _f16(Kinv), min_matches, C.c_float(max_res2)))
 
