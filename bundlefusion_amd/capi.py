@@ -1519,6 +1519,26 @@ class Pipeline:
                                                    None if sp is None else C.byref(sp), C.byref(st), C.byref(rst), C.byref(sst), C.byref(nt)))
         return st.as_dict(), rst.as_dict(), (None if sp is None else sst.as_dict()), nt.value
 
+    def mesh_texture_defaults(self):
+        """bf_pipeline_get_mesh_texture_defaults: the MeshTextureParams the pipeline uses where none are given"""
+        tp = MeshTextureParams()
+        check(lib.bf_pipeline_get_mesh_texture_defaults(self._h, C.byref(tp)))
+        return tp
+
+    def save_mesh_textured(self, filename, transform=None, min_faces=0, largest=False, normals=False, params=None, frame_stride=None, recolour_first=False, cell_size=None):
+        """bf_pipeline_save_mesh_textured: save_mesh_clean, then (recolour_first) the recolouring with the pipeline's defaults, then (cell_size given) the
+        simplification, then the texture atlas of the mesh that is written from the stored frames on the stride: the PLY at filename and the atlas as a PNG next
+        to it (the extension replaced by .png).  params None: mesh_texture_defaults(); frame_stride None: s_submapSize.  Returns (clean stats dict, recolour stats
+        dict or None, simplify stats dict or None, texture stats dict, triangles)."""
+        p = MeshCleanParams(int(min_faces), int(bool(largest)), int(bool(normals)))
+        sp = None if cell_size is None else MeshSimplifyParams(float(cell_size), int(bool(normals)))
+        st = MeshCleanStats(); rst = MeshRecolourStats(); sst = MeshSimplifyStats(); tst = MeshTextureStats(); nt = C.c_uint32()
+        T = mat16(transform) if transform is not None else None
+        stride = int(self.gbs.s_submapSize) if frame_stride is None else int(frame_stride)
+        check(lib.bf_pipeline_save_mesh_textured(self._h, str(filename).encode(), T, C.byref(p), None if params is None else C.byref(params), stride, int(bool(recolour_first)),
+                                                 None if sp is None else C.byref(sp), C.byref(st), C.byref(rst), C.byref(sst), C.byref(tst), C.byref(nt)))
+        return st.as_dict(), (rst.as_dict() if recolour_first else None), (None if sp is None else sst.as_dict()), tst.as_dict(), nt.value
+
     def save_point_cloud(self, filename, frame_stride=None, cell_size=0.005, max_depth=3.5, max_points=0):
         """bf_pipeline_save_point_cloud: the stored frames on the stride under the optimised trajectory as a thinned point cloud PLY, built on the device.
         frame_stride None: s_submapSize (the key frames).  Returns (points, frames used)."""
@@ -1854,6 +1874,88 @@ class MarchingCubesHashSDF:
         check(lib.bf_marching_cubes_save_mesh_recoloured(self._h, str(filename).encode(), T, C.byref(p), frames, len(frames), int(width), int(height), mat16(intrinsics), C.byref(params),
                                                          None if sp is None else C.byref(sp), C.byref(st), C.byref(rst), C.byref(sst)))
         return st.as_dict(), rst.as_dict(), (None if sp is None else sst.as_dict())
+
+    # ---- MI355X additions: a texture atlas for the mesh from the key frames in HBM (csrc/meshtexture.hip)
+    def texture(self, mesh, frames, width, height, intrinsics, params):
+        """bf_marching_cubes_texture + download: (atlas [H,A,4] uint8, faceFrame [nf] int32, faceUV [nf,6] float32, stats dict).  mesh: (positions, colours, faces) as
+        contiguous torch cuda tensors, or None for the last clean (or the last simplify if later); frames: a recolour_frames() array whose images are device
+        pointers; params: a MeshTextureParams."""
+        st = MeshTextureStats()
+        K = mat16(intrinsics)
+        if mesh is None:
+            check(lib.bf_marching_cubes_texture(self._h, None, frames, len(frames), int(width), int(height), K, C.byref(params), C.byref(st)))
+        else:
+            pos, col, faces = mesh
+            assert pos.is_contiguous() and col.is_contiguous() and faces.is_contiguous() and pos.numel() == col.numel() and pos.numel() % 3 == 0 and faces.numel() % 3 == 0
+            m = CleanMesh(pos.data_ptr() or None, col.data_ptr() or None, None, faces.data_ptr() or None, pos.numel() // 3, faces.numel() // 3)
+            check(lib.bf_marching_cubes_texture(self._h, C.byref(m), frames, len(frames), int(width), int(height), K, C.byref(params), C.byref(st)))
+        return self.download_texture(st.atlasWidth, st.atlasHeight, st.numFaces) + (st.as_dict(),)
+
+    def download_texture(self, atlas_width, atlas_height, nf):
+        """bf_marching_cubes_download_texture: (atlas, faceFrame, faceUV) of the last texture, whose sizes the caller knows"""
+        atlas = np.zeros((atlas_height, atlas_width, 4), np.uint8); ff = np.zeros(nf, np.int32); uv = np.zeros((nf, 6), np.float32)
+        check(lib.bf_marching_cubes_download_texture(self._h, atlas.ctypes.data_as(C.c_void_p), ff.ctypes.data_as(C.c_void_p), uv.ctypes.data_as(C.c_void_p)))
+        return atlas, ff, uv
+
+    def save_mesh_textured(self, filename, frames, width, height, intrinsics, params, transform=None, min_faces=0, largest=False, normals=False, recolour_params=None, cell_size=None):
+        """weld of the last extraction + clean (+ recolour with recolour_params, + simplify on a grid of cell_size) + texture on the device + the PLY and the PNG
+        next to it: (clean stats dict, recolour stats dict or None, simplify stats dict or None, texture stats dict).  The frames' poses are camera to mesh: the
+        transform already applied."""
+        p = MeshCleanParams(int(min_faces), int(bool(largest)), int(bool(normals)))
+        sp = None if cell_size is None else MeshSimplifyParams(float(cell_size), int(bool(normals)))
+        st = MeshCleanStats(); rst = MeshRecolourStats(); sst = MeshSimplifyStats(); tst = MeshTextureStats()
+        T = mat16(transform) if transform is not None else None
+        check(lib.bf_marching_cubes_save_mesh_textured(self._h, str(filename).encode(), T, C.byref(p), frames, len(frames), int(width), int(height), mat16(intrinsics), C.byref(params),
+                                                       None if recolour_params is None else C.byref(recolour_params), None if sp is None else C.byref(sp), C.byref(st), C.byref(rst),
+                                                       C.byref(sst), C.byref(tst)))
+        return st.as_dict(), (None if recolour_params is None else rst.as_dict()), (None if sp is None else sst.as_dict()), tst.as_dict()
+
+
+class MeshTextureParams(C.Structure):
+    _fields_ = [("depthMin", C.c_float), ("depthMax", C.c_float), ("depthTolerance", C.c_float), ("depthToleranceLin", C.c_float), ("minCos", C.c_float), ("patchSize", C.c_uint32),
+                ("atlasWidth", C.c_uint32)]
+
+
+class MeshTextureStats(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("numFaces", "numFacesTextured", "numFacesUntextured", "numFramesUsed", "numFramesSkipped", "atlasWidth", "atlasHeight")] + \
+               [(n, C.c_uint64) for n in ("numTexelsFromFrames", "numTexelsFromVertices", "numTexelsUnused")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+def mesh_texture_atlas_height(num_faces, params):
+    """bf_mesh_texture_atlas_height: the atlas height of the layout for num_faces faces.  Host-only."""
+    h = C.c_uint32()
+    check(lib.bf_mesh_texture_atlas_height(int(num_faces), C.byref(params), C.byref(h)))
+    return h.value
+
+
+def mesh_texture_host(positions, colors, faces, frames, width, height, intrinsics, params):
+    """bf_mesh_texture_host, the definition on one core: (atlas [H,A,4] uint8, faceFrame [nf] int32, faceUV [nf,6] float32, stats dict).  frames: (depth [h,w]
+    float32, colour [h,w,4] uint8, meshToCamera, cameraCentre, skipped) tuples of host arrays.  Host-only."""
+    pos = np.ascontiguousarray(positions, np.float32).reshape(-1, 3); col = np.ascontiguousarray(colors, np.float32).reshape(-1, 3)
+    fc = np.ascontiguousarray(faces, np.uint32).reshape(-1, 3)
+    keep = [(np.ascontiguousarray(d, np.float32), np.ascontiguousarray(c, np.uint8)) for d, c, _, _, _ in frames]
+    for d, c in keep:
+        assert d.shape == (height, width) and c.shape == (height, width, 4)
+    fr = recolour_frames([(d.ctypes.data, c.ctypes.data, W, o, s) for (d, c), (_, _, W, o, s) in zip(keep, frames)])
+    st = MeshTextureStats()
+    K = mat16(intrinsics)
+    atlas = np.zeros((mesh_texture_atlas_height(len(fc), params), int(params.atlasWidth), 4), np.uint8); ff = np.zeros(len(fc), np.int32); uv = np.zeros((len(fc), 6), np.float32)
+    check(lib.bf_mesh_texture_host(pos.ctypes.data_as(C.c_void_p), col.ctypes.data_as(C.c_void_p), fc.ctypes.data_as(C.c_void_p), len(pos), len(fc), fr, len(frames), int(width), int(height), K,
+                                   C.byref(params), atlas.ctypes.data_as(C.c_void_p), ff.ctypes.data_as(C.c_void_p), uv.ctypes.data_as(C.c_void_p), C.byref(st)))
+    return atlas, ff, uv, st.as_dict()
+
+
+def write_ply_textured(filename, texture_name, positions, normals, colors, faces, face_uv):
+    """bf_write_ply_textured: the PLY of an indexed mesh with per-face texture coordinates ([nf,6] float32) into the picture texture_name.  Host-only."""
+    pos = np.ascontiguousarray(positions, np.float32).reshape(-1, 3); col = np.ascontiguousarray(colors, np.float32).reshape(-1, 3)
+    nrm = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    fc = np.ascontiguousarray(faces, np.uint32).reshape(-1, 3); uv = np.ascontiguousarray(face_uv, np.float32).reshape(-1, 6)
+    assert len(uv) == len(fc) and len(col) == len(pos) and (nrm is None or len(nrm) == len(pos))
+    check(lib.bf_write_ply_textured(str(filename).encode(), str(texture_name).encode(), pos.ctypes.data_as(C.c_void_p), None if nrm is None else nrm.ctypes.data_as(C.c_void_p),
+                                    col.ctypes.data_as(C.c_void_p), fc.ctypes.data_as(C.c_void_p), uv.ctypes.data_as(C.c_void_p), len(pos), len(fc)))
 
 
 class MeshRecolourParams(C.Structure):

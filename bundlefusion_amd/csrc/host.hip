@@ -2578,6 +2578,8 @@ struct PlMeshJob {
     const bf_mesh_simplify_params* simplify; bf_mesh_simplify_stats* simplifyStats;
     // recolour non-null (with clean): the recoloured save, its frames resolved by the poster; simplify is optional behind it
     const bf_mesh_recolour_params* recolour; bf_mesh_recolour_stats* recolourStats; const bf_mesh_recolour_frame* frames; uint32_t numFrames; const float* intrinsics;
+    // texture non-null (with clean): the textured save from the same frames; recolour and simplify are optional before it
+    const bf_mesh_texture_params* texture; bf_mesh_texture_stats* textureStats;
 };
 
 // on the volume thread (timings: on the calling thread), between two batches.  The view's exclusive section is a render's: the preparation stream has finished
@@ -2591,7 +2593,10 @@ int plMeshExec(void* ctx) {
     BF_TRY(bf_scene_begin_view(p->scene, I, &p->cam, &hd, &hp));
     int rc = bf_marching_cubes_extract_gpu(p->marchingCubes, &hd, &hp, nullptr, nullptr, 0);
     if (rc == BF_OK) rc = bf_marching_cubes_get_triangles_gpu(p->marchingCubes, nullptr, nullptr, &j.nt);
-    if (rc == BF_OK && j.recolour)
+    if (rc == BF_OK && j.texture)
+        rc = bf_marching_cubes_save_mesh_textured(p->marchingCubes, j.filename, j.transform, j.clean, j.frames, j.numFrames, p->im->wInt, p->im->hInt, j.intrinsics, j.texture, j.recolour,
+                                                  j.simplify, j.stats, j.recolourStats, j.simplifyStats, j.textureStats);
+    else if (rc == BF_OK && j.recolour)
         rc = bf_marching_cubes_save_mesh_recoloured(p->marchingCubes, j.filename, j.transform, j.clean, j.frames, j.numFrames, p->im->wInt, p->im->hInt, j.intrinsics, j.recolour, j.simplify,
                                                     j.stats, j.recolourStats, j.simplifyStats);
     else if (rc == BF_OK) rc = j.simplify ? bf_marching_cubes_save_mesh_simplified(p->marchingCubes, j.filename, j.transform, j.clean, j.simplify, j.stats, j.simplifyStats)
@@ -2616,7 +2621,7 @@ static int plSaveMesh(bf_pipeline* p, PlMeshJob& j) {
         BF_TRY(bf_marching_cubes_set_stream(p->marchingCubes, p->sVolume));
     }
     VolumeQueue::Cmd c;
-    c.op = j.recolour ? VolumeQueue::Op::SaveMeshRecoloured : j.simplify ? VolumeQueue::Op::SaveMeshSimplified : VolumeQueue::Op::SaveMesh; c.render = plMeshExec; c.renderCtx = &j;
+    c.op = j.texture ? VolumeQueue::Op::SaveMeshTextured : j.recolour ? VolumeQueue::Op::SaveMeshRecoloured : j.simplify ? VolumeQueue::Op::SaveMeshSimplified : VolumeQueue::Op::SaveMesh; c.render = plMeshExec; c.renderCtx = &j;
     return p->vol.postAndWait(c);
 }
 
@@ -2665,16 +2670,9 @@ int bf_pipeline_get_mesh_recolour_intrinsics(bf_pipeline* p, float K[16]) {
     return BF_OK;
 }
 
-// ... and with bf_marching_cubes_recolour behind the clean, the optional simplify behind that (bf_marching_cubes_save_mesh_recoloured).  The frames are chosen and
-// resolved here, on the calling thread: bf_pipeline_save_point_cloud's rule over the optimised trajectory.
-int bf_pipeline_save_mesh_recoloured(bf_pipeline* p, const char* filename, const float* transform, const bf_mesh_clean_params* cleanParams, const bf_mesh_recolour_params* recolourParams,
-                                     uint32_t frameStride, const bf_mesh_simplify_params* simplifyParams, bf_mesh_clean_stats* cleanStats, bf_mesh_recolour_stats* recolourStats,
-                                     bf_mesh_simplify_stats* simplifyStats, uint32_t* numTriangles) {
-    BF_REQUIRE(p && filename && cleanParams, "null argument");
-    BF_REQUIRE(frameStride >= 1, "the frame stride must be at least 1");
-    BF_REQUIRE(!p->volumeSharded && !p->volumeComm, "the volume is sharded over ranks (bf_pipeline_set_volume_shard / _set_comm): a shard lacks its neighbours' blocks, meshing across ranks is not supported");
-    bf_mesh_recolour_params rp;
-    if (recolourParams) rp = *recolourParams; else BF_TRY(bf_pipeline_get_mesh_recolour_defaults(p, &rp));
+// the frames a recoloured or textured save takes its colours from, chosen and resolved on the calling thread after a flush: bf_pipeline_save_point_cloud's rule
+// over the optimised trajectory, camera to mesh = transform * pose
+static int plMeshFrames(bf_pipeline* p, const float* transform, uint32_t frameStride, std::vector<bf_mesh_recolour_frame>& frames) {
     BF_TRY(plFlush(p));
     bf_trajectory_manager* tm = nullptr;
     BF_TRY(bf_online_bundler_get_trajectory_manager(p->ob, &tm));
@@ -2685,7 +2683,6 @@ int bf_pipeline_save_mesh_recoloured(bf_pipeline* p, const char* filename, const
     count = std::min(count, p->im->currFrame);
     m44 X = identity44();
     if (transform) memcpy(X.e, transform, 64);
-    std::vector<bf_mesh_recolour_frame> frames;
     for (uint32_t f = 0; f < count; f += frameStride) {
         const float* Tf = T.data() + 16 * (size_t)f;
         if (Tf[0] != Tf[0] || Tf[0] == NINF) continue;
@@ -2696,9 +2693,56 @@ int bf_pipeline_save_mesh_recoloured(bf_pipeline* p, const char* filename, const
         BF_TRY(bf_mesh_recolour_frame_from_pose(M.e, &fr));
         frames.push_back(fr);
     }
+    return BF_OK;
+}
+
+// ... and with bf_marching_cubes_recolour behind the clean, the optional simplify behind that (bf_marching_cubes_save_mesh_recoloured); the frames: plMeshFrames.
+int bf_pipeline_save_mesh_recoloured(bf_pipeline* p, const char* filename, const float* transform, const bf_mesh_clean_params* cleanParams, const bf_mesh_recolour_params* recolourParams,
+                                     uint32_t frameStride, const bf_mesh_simplify_params* simplifyParams, bf_mesh_clean_stats* cleanStats, bf_mesh_recolour_stats* recolourStats,
+                                     bf_mesh_simplify_stats* simplifyStats, uint32_t* numTriangles) {
+    BF_REQUIRE(p && filename && cleanParams, "null argument");
+    BF_REQUIRE(frameStride >= 1, "the frame stride must be at least 1");
+    BF_REQUIRE(!p->volumeSharded && !p->volumeComm, "the volume is sharded over ranks (bf_pipeline_set_volume_shard / _set_comm): a shard lacks its neighbours' blocks, meshing across ranks is not supported");
+    bf_mesh_recolour_params rp;
+    if (recolourParams) rp = *recolourParams; else BF_TRY(bf_pipeline_get_mesh_recolour_defaults(p, &rp));
+    std::vector<bf_mesh_recolour_frame> frames;
+    BF_TRY(plMeshFrames(p, transform, frameStride, frames));
     float K[16];
     BF_TRY(bf_pipeline_get_mesh_recolour_intrinsics(p, K));
     PlMeshJob j = {p, filename, transform, 0, 0, 0, cleanParams, cleanStats, simplifyParams, simplifyStats, &rp, recolourStats, frames.data(), (uint32_t)frames.size(), K};
+    BF_TRY(plSaveMesh(p, j));
+    if (numTriangles) *numTriangles = j.nt;
+    return BF_OK;
+}
+
+// The texture's defaults: the recolouring's five floats, patches of 8 x 8 texels in an atlas 8192 wide (starting points, not measured optima: DESIGN.md "Mesh texture")
+int bf_pipeline_get_mesh_texture_defaults(bf_pipeline* p, bf_mesh_texture_params* params) {
+    BF_REQUIRE(p && params, "null argument");
+    bf_mesh_recolour_params rp;
+    BF_TRY(bf_pipeline_get_mesh_recolour_defaults(p, &rp));
+    params->depthMin = rp.depthMin; params->depthMax = rp.depthMax; params->depthTolerance = rp.depthTolerance; params->depthToleranceLin = rp.depthToleranceLin; params->minCos = rp.minCos;
+    params->patchSize = 8; params->atlasWidth = 8192;
+    return BF_OK;
+}
+
+// ... and with bf_marching_cubes_texture at the end (bf_marching_cubes_save_mesh_textured): clean, the optional recolour with the pipeline's defaults, the optional
+// simplify, the atlas; the same frames, poses and intrinsics as the recoloured save.
+int bf_pipeline_save_mesh_textured(bf_pipeline* p, const char* filename, const float* transform, const bf_mesh_clean_params* cleanParams, const bf_mesh_texture_params* textureParams,
+                                   uint32_t frameStride, int recolourFirst, const bf_mesh_simplify_params* simplifyParams, bf_mesh_clean_stats* cleanStats,
+                                   bf_mesh_recolour_stats* recolourStats, bf_mesh_simplify_stats* simplifyStats, bf_mesh_texture_stats* textureStats, uint32_t* numTriangles) {
+    BF_REQUIRE(p && filename && cleanParams, "null argument");
+    BF_REQUIRE(frameStride >= 1, "the frame stride must be at least 1");
+    BF_REQUIRE(!p->volumeSharded && !p->volumeComm, "the volume is sharded over ranks (bf_pipeline_set_volume_shard / _set_comm): a shard lacks its neighbours' blocks, meshing across ranks is not supported");
+    bf_mesh_texture_params tp;
+    if (textureParams) tp = *textureParams; else BF_TRY(bf_pipeline_get_mesh_texture_defaults(p, &tp));
+    bf_mesh_recolour_params rp;
+    BF_TRY(bf_pipeline_get_mesh_recolour_defaults(p, &rp));
+    std::vector<bf_mesh_recolour_frame> frames;
+    BF_TRY(plMeshFrames(p, transform, frameStride, frames));
+    float K[16];
+    BF_TRY(bf_pipeline_get_mesh_recolour_intrinsics(p, K));
+    PlMeshJob j = {p, filename, transform, 0, 0, 0, cleanParams, cleanStats, simplifyParams, simplifyStats, recolourFirst ? &rp : nullptr, recolourStats, frames.data(), (uint32_t)frames.size(), K,
+                   &tp, textureStats};
     BF_TRY(plSaveMesh(p, j));
     if (numTriangles) *numTriangles = j.nt;
     return BF_OK;

@@ -29,12 +29,14 @@
 #include <unordered_set>
 #include <vector>
 
+#include "../../include/bf_render.h"
 #include "bf_device.h"
 #include "bf_resources.h"
 #include "bf_meshweld.h"
 #include "bf_meshclean.h"
 #include "bf_meshsimplify.h"
 #include "bf_meshrecolour.h"
+#include "bf_meshtexture.h"
 #include "bf_volume.h"
 
 using namespace bf;
@@ -318,8 +320,9 @@ struct bf_marching_cubes {
     MeshClean clean;                    // the cleaned mesh of the last bf_marching_cubes_clean, in HBM (meshclean.hip)
     MeshSimplify simplify;              // the simplified mesh of the last bf_marching_cubes_simplify, in HBM (meshsimplify.hip)
     MeshRecolour recolour;              // the colours of the last bf_marching_cubes_recolour, in HBM (meshrecolour.hip)
-    int lastMesh = 0;                   // bf_marching_cubes_recolour's default input: 0 none, 1 the last clean, 2 the last simplify (whichever ran later)
-    bf::Resources res;                  // owns every buffer above, the weld's, the clean's, the simplification's and the recolouring's included
+    MeshTexture texture;                // the atlas, face frames and texture coordinates of the last bf_marching_cubes_texture, in HBM (meshtexture.hip)
+    int lastMesh = 0;                   // bf_marching_cubes_recolour's and _texture's default input: 0 none, 1 the last clean, 2 the last simplify (whichever ran later)
+    bf::Resources res;                  // owns every buffer above, the weld's, the clean's, the simplification's, the recolouring's and the texture's included
 };
 
 extern "C" {
@@ -390,6 +393,7 @@ static int mcExtract(bf_marching_cubes* m, const bf_hash_data* hd, const bf_hash
     BF_HIP_TRY(hipStreamSynchronize(st));
     m->numTriangles = m->numTrianglesFound = 0;
     m->recolour.numVertices = m->recolour.numFaces = 0;          // the last recolour's mesh is gone with the extraction it came from
+    m->texture.numFaces = m->texture.atlasWidth = m->texture.atlasHeight = 0;          // ... and the last texture
     if (nb == 0) return BF_OK;
     const uint32_t grid = std::min(nb, 8192u);
     hipLaunchKernelGGL(k_mc_blocks<false>, dim3(grid), dim3(512), 0, st, a, (const McTables*)m->d_tables, (const uint32_t*)m->d_slots, (const uint32_t*)m->d_numBlocks,
@@ -498,6 +502,7 @@ int bf_marching_cubes_weld(bf_marching_cubes* m, const bf_mc_triangle* d_triangl
     BF_REQUIRE(m, "null argument");
     if (!d_triangles) { d_triangles = m->d_triangles; numTriangles = m->numTriangles; }
     m->recolour.numVertices = m->recolour.numFaces = 0;          // a recolour's result ends here: the arrays it points into may be regrown
+    m->texture.numFaces = m->texture.atlasWidth = m->texture.atlasHeight = 0;          // a texture's too: its faces are another mesh's
     BF_TRY(meshweld_run(m->weld, m->res, m->stream, d_triangles, numTriangles, transform));
     if (out) { out->d_positions = m->weld.d_positions; out->d_colors = m->weld.d_colors; out->d_faces = m->weld.d_faces; out->numVertices = m->weld.numVertices; out->numFaces = m->weld.numFaces; }
     return BF_OK;
@@ -533,6 +538,7 @@ int bf_marching_cubes_clean(bf_marching_cubes* m, const bf_indexed_mesh* in, con
     bf_indexed_mesh last;
     last.d_positions = m->weld.d_positions; last.d_colors = m->weld.d_colors; last.d_faces = m->weld.d_faces; last.numVertices = m->weld.numVertices; last.numFaces = m->weld.numFaces;
     m->recolour.numVertices = m->recolour.numFaces = 0;          // (as the weld)
+    m->texture.numFaces = m->texture.atlasWidth = m->texture.atlasHeight = 0;
     BF_TRY(meshclean_run(m->clean, m->res, m->stream, in ? *in : last, *params, stats));
     m->lastMesh = 1;
     const MeshClean& c = m->clean;
@@ -577,6 +583,7 @@ int bf_marching_cubes_simplify(bf_marching_cubes* m, const bf_indexed_mesh* in, 
     BF_REQUIRE(in || m->clean.hasResult, "no input mesh and no result of a clean to take");
     bf_indexed_mesh last;
     last.d_positions = m->clean.d_positions; last.d_colors = m->clean.d_colors; last.d_faces = m->clean.d_faces; last.numVertices = m->clean.numVertices; last.numFaces = m->clean.numFaces;
+    m->texture.numFaces = m->texture.atlasWidth = m->texture.atlasHeight = 0;          // (as the weld)
     BF_TRY(meshsimplify_run(m->simplify, m->res, m->stream, in ? *in : last, *params, stats));
     m->lastMesh = 2;
     const MeshSimplify& s = m->simplify;
@@ -621,11 +628,8 @@ int bf_marching_cubes_save_mesh_simplified(bf_marching_cubes* m, const char* fil
     return bf_write_ply_indexed_normals(filename, pos.data(), sm.d_normals ? nrm.data() : nullptr, col.data(), faces.data(), sm.numVertices, sm.numFaces);
 }
 
-// Vertex colours from the key frames over a mesh in HBM (meshrecolour.hip); in null: the last clean's result, or the last simplify's if that ran later.  On the object's stream.
-int bf_marching_cubes_recolour(bf_marching_cubes* m, const bf_clean_mesh* in, const bf_mesh_recolour_frame* frames, uint32_t numFrames, uint32_t width, uint32_t height,
-                               const float intrinsics[16], const bf_mesh_recolour_params* params, bf_clean_mesh* out, bf_mesh_recolour_stats* stats) {
-    BF_REQUIRE(m && params && intrinsics, "null argument");
-    BF_REQUIRE(in || m->lastMesh, "no input mesh and no result of a clean or a simplify to take");
+// the result of the last clean, or of the last simplify if that ran later
+static bf_clean_mesh mcLastMesh(const bf_marching_cubes* m) {
     bf_clean_mesh last;
     if (m->lastMesh == 2) {
         const MeshSimplify& s = m->simplify;
@@ -634,6 +638,15 @@ int bf_marching_cubes_recolour(bf_marching_cubes* m, const bf_clean_mesh* in, co
         const MeshClean& c = m->clean;
         last.d_positions = c.d_positions; last.d_colors = c.d_colors; last.d_normals = c.hasNormals ? c.normals.d_normals : nullptr; last.d_faces = c.d_faces; last.numVertices = c.numVertices; last.numFaces = c.numFaces;
     }
+    return last;
+}
+
+// Vertex colours from the key frames over a mesh in HBM (meshrecolour.hip); in null: the last clean's result, or the last simplify's if that ran later.  On the object's stream.
+int bf_marching_cubes_recolour(bf_marching_cubes* m, const bf_clean_mesh* in, const bf_mesh_recolour_frame* frames, uint32_t numFrames, uint32_t width, uint32_t height,
+                               const float intrinsics[16], const bf_mesh_recolour_params* params, bf_clean_mesh* out, bf_mesh_recolour_stats* stats) {
+    BF_REQUIRE(m && params && intrinsics, "null argument");
+    BF_REQUIRE(in || m->lastMesh, "no input mesh and no result of a clean or a simplify to take");
+    const bf_clean_mesh last = mcLastMesh(m);
     const bf_clean_mesh& src = in ? *in : last;
     BF_TRY(meshrecolour_run(m->recolour, m->res, m->stream, src, frames, numFrames, width, height, intrinsics, *params, stats));
     if (out) { *out = src; out->d_colors = m->recolour.d_colors; }
@@ -690,6 +703,68 @@ int bf_marching_cubes_save_mesh_recoloured(bf_marching_cubes* m, const char* fil
         BF_TRY(bf_marching_cubes_download_recoloured(m, pos.data(), col.data(), wantNormals ? nrm.data() : nullptr, faces.data()));
     }
     return bf_write_ply_indexed_normals(filename, pos.data(), wantNormals ? nrm.data() : nullptr, col.data(), faces.data(), nv, nf);
+}
+
+// A texture atlas from the key frames for a mesh in HBM (meshtexture.hip); in null: the last clean's result, or the last simplify's if that ran later.  On the object's stream.
+int bf_marching_cubes_texture(bf_marching_cubes* m, const bf_clean_mesh* in, const bf_mesh_recolour_frame* frames, uint32_t numFrames, uint32_t width, uint32_t height,
+                              const float intrinsics[16], const bf_mesh_texture_params* params, bf_mesh_texture_stats* stats) {
+    BF_REQUIRE(m && params && intrinsics, "null argument");
+    BF_REQUIRE(in || m->lastMesh, "no input mesh and no result of a clean or a simplify to take");
+    const bf_clean_mesh last = mcLastMesh(m);
+    return meshtexture_run(m->texture, m->res, m->stream, in ? *in : last, frames, numFrames, width, height, intrinsics, *params, stats);
+}
+
+int bf_marching_cubes_download_texture(bf_marching_cubes* m, uint8_t* h_atlasRGBA, int32_t* h_faceFrame, float* h_faceUV) {
+    BF_REQUIRE(m, "null argument");
+    const MeshTexture& t = m->texture;
+    const size_t texels = (size_t)t.atlasWidth * t.atlasHeight;
+    if (h_atlasRGBA && texels) BF_HIP_TRY(hipMemcpyAsync(h_atlasRGBA, t.d_atlas, 4 * texels, hipMemcpyDeviceToHost, m->stream));
+    if (h_faceFrame && t.numFaces) BF_HIP_TRY(hipMemcpyAsync(h_faceFrame, t.d_faceFrame, 4 * (size_t)t.numFaces, hipMemcpyDeviceToHost, m->stream));
+    if (h_faceUV && t.numFaces) BF_HIP_TRY(hipMemcpyAsync(h_faceUV, t.d_faceUV, 24 * (size_t)t.numFaces, hipMemcpyDeviceToHost, m->stream));
+    BF_HIP_TRY(hipStreamSynchronize(m->stream));
+    return BF_OK;
+}
+
+// weld of the last extraction + clean + the optional recolour (which needs the clean's normals) + the optional simplify + texture + download + the two writers;
+// m_meshData is not touched.  The PNG goes next to the PLY: the same path with the extension of its last component replaced by ".png".
+int bf_marching_cubes_save_mesh_textured(bf_marching_cubes* m, const char* filename, const float transform[16], const bf_mesh_clean_params* cleanParams,
+                                         const bf_mesh_recolour_frame* frames, uint32_t numFrames, uint32_t width, uint32_t height, const float intrinsics[16],
+                                         const bf_mesh_texture_params* textureParams, const bf_mesh_recolour_params* recolourParams, const bf_mesh_simplify_params* simplifyParams,
+                                         bf_mesh_clean_stats* cleanStats, bf_mesh_recolour_stats* recolourStats, bf_mesh_simplify_stats* simplifyStats,
+                                         bf_mesh_texture_stats* textureStats) {
+    BF_REQUIRE(m && filename && cleanParams && textureParams && intrinsics, "null argument");
+    bf_mesh_clean_params cp = *cleanParams;
+    const bool wantNormals = cp.computeNormals || (simplifyParams && simplifyParams->computeNormals);
+    if (recolourParams) cp.computeNormals = 1;
+    bf_clean_mesh mesh;
+    BF_TRY(bf_marching_cubes_weld(m, nullptr, 0, transform, nullptr));
+    BF_TRY(bf_marching_cubes_clean(m, nullptr, &cp, &mesh, cleanStats));
+    if (recolourParams) BF_TRY(bf_marching_cubes_recolour(m, nullptr, frames, numFrames, width, height, intrinsics, recolourParams, &mesh, recolourStats));
+    if (simplifyParams) {
+        bf_mesh_simplify_params sp = *simplifyParams;
+        sp.computeNormals = wantNormals ? 1 : 0;
+        bf_indexed_mesh im; im.d_positions = mesh.d_positions; im.d_colors = mesh.d_colors; im.d_faces = mesh.d_faces; im.numVertices = mesh.numVertices; im.numFaces = mesh.numFaces;
+        BF_TRY(bf_marching_cubes_simplify(m, &im, &sp, &mesh, simplifyStats));
+    }
+    bf_mesh_texture_stats ts;
+    BF_TRY(bf_marching_cubes_texture(m, &mesh, frames, numFrames, width, height, intrinsics, textureParams, &ts));
+    if (textureStats) *textureStats = ts;
+    const uint32_t nv = mesh.numVertices, nf = mesh.numFaces;
+    std::vector<float> pos(3 * (size_t)nv), col(3 * (size_t)nv), nrm(wantNormals ? 3 * (size_t)nv : 0), uv(6 * (size_t)nf);
+    std::vector<uint32_t> faces(3 * (size_t)nf);
+    std::vector<uint8_t> atlas(4 * (size_t)ts.atlasWidth * ts.atlasHeight);
+    if (nv) BF_HIP_TRY(hipMemcpyAsync(pos.data(), mesh.d_positions, 12 * (size_t)nv, hipMemcpyDeviceToHost, m->stream));
+    if (nv) BF_HIP_TRY(hipMemcpyAsync(col.data(), mesh.d_colors, 12 * (size_t)nv, hipMemcpyDeviceToHost, m->stream));
+    if (nv && wantNormals) BF_HIP_TRY(hipMemcpyAsync(nrm.data(), mesh.d_normals, 12 * (size_t)nv, hipMemcpyDeviceToHost, m->stream));
+    if (nf) BF_HIP_TRY(hipMemcpyAsync(faces.data(), mesh.d_faces, 12 * (size_t)nf, hipMemcpyDeviceToHost, m->stream));
+    BF_TRY(bf_marching_cubes_download_texture(m, atlas.data(), nullptr, uv.data()));          // waits for the stream
+    std::string png(filename);
+    const size_t slash = png.find_last_of('/'), base = slash == std::string::npos ? 0 : slash + 1, dot = png.find_last_of('.');
+    if (dot != std::string::npos && dot > base) png.erase(dot);          // the extension of the base name; a base name's leading dot is not one
+    png += ".png";
+    BF_TRY(bf_write_ply_textured(filename, png.c_str() + base, pos.data(), wantNormals ? nrm.data() : nullptr, col.data(), faces.data(), uv.data(), nv, nf));
+    if (atlas.empty()) return BF_OK;
+    return bf_write_png_rgba8(png.c_str(), atlas.data(), ts.atlasWidth, ts.atlasHeight);
 }
 
 }  // extern "C"

@@ -835,6 +835,62 @@ BF_API int bf_marching_cubes_save_mesh_recoloured(bf_marching_cubes* m, const ch
 BF_API int bf_mesh_recolour_host(const float* h_positions, const float* h_normals, const float* h_colors, uint32_t numVertices, const bf_mesh_recolour_frame* frames, uint32_t numFrames,
                                  uint32_t width, uint32_t height, const float intrinsics[16], const bf_mesh_recolour_params* params, float* h_colorsOut, uint32_t* h_viewsOut,
                                  uint8_t* h_codesOut, bf_mesh_recolour_stats* stats);
+/* ---- MI355X additions: a texture atlas for the mesh taken from the key frames in HBM (csrc/meshtexture.hip; DESIGN.md "Mesh texture: the definition"; reference:
+ * none, the definition is the library's own) ----
+ * Arithmetic as the recolouring's.  (1) Face choice, per face (a, b, c): e1 = P_b - P_a, e2 = P_c - P_a, n = e1 x e2 (n.x = e1.y*e2.z - e1.z*e2.y, ...),
+ * len = sqrt((n.x*n.x + n.y*n.y) + n.z*n.z), N = n / len per component; the face is degenerate if an index is >= numVertices, a position is not finite or len
+ * is not finite or not > 0.  A frame that is not skipped views the face iff rules RANGE .. COLOUR of the recolouring give BF_RECOLOUR_VIEW for all three corners
+ * with N in place of the vertex normal; its weight is fminf(fminf(wgt_a, wgt_b), wgt_c).  Over the frames in the order given the first viewing frame is taken
+ * and a later one replaces it iff its weight is strictly greater.  faceFrame[f]: the index into `frames` (skipped ones counted), -1 for a degenerate or unviewed
+ * face.  (2) Layout, integers: S = patchSize in 4 .. 64, m = S - 3, A = atlasWidth in S .. 16384, cellsPerRow = A / S; face f lives in cell q = f >> 1, half
+ * t = f & 1, the cell's origin is (X, Y) = ((q % cellsPerRow) * S, (q / cellsPerRow) * S), H = S * ceil(ceil(numFaces / 2) / cellsPerRow) (H > 32768:
+ * BF_ERR_CAPACITY; no faces: H = 0).  Texel (i, j) of a cell belongs to half 0 iff i + j <= S - 1.  Corner texels: half 0 a = (0, 0), b = (m, 0), c = (0, m);
+ * half 1 a = (S-1, S-1), b = (S-1-m, S-1), c = (S-1, S-1-m).  A corner texel (ci, cj) has u = ((float)(X + ci) + 0.5f) / (float)A,
+ * v = 1.0f - ((float)(Y + cj) + 0.5f) / (float)H; faceUV[f] = u_a v_a u_b v_b u_c v_c.  Atlas row 0 is Y = 0.  (3) Fill, per texel: right of cellsPerRow * S
+ * or with a face index >= numFaces it is unused, RGBA 0 0 0 0.  Otherwise s = (float)i / (float)m, r = (float)j / (float)m (half 1: S-1-i and S-1-j), wb = s,
+ * wc = r, wa = (1.0f - s) - r (gutter texels extrapolate), P = (wa*P_a + wb*P_b) + wc*P_c per component, and with k = faceFrame[f] >= 0: p_j and z as rule RANGE
+ * computes them, z finite and > 0, u, v, x0, y0, a, b and the four texels by rule IMAGE, none of the four colour texels black, val_c the bilinear sample; there
+ * is NO depth test per texel.  With k < 0 or any of these failing: val_c = ((wa*C_a + wb*C_b) + wc*C_c) * 255.0f from the vertex colours; a face with an index
+ * out of range gives 0 0 0.  Byte (uint8_t)(int)(fminf(fmaxf(val_c, 0.0f), 255.0f) + 0.5f), alpha 255.  No result depends on the order in which threads run. */
+typedef struct bf_mesh_texture_params { float depthMin, depthMax, depthTolerance, depthToleranceLin, minCos; uint32_t patchSize, atlasWidth; } bf_mesh_texture_params;
+/* numFacesTextured + numFacesUntextured == numFaces; numFramesUsed + numFramesSkipped == the frames given; the three texel counts sum to atlasWidth * atlasHeight */
+typedef struct bf_mesh_texture_stats { uint32_t numFaces, numFacesTextured, numFacesUntextured, numFramesUsed, numFramesSkipped, atlasWidth, atlasHeight;
+                                       uint64_t numTexelsFromFrames, numTexelsFromVertices, numTexelsUnused; } bf_mesh_texture_stats;
+/* Textures the mesh `in` (device arrays of any origin, normals not needed; NULL: the result of the last clean, or of the last simplify if that is later) from
+ * `frames` (bf_mesh_recolour_frame, filled by bf_mesh_recolour_frame_from_pose) on the object's stream - the face choice with one thread per face, the fill with
+ * one thread per texel - and waits for it once.  The atlas (atlasWidth x atlasHeight RGBA8), the per-face frame index and the per-face texture coordinates stay
+ * on the device with the object, valid until its next extract, weld, clean, simplify, texture or destroy.  Refused with BF_ERR_INVALID_ARG, nothing written and
+ * the last result staying: the recolouring's list without the normals and the mode; patchSize or atlasWidth out of range.  Zero frames, or all of them skipped:
+ * every face falls back, the atlas is the interpolated vertex colours.  stats may be NULL.  reference: none, the definition is the library's own */
+BF_API int bf_marching_cubes_texture(bf_marching_cubes* m, const bf_clean_mesh* in, const bf_mesh_recolour_frame* frames, uint32_t numFrames, uint32_t width, uint32_t height,
+                                     const float intrinsics[16], const bf_mesh_texture_params* params, bf_mesh_texture_stats* stats);
+/* host copies of the last texture: atlasWidth * atlasHeight * 4 bytes, numFaces int32, numFaces * 6 floats (any of them may be NULL).  reference: none, the
+ * definition is the library's own */
+BF_API int bf_marching_cubes_download_texture(bf_marching_cubes* m, uint8_t* h_atlasRGBA, int32_t* h_faceFrame, float* h_faceUV);
+/* weld of the last extraction (with the transform) + clean + (recolourParams non-NULL) recolour + (simplifyParams non-NULL) simplify + texture + download + the
+ * two files: bf_write_ply_textured to `filename` and the atlas as a PNG next to it, under the same name with its extension replaced by ".png" (the PLY's comment
+ * carries that name without its directory; the extension is what follows the last dot of the base name, a dot that begins the base name is not one: "a/.scan"
+ * gives "a/.scan.png", and a name without a dot gets ".png" appended).  The vertices keep their colours beside the texture.  A mesh without faces has no atlas: the PLY alone is written.
+ * The file carries normals if either params struct asks for them.  The frames' poses are camera to MESH: the caller has applied the transform to them.  Any
+ * stats may be NULL.  reference: none, the definition is the library's own */
+BF_API int bf_marching_cubes_save_mesh_textured(bf_marching_cubes* m, const char* filename, const float transform[16], const bf_mesh_clean_params* cleanParams,
+                                                const bf_mesh_recolour_frame* frames, uint32_t numFrames, uint32_t width, uint32_t height, const float intrinsics[16],
+                                                const bf_mesh_texture_params* textureParams, const bf_mesh_recolour_params* recolourParams, const bf_mesh_simplify_params* simplifyParams,
+                                                bf_mesh_clean_stats* cleanStats, bf_mesh_recolour_stats* recolourStats, bf_mesh_simplify_stats* simplifyStats,
+                                                bf_mesh_texture_stats* textureStats);
+/* the atlas height H of the layout for numFaces faces (BF_ERR_CAPACITY where H > 32768), for sizing the outputs of bf_mesh_texture_host.  Host only.  reference:
+ * none, the definition is the library's own */
+BF_API int bf_mesh_texture_atlas_height(uint32_t numFaces, const bf_mesh_texture_params* params, uint32_t* atlasHeight);
+/* The definition on one core (needs no device): host arrays in (the frames' image pointers are host pointers), h_atlasRGBA atlasWidth * H * 4 bytes,
+ * h_faceFrame numFaces, h_faceUV numFaces x 6.  Any output may be NULL.  reference: none, the definition is the library's own */
+BF_API int bf_mesh_texture_host(const float* h_positions, const float* h_colors, const uint32_t* h_faces, uint32_t numVertices, uint32_t numFaces, const bf_mesh_recolour_frame* frames,
+                                uint32_t numFrames, uint32_t width, uint32_t height, const float intrinsics[16], const bf_mesh_texture_params* params, uint8_t* h_atlasRGBA,
+                                int32_t* h_faceFrame, float* h_faceUV, bf_mesh_texture_stats* stats);
+/* the PLY of a textured mesh (host only): the header of bf_write_ply_indexed_normals (h_normals NULL: of bf_write_ply_indexed) with "comment TextureFile
+ * <textureFileName>" behind its comment line and "property list uchar float texcoord" behind vertex_indices; the vertex records are those writers', a face record
+ * is theirs followed by the byte 6 and the six floats u_a v_a u_b v_b u_c v_c (38 bytes).  reference: none, the definition is the library's own */
+BF_API int bf_write_ply_textured(const char* filename, const char* textureFileName, const float* h_positions, const float* h_normals, const float* h_colors, const uint32_t* h_faces,
+                                 const float* h_faceUV, uint32_t numVertices, uint32_t numFaces);
 /* the generated case tables (edge mask per case, up to 5 triangles of edge indices, -1 terminated), for inspection / tests */
 BF_API int bf_marching_cubes_tables(uint16_t edgeTable[256], int8_t triTable[256 * 16]);
 

@@ -425,6 +425,20 @@ BF_API int bf_pipeline_get_mesh_recolour_defaults(bf_pipeline* p, bf_mesh_recolo
 /* the intrinsics (4x4 row-major, at integration resolution) bf_pipeline_save_mesh_recoloured projects with: the colour camera's with the calibration on, the
  * depth camera's otherwise.  reference: none, the definition is the library's own */
 BF_API int bf_pipeline_get_mesh_recolour_intrinsics(bf_pipeline* p, float K[16]);
+/* The same command with bf_marching_cubes_texture at the end (bf_marching_cubes_save_mesh_textured; bf_hip.h has the definition): weld with the transform, clean,
+ * then - recolourFirst != 0 - the recolouring with bf_pipeline_get_mesh_recolour_defaults, then - with simplifyParams - the simplification, then the texture
+ * atlas of the mesh that is written, from the same frames (0, frameStride, 2 * frameStride, ... with a valid optimised pose), poses and intrinsics as
+ * bf_pipeline_save_mesh_recoloured.  Two files: the PLY (bf_write_ply_textured) and the atlas as a PNG next to it, the same name with the extension replaced by
+ * ".png"; the PLY's comment carries the PNG's base name only.  textureParams NULL: bf_pipeline_get_mesh_texture_defaults.  A typed command of the volume
+ * thread's queue like the recoloured save's, between two frames' batches.  cleanParams must not be NULL; simplifyParams, the stats and numTriangles may be.  The
+ * same refusal for a sharded volume; the reconstruction is left alone.  reference: none, the definition is the library's own */
+BF_API int bf_pipeline_save_mesh_textured(bf_pipeline* p, const char* filename, const float* transform, const bf_mesh_clean_params* cleanParams,
+                                          const bf_mesh_texture_params* textureParams, uint32_t frameStride, int recolourFirst, const bf_mesh_simplify_params* simplifyParams,
+                                          bf_mesh_clean_stats* cleanStats, bf_mesh_recolour_stats* recolourStats, bf_mesh_simplify_stats* simplifyStats,
+                                          bf_mesh_texture_stats* textureStats, uint32_t* numTriangles);
+/* the texture's defaults for this pipeline: the five floats of bf_pipeline_get_mesh_recolour_defaults, patchSize = 8, atlasWidth = 8192 (starting points, not
+ * measured optima).  reference: none, the definition is the library's own */
+BF_API int bf_pipeline_get_mesh_texture_defaults(bf_pipeline* p, bf_mesh_texture_params* params);
 BF_API int bf_pipeline_get_scene(bf_pipeline* p, bf_scene** out);
 BF_API int bf_pipeline_get_image_manager(bf_pipeline* p, bf_image_manager** out);
 BF_API int bf_pipeline_get_online_bundler(bf_pipeline* p, bf_online_bundler** out);

@@ -841,6 +841,25 @@ public:
         check(bf_marching_cubes_save_mesh_recoloured(m_h, filename.c_str(), transform ? transform->m : nullptr, &cleanParams, frames, numFrames, width, height, intrinsics.m, &recolourParams,
                                                      simplifyParams, cleanStats, recolourStats, simplifyStats));
     }
+    // A texture atlas for the last clean's (or, if later, the last simplify's) result from `frames` (bf_marching_cubes_texture): the atlas, the per-face frame
+    // index and the per-face texture coordinates stay on the device until the next extract, weld, clean, simplify, texture or destruction; downloadTexture copies
+    // them (sizes from the stats: atlasWidth * atlasHeight * 4 bytes, numFaces, numFaces * 6; any pointer may be null).
+    bf_mesh_texture_stats texture(const bf_mesh_recolour_frame* frames, unsigned int numFrames, unsigned int width, unsigned int height, const mat4f& intrinsics,
+                                  const bf_mesh_texture_params& params) {
+        bf_mesh_texture_stats stats;
+        check(bf_marching_cubes_texture(m_h, nullptr, frames, numFrames, width, height, intrinsics.m, &params, &stats));
+        return stats;
+    }
+    void downloadTexture(unsigned char* atlasRGBA, int* faceFrame, float* faceUV) { check(bf_marching_cubes_download_texture(m_h, atlasRGBA, faceFrame, faceUV)); }
+    // saveMeshClean with a texture atlas (a PNG next to the PLY, the same name with the extension ".png") from `frames` (poses: camera to the TRANSFORMED mesh);
+    // with recolourParams the vertices are recoloured first, with simplifyParams the mesh is simplified before it is textured
+    void saveMeshTextured(const std::string& filename, const bf_mesh_clean_params& cleanParams, const bf_mesh_recolour_frame* frames, unsigned int numFrames, unsigned int width,
+                          unsigned int height, const mat4f& intrinsics, const bf_mesh_texture_params& textureParams, const bf_mesh_recolour_params* recolourParams = nullptr,
+                          const bf_mesh_simplify_params* simplifyParams = nullptr, const mat4f* transform = nullptr, bf_mesh_clean_stats* cleanStats = nullptr,
+                          bf_mesh_recolour_stats* recolourStats = nullptr, bf_mesh_simplify_stats* simplifyStats = nullptr, bf_mesh_texture_stats* textureStats = nullptr) {
+        check(bf_marching_cubes_save_mesh_textured(m_h, filename.c_str(), transform ? transform->m : nullptr, &cleanParams, frames, numFrames, width, height, intrinsics.m, &textureParams,
+                                                   recolourParams, simplifyParams, cleanStats, recolourStats, simplifyStats, textureStats));
+    }
     bf_marching_cubes* handle() const { return m_h; }
 private:
     MarchingCubesParams m_params;

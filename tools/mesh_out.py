@@ -6,7 +6,10 @@ the cleaned mesh's vertices on a grid of that size before it is written (bf_pipe
 route; normals, if asked for, are the simplified mesh's) and prints the simplification's stats and its time.  --mesh-recolour takes the cleaned mesh's vertex
 colours from the stored frames on --mesh-recolour-stride under the optimised trajectory (bf_pipeline_save_mesh_recoloured on the device route,
 bf_mesh_recolour_host on the host route; --mesh-recolour-best: the best view in place of the blend), before the simplification if one is asked for, and prints
-the recolouring's stats, its time and the mean absolute colour difference across the cleaned mesh's edges before and after, for both modes."""
+the recolouring's stats, its time and the mean absolute colour difference across the cleaned mesh's edges before and after, for both modes.  --mesh-texture
+(device route) writes the mesh with a texture atlas from the same frames (bf_pipeline_save_mesh_textured: the PLY and a PNG next to it; after the recolouring and
+the simplification if those are asked for) and prints the texture's stats, the times of its stages, the one-core
+route's time and whether its atlas is the device's, and the held-out colour measurement of profiles/mesh_texture.md."""
 import ctypes as C
 import time
 
@@ -24,6 +27,7 @@ def add_arguments(ap):
     ap.add_argument("--mesh-simplify-cell", type=float, default=0.0, metavar="METRES", help="simplify the (cleaned) mesh before it is written: one vertex per grid cell of this size")
     ap.add_argument("--mesh-recolour", action="store_true", help="take the (cleaned) mesh's vertex colours from the stored frames under the optimised trajectory")
     ap.add_argument("--mesh-recolour-stride", type=int, default=0, metavar="N", help="recolour from every Nth frame (default: s_submapSize, the key frames)")
+    ap.add_argument("--mesh-texture", action="store_true", help="write the mesh with a texture atlas from the stored frames (a PNG next to the PLY); the stride is --mesh-recolour-stride")
     ap.add_argument("--mesh-recolour-best", action="store_true", help="each vertex takes its best view (greatest weight) instead of the weighted blend of all views")
 
 
@@ -66,10 +70,14 @@ def edge_colour_difference(col, faces):
     return float(np.abs(col[e[:, 0]].astype(np.float64) - col[e[:, 1]].astype(np.float64)).mean()) if len(e) else 0.0
 
 
-def _device_frames(p, a):
-    """the frames bf_pipeline_save_mesh_recoloured uses, as a table of device pointers: (table, intrinsics, width, height)"""
+def _device_frames(p, a, offset=0):
+    """the frames bf_pipeline_save_mesh_recoloured uses, as a table of device pointers: (table, intrinsics, width, height); offset: the frames offset, offset +
+    stride, ... in their place"""
     lib, check = bf.capi.lib, bf.capi.check
     host, K, w, h = p.mesh_recolour_frames_host(_stride(p, a), images=False)
+    if offset:
+        every, K, w, h = p.mesh_recolour_frames_host(1, images=False)
+        host = [f for f in every if f[0] % _stride(p, a) == offset]
     im = C.c_void_p()
     check(lib.bf_pipeline_get_image_manager(p._h, C.byref(im)))
     rows = []
@@ -127,6 +135,89 @@ def _device_stages_recolour(p, path, a):
         t8 = time.perf_counter()
         print("mesh (device route, stage by stage): extract %.4f s, weld %.4f s, clean + normals %.4f s, frame table %.4f s, recolour %.4f s (again %.4f s), write %.4f s"
               % (t1 - t0, t2 - t1, t3 - t2, t4 - t3, t5 - t4, t7 - t6, t8 - t7))
+    mc.close()
+
+
+def _texture_line(st):
+    return ("%d of %d faces textured, %d not; %d frames used, %d skipped; atlas %d x %d: %d texels from frames, %d from vertices, %d unused"
+            % (st["numFacesTextured"], st["numFaces"], st["numFacesUntextured"], st["numFramesUsed"], st["numFramesSkipped"], st["atlasWidth"], st["atlasHeight"],
+               st["numTexelsFromFrames"], st["numTexelsFromVertices"], st["numTexelsUnused"]))
+
+
+def _textured(p, a):
+    """the textured save from the frame loop, the simplified save as its reference point in the same process, the stages one by one on an object of their own, the
+    one-core route, and the held-out measurement"""
+    import torch
+    lib, check, capi = bf.capi.lib, bf.capi.check, bf.capi
+    cell = a.mesh_simplify_cell if a.mesh_simplify_cell > 0 else None
+    t0 = time.perf_counter()
+    st, rst, sst, tst, nt = p.save_mesh_textured(a.mesh, None, a.mesh_min_faces, a.mesh_largest, a.mesh_normals, None, _stride(p, a), a.mesh_recolour, cell)
+    dt = time.perf_counter() - t0
+    print("mesh (device route) %s: %d triangles; cleaned: %s;%s%s textured: %s; bf_pipeline_save_mesh_textured %.3f s"
+          % (a.mesh, nt, _stats_line(st), " recoloured: %s;" % _recolour_line(rst) if rst else "", " simplified at %g m: %s;" % (cell, _simplify_line(sst)) if sst else "",
+             _texture_line(tst), dt))
+    if cell:
+        t0 = time.perf_counter()
+        p.save_mesh_simplified(a.mesh + ".untextured.ply", cell, None, a.mesh_min_faces, a.mesh_largest, a.mesh_normals)
+        print("  the reference point, bf_pipeline_save_mesh_simplified of the same mesh in the same process: %.3f s" % (time.perf_counter() - t0))
+    mc = capi.MarchingCubesHashSDF.from_global_app_state(p.gas)
+    t0 = time.perf_counter()
+    mc.extract_gpu(p.scene())
+    t1 = time.perf_counter()
+    check(lib.bf_marching_cubes_weld(mc._h, None, 0, None, None))
+    prm = capi.MeshCleanParams(a.mesh_min_faces, int(a.mesh_largest), 0); mesh = capi.CleanMesh()
+    check(lib.bf_marching_cubes_clean(mc._h, None, C.byref(prm), C.byref(mesh), None))
+    if cell:
+        sp = capi.MeshSimplifyParams(cell, 0)
+        check(lib.bf_marching_cubes_simplify(mc._h, None, C.byref(sp), C.byref(mesh), None))
+        check(lib.bf_marching_cubes_simplify_map(mc._h, None, 0))                # waits for the stream
+    else:
+        check(lib.bf_marching_cubes_clean_labels(mc._h, None, 0))                # waits for the stream
+    t2 = time.perf_counter()
+    frames, K, w, h = _device_frames(p, a)
+    tp = p.mesh_texture_defaults(); ts = capi.MeshTextureStats()
+    times = []
+    for _ in range(2):
+        t3 = time.perf_counter()
+        check(lib.bf_marching_cubes_texture(mc._h, None, frames, len(frames), w, h, capi.mat16(K), C.byref(tp), C.byref(ts)))          # (waits for its stream)
+        times.append(time.perf_counter() - t3)
+    t4 = time.perf_counter()
+    atlas, ff, uv = mc.download_texture(ts.atlasWidth, ts.atlasHeight, ts.numFaces)
+    t5 = time.perf_counter()
+    capi.write_png_rgba8(a.mesh + ".stages.png", atlas)
+    t6 = time.perf_counter()
+    print("mesh (device route, stage by stage): extract %.4f s, weld + clean%s %.4f s; texture (select + fill + one wait) %.4f s (first call, buffers allocated) and %.4f s; "
+          "download of the atlas %.4f s, PNG write %.4f s" % (t1 - t0, " + simplify" if cell else "", t2 - t1, times[0], times[1], t5 - t4, t6 - t5))
+    # the one-core route on the same mesh and frames
+    nv, nf = mesh.numVertices, mesh.numFaces
+    pos = np.empty((nv, 3), np.float32); col = np.empty((nv, 3), np.float32); faces = np.empty((nf, 3), np.uint32)
+    for dst, src in ((pos, mesh.d_positions), (col, mesh.d_colors), (faces, mesh.d_faces)):
+        if dst.nbytes:
+            check(lib.bf_memcpy_d2h(dst.ctypes.data_as(C.c_void_p), C.c_void_p(src), C.c_size_t(dst.nbytes)))
+    hframes = p.mesh_recolour_frames_host(_stride(p, a))[0]
+    t7 = time.perf_counter()
+    hatlas, hff, huv, hst = capi.mesh_texture_host(pos, col, faces, hframes, w, h, K, tp)
+    t8 = time.perf_counter()
+    same = np.array_equal(hatlas, atlas) and np.array_equal(hff, ff) and np.array_equal(huv.view(np.uint32), uv.view(np.uint32)) and hst == ts.as_dict()
+    print("mesh (host route) textured on one core (bf_mesh_texture_host): %.3f s; atlas, face frames, texture coordinates and stats %s the device's" % (t8 - t7, "are" if same else "ARE NOT"))
+    # held out: the atlas from the frames on the stride, from the frames half a stride later, and from no frame; a texel came from a frame where the atlas does
+    # not change with the vertex colours (all 0 against all 1)
+    dpos = torch.from_numpy(pos).cuda(); dfaces = torch.from_numpy(faces.view(np.int32)).cuda(); dcol = torch.from_numpy(col).cuda()
+    black = torch.zeros_like(dcol); white = torch.ones_like(dcol)
+    none = capi.recolour_frames([])
+
+    def run(colours, table):
+        return mc.texture((dpos, colours, dfaces), table, w, h, K, tp)[0]
+
+    later = _device_frames(p, a, _stride(p, a) // 2)[0]
+    first, second, plain = run(dcol, frames), run(dcol, later), run(dcol, none)
+    in_first = (run(black, frames) == run(white, frames)).all(2) & (first[:, :, 3] == 255); in_second = (run(black, later) == run(white, later)).all(2) & (second[:, :, 3] == 255)
+    both = in_first & in_second
+    n = int(both.sum())
+    diff = lambda x, y: float(np.abs(x[both][:, :3].astype(np.int32) - y[both][:, :3].astype(np.int32)).mean()) if n else 0.0
+    print("mesh texture held out: %d frames on the stride, %d half a stride later; %d texels come from frames in both atlases (of %d and %d); mean |byte difference| first vs second %.4f, "
+          "interpolated vertex colours vs second %.4f" % (len(frames), len(later), n, int(in_first.sum()), int(in_second.sum()), diff(first, second),
+                                                      diff(plain, second)))
     mc.close()
 
 
@@ -232,6 +323,9 @@ def _host(p, path, a):
 
 def write(p, a):
     """p: the Pipeline after process_end_of_sequence / synchronize; a: the parsed arguments"""
+    if a.mesh and a.mesh_texture:
+        _textured(p, a)
+        return
     if a.mesh:
         t0 = time.perf_counter()
         if a.mesh_recolour:

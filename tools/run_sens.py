@@ -13,6 +13,8 @@ bf_mesh_simplify_host with --mesh-host); both print the simplification's stats a
 --mesh-recolour [--mesh-recolour-stride N] [--mesh-recolour-best]: take the cleaned mesh's vertex colours from the stored frames on the stride (default
 s_submapSize: the key frames) under the optimised trajectory, before the simplification if there is one (bf_pipeline_save_mesh_recoloured with --mesh,
 bf_mesh_recolour_host with --mesh-host); both print the recolouring's stats and its time.
+--mesh-texture (with --mesh): write the mesh with a texture atlas from the same frames, a PNG next to the PLY (bf_pipeline_save_mesh_textured; after the
+recolouring and the simplification if those are asked for); prints the texture's stats and times and compares with bf_mesh_texture_host on one core.
 --point-cloud FILE [--point-cloud-stride N --point-cloud-cell M]: the stored frames on the stride (default s_submapSize: the key frames) under the optimised
 trajectory as a coloured, oriented point cloud, one point per cell of M metres (default 0.005), thinned on the device (bf_pipeline_save_point_cloud);
 --point-cloud-host FILE: the same file by the host route on one core.  Both print frame and point counts and the seconds spent.

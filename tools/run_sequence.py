@@ -4,6 +4,7 @@ usage: python tools/run_sequence.py [--frames N] [--voxel 0.01] [--host] [--timi
                                      [--mesh-min-faces N] [--mesh-largest] [--mesh-normals]    (clean the mesh before it is written: tools/mesh_out.py)
                                      [--mesh-simplify-cell METRES]    (simplify the cleaned mesh before it is written, one vertex per grid cell: tools/mesh_out.py)
                                      [--mesh-recolour [--mesh-recolour-stride N] [--mesh-recolour-best]]    (vertex colours from the stored key frames: tools/mesh_out.py)
+                                     [--mesh-texture]    (a texture atlas from the stored key frames, a PNG next to the PLY: tools/mesh_out.py)
                                     [--point-cloud cloud.ply [--point-cloud-stride N --point-cloud-cell M]] [--point-cloud-host cloud_host.ply]
 """
 import argparse
