@@ -744,6 +744,10 @@ class SiftManager:
     def add_curr_to_residuals(self, cur, start, num, Kinv):
         check(lib.bf_siftmgr_add_curr_to_residuals(self._h, cur, start, num, _f16(Kinv)))
 
+    def commit_frame(self, cur, start, num, Kinv):
+        """filter_frames_async and add_curr_to_residuals in one launch"""
+        check(lib.bf_siftmgr_commit_frame(self._h, cur, start, num, _f16(Kinv)))
+
     def sync_frame_result(self, cur):
         last = C.c_uint32(); nk = C.c_int32()
         check(lib.bf_siftmgr_sync_frame_result(self._h, cur, C.byref(last), C.byref(nk)))
@@ -853,6 +857,16 @@ class SiftManager:
     def fuse_error(self):
         e = C.c_int()
         check(lib.bf_siftmgr_fuse_error(self._h, C.byref(e)))
+        return e.value
+
+    def set_fuse_lds_limit(self, keys):
+        """the device fuse searches from LDS while at most `keys` keys have a valid correspondence (and they fit), from global memory beyond; 0: never from LDS"""
+        check(lib.bf_siftmgr_set_fuse_lds_limit(self._h, int(keys)))
+
+    def fuse_path(self):
+        """the form the last device fuse ran in: 1 LDS, 0 global memory"""
+        e = C.c_int()
+        check(lib.bf_siftmgr_fuse_path(self._h, C.byref(e)))
         return e.value
 
 

@@ -648,6 +648,12 @@ int evaluateStage(bf_bundler* b, bool filtered, bool recompute, bool clear, cons
     return bf_correspondence_evaluator_evaluate(b->corrEvaluator, b->mgr, b->cache, b->siftIntrinsicsInv.e, &p, filtered, recompute, clear, type, b->stream, nullptr);
 }
 
+// BF_FILTER_FUSED=0 (the A/B): filterFrames and the residual rows as two launches
+bool filterFused() {
+    static const bool on = [] { const char* e = getenv("BF_FILTER_FUSED"); return !e || atoi(e) != 0; }();
+    return on;
+}
+
 // ... in two stages.  The PAIR stage - match, Kabsch filter, surface-area filter, dense verification - computes, per previous image, from the two images
 // alone; it runs on the stream and result set bf_siftmgr_set_pair_stage selected.  The COMMIT stage - which previous images count, filterFrames, the
 // frame's EntryJ rows - needs the valid flags of all earlier frames and runs on the bundler's stream.
@@ -680,6 +686,7 @@ int matchAndFilterPairs(bf_bundler* b, uint32_t& curFrame, uint32_t& startFrame,
 int matchAndFilterCommit(bf_bundler* b, uint32_t curFrame, uint32_t startFrame, uint32_t numFrames, bool speculative) {
     if (curFrame > 0) {
         if (speculative) BF_TRY(bf_siftmgr_commit_pairs(b->mgr, curFrame, startFrame, numFrames));
+        if (filterFused()) return bf_siftmgr_commit_frame(b->mgr, curFrame, startFrame, numFrames, b->siftIntrinsicsInv.e);
         BF_TRY(bf_siftmgr_filter_frames_async(b->mgr, curFrame, startFrame, numFrames));
         BF_TRY(bf_siftmgr_add_curr_to_residuals(b->mgr, curFrame, startFrame, numFrames, b->siftIntrinsicsInv.e));
     }

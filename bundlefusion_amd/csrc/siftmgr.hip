@@ -18,6 +18,7 @@
 //    results are bit-reproducible: matches appended in ascending current-key order, residuals in ascending
 //    previous-image order, dense-verify sums over 256 strided partials + xor butterflies + 4 wave totals in order.
 #include <algorithm>
+#include <cstdlib>
 #include <cstring>
 #include <deque>
 #include <vector>
@@ -922,6 +923,101 @@ __global__ __launch_bounds__(1024) void k_add_residuals(uint32_t curFrame, uint3
     if (tid == 1023) { const int total = min(base0 + part[1023], (int)maxResiduals); *globNum = total; res->numResiduals = total; }
 }
 
+// k_filter_frames and k_add_residuals in ONE launch (the frame loop's commit stage).  The last matched frame is the maximum over the previous images that
+// count (what the downward scan of k_filter_frames finds first).  Up to 64 pairs - a chunk has 10 - the first wave forms that maximum and the rows' offsets
+// with shuffles, behind one barrier, and the rows are written one thread per (pair, k); more pairs (the global manager of a long stream) take the block scan
+// and the per-thread pair ranges of k_add_residuals.  Same rows at the same places, same cap, same counts.
+BF_DEV void writeResidualRow(uint32_t prev, uint32_t curFrame, uint2 ki, const Key* keys, const m44& Kinv, bf_entry_j* glob, uint2* globKeys, int pos) {
+    const f3 a = backProject(Kinv, keys[ki.x]), b = backProject(Kinv, keys[ki.y]);
+    bf_entry_j e;
+    e.imgIdx_i = prev; e.imgIdx_j = curFrame;
+    e.pos_i[0] = a.x; e.pos_i[1] = a.y; e.pos_i[2] = a.z;
+    e.pos_j[0] = b.x; e.pos_j[1] = b.y; e.pos_j[2] = b.z;
+    glob[pos] = e; globKeys[pos] = ki;
+}
+
+__global__ __launch_bounds__(1024) void k_commit_frame(uint32_t curFrame, uint32_t startFrame, uint32_t numFrames, const int* numFilt, const uint2* fidx,
+                                                       const Key* keys, m44 Kinv, int* validImages, const int* numKeys, bf_entry_j* glob, uint2* globKeys,
+                                                       int* globNum, uint32_t maxResiduals, FrameResult* res) {
+    __shared__ int part[1024];
+    __shared__ int offs[64], cnts[64];
+    __shared__ int shLast, shSum;
+    const uint32_t tid = threadIdx.x;
+    const int base0 = *globNum;
+    const uint32_t nPairs = numFrames - startFrame;
+    if (tid == 0) shLast = -1;
+    if (nPairs <= 64u) {
+        if (tid < 64u) {
+            const uint32_t prev = startFrame + tid;
+            const bool in = tid < nPairs && prev != curFrame;
+            const int nf = in ? numFilt[prev] : 0;
+            const int cnt = max(nf, 0);
+            int last = (in && nf > 0 && validImages[prev] != 0) ? (int)prev : -1;
+            int inc = cnt;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                last = max(last, __shfl_xor(last, o, 64));
+                const int up = __shfl_up(inc, o, 64);
+                if ((int)tid >= o) inc += up;
+            }
+            offs[tid] = inc - cnt; cnts[tid] = cnt;
+            if (tid == 63u) { shLast = last; shSum = inc; }
+        }
+        __syncthreads();
+    } else {
+        const uint32_t chunk = (nPairs + 1023) / 1024;
+        const uint32_t p0 = min(tid * chunk, nPairs), p1 = min(p0 + chunk, nPairs);
+        int cnt = 0, last = -1;
+        for (uint32_t p = p0; p < p1; ++p) {
+            const uint32_t prev = p + startFrame;
+            if (prev == curFrame) continue;
+            const int nf = numFilt[prev];
+            cnt += max(nf, 0);
+            if (nf > 0 && validImages[prev] != 0) last = (int)prev;
+        }
+        part[tid] = cnt;
+        __syncthreads();
+        if (last >= 0) atomicMax(&shLast, last);
+        for (uint32_t off = 1; off < 1024; off <<= 1) {
+            int t = 0;
+            if (tid >= off) t = part[tid - off];
+            __syncthreads();
+            part[tid] += t;
+            __syncthreads();
+        }
+        if (tid == 1023u) shSum = part[1023];
+        __syncthreads();
+    }
+    const int last = shLast, connected = last >= 0 ? 1 : 0;
+    if (tid == 0) {
+        validImages[curFrame] = connected;
+        res->lastMatched = last; res->valid = connected; res->numKeysCur = numKeys[curFrame];
+        if (connected) { const int total = min(base0 + shSum, (int)maxResiduals); *globNum = total; res->numResiduals = total; }
+        else res->numResiduals = base0;
+    }
+    if (!connected) return;
+    if (nPairs <= 64u) {
+        for (uint32_t w = tid; w < nPairs * (uint32_t)MAX_FILT; w += 1024u) {
+            const uint32_t p = w / (uint32_t)MAX_FILT, k0 = w % (uint32_t)MAX_FILT, prev = p + startFrame;
+            for (int k = (int)k0; k < cnts[p]; k += MAX_FILT) {                          // (a count never exceeds MAX_FILT: one row per thread)
+                const int pos = base0 + offs[p] + k;
+                if ((uint32_t)pos < maxResiduals) writeResidualRow(prev, curFrame, fidx[prev * MAX_FILT + k], keys, Kinv, glob, globKeys, pos);
+            }
+        }
+    } else {
+        const uint32_t chunk = (nPairs + 1023) / 1024;
+        const uint32_t p0 = min(tid * chunk, nPairs), p1 = min(p0 + chunk, nPairs);
+        int pos = base0 + (tid > 0 ? part[tid - 1] : 0);
+        for (uint32_t p = p0; p < p1; ++p) {
+            const uint32_t prev = p + startFrame;
+            if (prev == curFrame) continue;
+            const int n = max(numFilt[prev], 0);
+            for (int k = 0; k < n; ++k, ++pos)
+                if ((uint32_t)pos < maxResiduals) writeResidualRow(prev, curFrame, fidx[prev * MAX_FILT + k], keys, Kinv, glob, globKeys, pos);
+        }
+    }
+}
+
 __global__ void k_invalidate_pair(bf_entry_j* glob, uint32_t n, uint32_t i, uint32_t j) {      // :692-704
     const uint32_t idx = blockDim.x * blockIdx.x + threadIdx.x;
     if (idx < n && glob[idx].imgIdx_i == i && glob[idx].imgIdx_j == j) { glob[idx].imgIdx_i = 0xFFFFFFFFu; glob[idx].imgIdx_j = 0xFFFFFFFFu; }
@@ -1003,7 +1099,8 @@ BF_DEV uint32_t fuseBlockScan(uint32_t v, uint32_t* lds, uint32_t& total) {     
     return ex;
 }
 
-__global__ __launch_bounds__(FUSE_THREADS) void k_fuse_to_global(FuseArgs a) {
+// the search with its state in global memory: any number of keys and correspondences (k_fuse_to_global; what k_fuse_to_global_lds falls back to)
+BF_DEV void fuseToGlobalBody(const FuseArgs& a) {
     __shared__ uint32_t lds[FUSE_THREADS];
     __shared__ uint32_t changed;
     const uint32_t t = threadIdx.x, N = a.nI * a.mk;
@@ -1130,6 +1227,177 @@ __global__ __launch_bounds__(FUSE_THREADS) void k_fuse_to_global(FuseArgs a) {
     if (t == 0) *a.dstNum = (int)numOut;
 }
 
+__global__ __launch_bounds__(FUSE_THREADS) void k_fuse_to_global(FuseArgs a) { fuseToGlobalBody(a); }
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The same search with its state in LDS.  k_fuse_to_global's search walks 4-5 dependent global round trips per step (list position, count, list
+// entry, marker, parent) and a feature seen in all 11 images makes a track of ~120 steps: 0.3 ms of latency for a graph of a few KB.  Here the keys
+// that have a correspondence get dense ids in ascending key order (so the smallest id of a component is its smallest key, and ascending ids are
+// ascending start keys); per id: list end, list position, label, parent (FUSE_NONE: not visited - the marker), key index, representative, track
+// flag; per directed edge: source and destination id, correspondence order with the inlier bit, and the edge's term of the track's position sum,
+// T[img] * p, formed when the edge is written (the same operations on the same operands as in the search of k_fuse_to_global - the library is built
+// without contraction - so the sum adds the same floats in the same pre-order).  12 words per id and edge: `cap` of either in cap * 48 bytes.
+// The map key index -> id lives in global scratch (a.cnt), written and read by parallel sweeps only; so do the fused key points (a.tmpKeys).
+// More ids than `limit` (bf_siftmgr_set_fuse_lds_limit; the host holds limit <= cap and 2 R <= cap): the workgroup runs fuseToGlobalBody instead.
+// ---------------------------------------------------------------------------------------------------------------------------
+constexpr uint32_t FUSE_LDS_CAP = 3072;        // 144 KB + the scan's 4 KB of the workgroup's 160 KB; a chunk's manager (11 images) has at most 25 x 55 = 1375 correspondences: 2750 ids / edges
+constexpr uint32_t FUSE_LDS_WORDS = 12;
+constexpr uint32_t FUSE_NONE = 0xFFFFFFFFu;
+
+__global__ __launch_bounds__(FUSE_THREADS) void k_fuse_to_global_lds(FuseArgs a, uint32_t cap, uint32_t limit, int* path) {
+    extern __shared__ uint32_t fuseLds[];
+    __shared__ uint32_t scan[FUSE_THREADS];
+    __shared__ uint32_t changed;
+    const uint32_t t = threadIdx.x, N = a.nI * a.mk;
+    uint32_t* kEnd = fuseLds; uint32_t* kFill = kEnd + cap; uint32_t* kLabel = kFill + cap; uint32_t* kParent = kLabel + cap; uint32_t* kKey = kParent + cap;
+    uint32_t* kRep = kKey + cap; uint32_t* kFlag = kRep + cap;
+    uint32_t* eSD = kFlag + cap; uint32_t* eOrd = eSD + cap;
+    float* eWx = reinterpret_cast<float*>(eOrd + cap); float* eWy = eWx + cap; float* eWz = eWy + cap;
+    uint32_t* idOf = a.cnt;                                                            // key index -> id + 1; 0: the key has no valid correspondence
+    // 0. the active keys, ids in ascending key order
+    for (uint32_t k = t; k < N; k += FUSE_THREADS) idOf[k] = 0u;
+    __syncthreads();
+    for (uint32_t i = t; i < a.R; i += FUSE_THREADS) {
+        if (a.glob[i].imgIdx_i == 0xFFFFFFFFu) continue;
+        const uint2 k = a.globKeys[i];
+        idOf[k.x] = 1u; idOf[k.y] = 1u;
+    }
+    __syncthreads();
+    const uint32_t per = (N + FUSE_THREADS - 1) / FUSE_THREADS;
+    uint32_t mine = 0;
+    for (uint32_t k = t * per; k < min(N, (t + 1) * per); ++k) mine += idOf[k];
+    uint32_t A;
+    uint32_t base = fuseBlockScan(mine, scan, A);
+    if (A > limit) {                                                                   // (uniform) does not fit: the global form, which initialises all it uses
+        if (t == 0) *path = 0;
+        fuseToGlobalBody(a);
+        return;
+    }
+    for (uint32_t k = t * per; k < min(N, (t + 1) * per); ++k) if (idOf[k]) { kKey[base] = k; idOf[k] = ++base; }
+    for (uint32_t id = t; id < A; id += FUSE_THREADS) { kEnd[id] = 0u; kLabel[id] = id; kParent[id] = FUSE_NONE; kFlag[id] = 0u; }
+    __syncthreads();
+    // 1. adjacency: count, scan, fill, per-key order
+    for (uint32_t i = t; i < a.R; i += FUSE_THREADS) {
+        if (a.glob[i].imgIdx_i == 0xFFFFFFFFu) continue;
+        const uint2 k = a.globKeys[i];
+        atomicAdd(&kEnd[idOf[k.x] - 1u], 1u); atomicAdd(&kEnd[idOf[k.y] - 1u], 1u);
+    }
+    __syncthreads();
+    const uint32_t perA = (A + FUSE_THREADS - 1) / FUSE_THREADS;
+    mine = 0;
+    for (uint32_t id = t * perA; id < min(A, (t + 1) * perA); ++id) mine += kEnd[id];
+    uint32_t totalE;
+    base = fuseBlockScan(mine, scan, totalE);
+    for (uint32_t id = t * perA; id < min(A, (t + 1) * perA); ++id) { const uint32_t c = kEnd[id]; kFill[id] = base; kRep[id] = base; base += c; kEnd[id] = base; }    // kRep: the list's start, until the search
+    __syncthreads();
+    for (uint32_t i = t; i < a.R; i += FUSE_THREADS) {
+        const bf_entry_j c = a.glob[i];
+        if (c.imgIdx_i == 0xFFFFFFFFu) continue;
+        const uint2 k = a.globKeys[i];
+        const f3 pi = mk3(c.pos_i[0], c.pos_i[1], c.pos_i[2]), pj = mk3(c.pos_j[0], c.pos_j[1], c.pos_j[2]);
+        const f3 wi = xform(a.T[c.imgIdx_i], pi), wj = xform(a.T[c.imgIdx_j], pj);
+        const f3 d = wi - wj;
+        const uint32_t ok = sqrtf(dot3(d, d)) < 0.03f ? 1u : 0u;                       // MAX_TRACK_CORR_ERROR
+        const uint32_t ix = idOf[k.x] - 1u, iy = idOf[k.y] - 1u;
+        uint32_t s = atomicAdd(&kFill[ix], 1u);
+        eSD[s] = (ix << 16) | iy; eOrd[s] = (i << 1) | ok; eWx[s] = wj.x; eWy[s] = wj.y; eWz[s] = wj.z;
+        s = atomicAdd(&kFill[iy], 1u);
+        eSD[s] = (iy << 16) | ix; eOrd[s] = (i << 1) | ok; eWx[s] = wi.x; eWy[s] = wi.y; eWz[s] = wi.z;
+    }
+    __syncthreads();
+    for (uint32_t id = t; id < A; id += FUSE_THREADS) {                                // each key's list in correspondence order
+        const uint32_t s0 = kRep[id], n = kEnd[id] - s0;
+        for (uint32_t i = 1; i < n; ++i) {
+            const uint32_t sd = eSD[s0 + i], o = eOrd[s0 + i]; const float wx = eWx[s0 + i], wy = eWy[s0 + i], wz = eWz[s0 + i];
+            uint32_t j = i;
+            while (j > 0 && eOrd[s0 + j - 1] > o) {
+                eSD[s0 + j] = eSD[s0 + j - 1]; eOrd[s0 + j] = eOrd[s0 + j - 1]; eWx[s0 + j] = eWx[s0 + j - 1]; eWy[s0 + j] = eWy[s0 + j - 1]; eWz[s0 + j] = eWz[s0 + j - 1];
+                --j;
+            }
+            eSD[s0 + j] = sd; eOrd[s0 + j] = o; eWx[s0 + j] = wx; eWy[s0 + j] = wy; eWz[s0 + j] = wz;
+        }
+        kFill[id] = s0;                                                                // from here on: the search's position in this key's list
+    }
+    __syncthreads();
+    // 2. connected components: label = smallest id.  A sweep over the edges (atomicMin), then every label jumps to its label's label: a label is always an
+    //    id of the same component and the smallest id keeps itself, so a sweep that changes nothing has found every component at its smallest id
+    for (int it = 0; it < 4096; ++it) {
+        if (t == 0) changed = 0u;
+        __syncthreads();
+        for (uint32_t e = t; e < totalE; e += FUSE_THREADS) {
+            const uint32_t u = eSD[e] >> 16, v = eSD[e] & 0xFFFFu;
+            const uint32_t lu = kLabel[u], lv = kLabel[v];
+            if (lu < lv) { atomicMin(&kLabel[v], lu); changed = 1u; }
+            else if (lv < lu) { atomicMin(&kLabel[u], lv); changed = 1u; }
+        }
+        __syncthreads();
+        const uint32_t ch = changed;
+        if (ch)
+            for (uint32_t id = t; id < A; id += FUSE_THREADS) { const uint32_t l = kLabel[id], ll = kLabel[l]; if (ll < l) atomicMin(&kLabel[id], ll); }
+        __syncthreads();
+        if (!ch) break;
+        if (it == 4095 && t == 0) *a.error = 2;
+    }
+    // 3. the reference's depth-first search, one thread per component, with the semantics described in fuseToGlobalBody: no stack, the start key may be
+    //    entered a second time, the search ends when the count of open calls returns to zero
+    for (uint32_t id = t; id < A; id += FUSE_THREADS) {
+        if (kLabel[id] != id) continue;
+        f3 pos = mk3(0, 0, 0);
+        uint32_t num = 0, rep = FUSE_NONE, u = id;
+        int depth = 1;
+        while (depth > 0 && u < A) {                                                   // (u < A always holds while a call is open)
+            const uint32_t p = kFill[u];
+            if (p >= kEnd[u]) { --depth; u = kParent[u]; continue; }
+            kFill[u] = p + 1;
+            const uint32_t dst = eSD[p] & 0xFFFFu;
+            if (kParent[dst] != FUSE_NONE) continue;
+            if (rep == FUSE_NONE) rep = dst;
+            if (eOrd[p] & 1u) { pos = pos + mk3(eWx[p], eWy[p], eWz[p]); num++; }
+            kParent[dst] = u;
+            u = dst; ++depth;
+        }
+        if (num > 0) {
+            pos = pos / (float)num;
+            pos = xform(a.K, pos);
+            const uint32_t repKey = kKey[rep];
+            Key key;
+            key.x = pos.x / pos.z; key.y = pos.y / pos.z; key.scale = a.keys[repKey].scale; key.depth = pos.z;
+            a.tmpKeys[id] = key; kRep[id] = repKey; kFlag[id] = 1u;
+        }
+    }
+    __syncthreads();
+    // 4. tracks in ascending start-key order -> the new key frame (kLabel: the track's position from here on)
+    mine = 0;
+    for (uint32_t id = t * perA; id < min(A, (t + 1) * perA); ++id) mine += kFlag[id];
+    uint32_t M;
+    base = fuseBlockScan(mine, scan, M);
+    for (uint32_t id = t * perA; id < min(A, (t + 1) * perA); ++id) { kLabel[id] = base; base += kFlag[id]; }
+    __syncthreads();
+    const uint32_t numOut = min(M, a.dstMaxKeys);
+    if (M <= a.dstMaxKeys) {
+        for (uint32_t id = t; id < A; id += FUSE_THREADS) if (kFlag[id]) a.dstKeys[kLabel[id]] = a.tmpKeys[id];
+    } else {
+        // more tracks than the key frame holds: the keys by (depth, track position), the first maxKeys kept - as in fuseToGlobalBody
+        float* dep = eWx;                                                              // (the edges are done with)
+        for (uint32_t id = t; id < A; id += FUSE_THREADS) dep[id] = kFlag[id] ? a.tmpKeys[id].depth : 0.0f;
+        __syncthreads();
+        for (uint32_t id = t; id < A; id += FUSE_THREADS) {
+            if (!kFlag[id]) continue;
+            const float dk = dep[id]; const uint32_t pk = kLabel[id];
+            uint32_t rank = 0;
+            for (uint32_t j = 0; j < A; ++j) if (kFlag[j]) { const float dj = dep[j]; rank += (dj < dk || (dj == dk && kLabel[j] < pk)) ? 1u : 0u; }
+            if (rank < a.dstMaxKeys) a.dstKeys[rank] = a.tmpKeys[id];
+        }
+    }
+    // descriptors of the representatives: 128 B = 8 x 16 B each, one thread per 16 B
+    for (uint32_t w = t; w < A * 8u; w += FUSE_THREADS) {
+        const uint32_t id = w >> 3, q = w & 7u;
+        if (!kFlag[id] || kLabel[id] >= numOut) continue;
+        reinterpret_cast<uint4*>(a.dstDescs + (size_t)kLabel[id] * 128)[q] = reinterpret_cast<const uint4*>(a.descs + (size_t)kRep[id] * 128)[q];
+    }
+    if (t == 0) { *a.dstNum = (int)numOut; *path = 1; }
+}
+
 struct bf_siftmgr {
     uint32_t maxImages = 0, maxKeys = 0, maxResiduals = 0;
     hipStream_t stream = nullptr;
@@ -1160,7 +1428,8 @@ struct bf_siftmgr {
     bool validDirty = false;          // host copy of the valid flags changed since the last upload
     std::deque<uint32_t> retry;
     // scratch of the device-side fuseToGlobal (allocated at first use)
-    void* fuseScratch = nullptr; size_t fuseScratchBytes = 0; int* d_fuseError = nullptr;
+    void* fuseScratch = nullptr; size_t fuseScratchBytes = 0; int* d_fuseError = nullptr;      // d_fuseError: {condition, form of the last fuse (1: LDS)}
+    uint32_t fuseLdsLimit = FUSE_LDS_CAP;      // active keys up to which k_fuse_to_global_lds serves; 0: k_fuse_to_global always (bf_siftmgr_set_fuse_lds_limit, BF_FUSE_LDS=0)
     bf::Resources res;
 };
 
@@ -1223,6 +1492,8 @@ int bf_siftmgr_create(uint32_t maxImages, uint32_t maxKeyPointsPerImage, bf_sift
     m->validImages.assign(maxImages, 0);
     m->validImages[0] = 1;
     BF_HIP_TRY(hipMemcpy(m->d_validImages, m->validImages.data(), sizeof(int) * maxImages, hipMemcpyHostToDevice));
+    BF_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fuse_to_global_lds), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(FUSE_LDS_CAP * FUSE_LDS_WORDS * 4)));
+    if (const char* e = getenv("BF_FUSE_LDS")) if (atoi(e) == 0) m->fuseLdsLimit = 0;      // (the A/B: the search in global memory for every chunk)
     *out = guard.dismiss();
     return BF_OK;
 }
@@ -1344,6 +1615,15 @@ int bf_siftmgr_add_curr_to_residuals(bf_siftmgr* m, uint32_t curFrame, uint32_t 
     BF_REQUIRE(m && colorIntrinsicsInv && numFrames <= m->numImages && startFrame < numFrames, "frame range out of bounds");
     k_add_residuals<<<1, 1024, 0, m->stream>>>(curFrame, startFrame, numFrames, m->d_numFilt, m->d_fidx, m->d_keys, toM44(colorIntrinsicsInv),
                                                m->d_validImages, m->d_glob, m->d_globKeys, m->d_globNum, m->maxResiduals, m->d_res);
+    BF_HIP_TRY(hipGetLastError());
+    return BF_OK;
+}
+
+// bf_siftmgr_filter_frames_async and bf_siftmgr_add_curr_to_residuals in one launch (k_commit_frame)
+int bf_siftmgr_commit_frame(bf_siftmgr* m, uint32_t curFrame, uint32_t startFrame, uint32_t numFrames, const float colorIntrinsicsInv[16]) {
+    BF_REQUIRE(m && colorIntrinsicsInv && numFrames <= m->numImages && startFrame < numFrames && curFrame < m->maxImages, "frame range out of bounds");
+    k_commit_frame<<<1, 1024, 0, m->stream>>>(curFrame, startFrame, numFrames, m->d_numFilt, m->d_fidx, m->d_keys, toM44(colorIntrinsicsInv), m->d_validImages,
+                                              m->d_numKeys, m->d_glob, m->d_globKeys, m->d_globNum, m->maxResiduals, m->d_res);
     BF_HIP_TRY(hipGetLastError());
     return BF_OK;
 }
@@ -1583,7 +1863,7 @@ int bf_siftmgr_fuse_to_global(bf_siftmgr* local, bf_siftmgr* global, const float
         BF_TRY(local->res.regrow(&local->fuseScratch, cap));
         local->fuseScratchBytes = cap;
     }
-    if (!local->d_fuseError) { BF_TRY(local->res.device(&local->d_fuseError, 1)); BF_HIP_TRY(hipMemset(local->d_fuseError, 0, sizeof(int))); }
+    if (!local->d_fuseError) { BF_TRY(local->res.device(&local->d_fuseError, 2)); BF_HIP_TRY(hipMemset(local->d_fuseError, 0, 2 * sizeof(int))); }
     bf_sift_image_gpu img;
     { const int rc = bf_siftmgr_create_image(global, &img); if (rc != BF_OK) return rc; }
     FuseArgs a;
@@ -1599,7 +1879,15 @@ int bf_siftmgr_fuse_to_global(bf_siftmgr* local, bf_siftmgr* global, const float
     a.error = local->d_fuseError;
     // the chunk's manager and the global manager share the bundling stream in the frame loop; if they do not, order them
     if (global->stream != local->stream) BF_HIP_TRY(hipStreamSynchronize(global->stream));
-    k_fuse_to_global<<<1, FUSE_THREADS, 0, local->stream>>>(a);
+    // the LDS form where the graph fits: at most 2 R directed edges and as many keys with an edge (the kernel itself compares the keys with the limit)
+    const uint32_t limit = std::min(local->fuseLdsLimit, FUSE_LDS_CAP);
+    if (limit > 0 && 2u * R <= FUSE_LDS_CAP) {
+        const uint32_t cap = std::max(2u * R, 64u);
+        k_fuse_to_global_lds<<<1, FUSE_THREADS, (size_t)cap * FUSE_LDS_WORDS * 4, local->stream>>>(a, cap, std::min(limit, cap), local->d_fuseError + 1);
+    } else {
+        BF_HIP_TRY(hipMemsetAsync(local->d_fuseError + 1, 0, sizeof(int), local->stream));
+        k_fuse_to_global<<<1, FUSE_THREADS, 0, local->stream>>>(a);
+    }
     BF_HIP_TRY(hipGetLastError());
     if (global->stream != local->stream) BF_HIP_TRY(hipStreamSynchronize(local->stream));
     return bf_siftmgr_finalize_image(global, -1);          // the count was written on the device
@@ -1611,6 +1899,17 @@ int bf_siftmgr_fuse_error(bf_siftmgr* local, int* err) {
     BF_REQUIRE(local && err, "null argument");
     *err = 0;
     if (local->d_fuseError) { BF_HIP_TRY(hipMemcpyAsync(err, local->d_fuseError, sizeof(int), hipMemcpyDeviceToHost, local->stream)); BF_HIP_TRY(hipStreamSynchronize(local->stream)); }
+    return BF_OK;
+}
+
+// Which search bf_siftmgr_fuse_to_global uses: k_fuse_to_global_lds while the keys with a valid correspondence number at most `keys` (and at most what the
+// workgroup's LDS holds: the default), k_fuse_to_global beyond; 0: k_fuse_to_global always.  Same results either way.
+int bf_siftmgr_set_fuse_lds_limit(bf_siftmgr* local, uint32_t keys) { BF_REQUIRE(local, "null manager"); local->fuseLdsLimit = keys; return BF_OK; }
+// the form the LAST fuse ran in: 1 the LDS search, 0 the search in global memory
+int bf_siftmgr_fuse_path(bf_siftmgr* local, int* path) {
+    BF_REQUIRE(local && path, "null argument");
+    *path = 0;
+    if (local->d_fuseError) { BF_HIP_TRY(hipMemcpyAsync(path, local->d_fuseError + 1, sizeof(int), hipMemcpyDeviceToHost, local->stream)); BF_HIP_TRY(hipStreamSynchronize(local->stream)); }
     return BF_OK;
 }
 

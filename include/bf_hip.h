@@ -495,6 +495,9 @@ BF_API int bf_siftmgr_filter_frames_async(bf_siftmgr* m, uint32_t curFrame, uint
  * when curFrame was not connected (Bundler.cpp:218-219); pairs are appended in ascending previous-image order. */
 BF_API int bf_siftmgr_add_curr_to_residuals(bf_siftmgr* m, uint32_t curFrame, uint32_t startFrame, uint32_t numFrames,
                                             const float colorIntrinsicsInv[16]);
+/* MI355X addition: _filter_frames_async and _add_curr_to_residuals in ONE launch - same flags, frame result, rows and counts */
+BF_API int bf_siftmgr_commit_frame(bf_siftmgr* m, uint32_t curFrame, uint32_t startFrame, uint32_t numFrames,
+                                   const float colorIntrinsicsInv[16]);
 BF_API int bf_siftmgr_sync_frame_result(bf_siftmgr* m, uint32_t curFrame, uint32_t* lastMatchedFrame,
                                         int32_t* numKeyPointsCur);
 /* optional: enqueue that read-back now (after filter_frames_async / add_curr_to_residuals); sync_frame_result then only waits - for an
@@ -564,6 +567,11 @@ BF_API int bf_siftmgr_fuse_to_global(bf_siftmgr* local, bf_siftmgr* global, cons
 BF_API int bf_siftmgr_fuse_to_global_host(bf_siftmgr* local, bf_siftmgr* global, const float colorIntrinsics[16],
                                           const float* d_transforms, const float colorIntrinsicsInv[16]);
 BF_API int bf_siftmgr_fuse_error(bf_siftmgr* local, int* err);
+/* MI355X addition: the device search keeps its graph in LDS while the keys that have a valid correspondence number at most `keys` (default, and upper
+ * bound: what one workgroup's LDS holds - every chunk of 11 images fits) and in global memory beyond; 0: always in global memory (also BF_FUSE_LDS=0 in
+ * the environment at creation).  Same results either way.  _fuse_path: the form the last fuse ran in, 1 LDS / 0 global memory (syncs). */
+BF_API int bf_siftmgr_set_fuse_lds_limit(bf_siftmgr* local, uint32_t keys);
+BF_API int bf_siftmgr_fuse_path(bf_siftmgr* local, int* path);
 
 
 /* ------------------------------------------------------------------------- */
