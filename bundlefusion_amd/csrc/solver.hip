@@ -57,6 +57,7 @@ struct Dev {
     float *diagA, *rhs, *prec;
     float *delta, *r, *p, *Ap;
     uint2* densePairs; float* denseWeight; float* denseBlocks;
+    float* densePart; uint32_t* denseTicket;      // k_dense_wide: the four chains' Grams of a pair (4 x 256 floats) and its arrival count (0 between launches)
     const bf_cached_frame* cache;
     int* flags;
     int* gridBar;                    // one grid-barrier counter per Gauss-Newton iteration (k_pcg_coop)
@@ -513,6 +514,323 @@ __global__ __launch_bounds__(256) void k_dense_build(Dev d, Cfg c) {
             out[t] = ((part[0][e] + part[1][e]) + part[2][e]) + part[3][e];
         }
         __syncthreads();
+    }
+}
+
+// ------------------------------------------------------------------ the dense term, wide form (default; BF_DENSE_WIDE=0 keeps the two kernels above, whose
+// bits this one gives).  k_dense_build is ONE workgroup per pair that walks the pair's pixels in 19 dependent trips (80x60), and its four waves' MFMA chains are
+// the only part whose order reaches the result.  Here a workgroup is one CHAIN (pair, w): wave w of k_dense_build, pixels 256 t + 64 w + lane for t = 0, 1, ...
+//   1. the pair's weight: every chain workgroup counts the pair's correspondences itself (an integer: any partition is exact), DW_PIX pixels per thread in
+//      flight; chain 0 writes denseWeight[p].  k_dense_weight's launch is gone;
+//   2. rounds of DW_WAVES trips: wave v generates the rows of trip DW_WAVES r + v (k_dense_build's search, op by op, its loads issued ahead) and leaves both
+//      passes' tiles and weights in LDS; then wave 0 runs the acc0 steps (g even) and wave 1 the acc1 steps (g odd) of the trips in ascending order, depth pass
+//      before colour pass: the operands of every MFMA, lane by lane, and each accumulator's order are k_dense_build's;
+//   3. acc0[r] + acc1[r] goes to the pair's part w in global memory; the chain that arrives last at the pair's ticket adds ((part0 + part1) + part2) + part3
+//      and scatters the pair's DENSE_BLK entries.
+// THREADS: 256, at most 256 registers, so that two workgroups fit a CU.  LDS: 30 KB (tile rows hold their 13 columns; columns 13..15 of the MFMA operand are
+// the same +0 as k_dense_build's stored zeros).  Row generation and the count are bound by VALU issue, not by latency, so eight waves on a CU gain nothing over
+// four, and the smaller workgroup is placed sooner beside the voxel update (profiles/dense_term.md).
+constexpr uint32_t DW_WAVES = 4, DW_THREADS = DW_WAVES * 64, DW_COLS = 13, DW_PIX = 10;
+constexpr uint32_t DW_MAX_PAIRS = 2048;          // parts and tickets exist for this many pairs; problems that can have more take the two kernels above
+
+struct DenseWideLds {
+    float X[DW_WAVES][2][64][DW_COLS];
+    float W[DW_WAVES][2][64];
+    float acc[2][4][64];
+    float m[4][3][3];      // derivI's pair-uniform values of the pair (i, j): -(R_A * skew(D column k)), A = Tinv[j], D = T[i] ...
+    float trI[16];         // ... and mul44(A, D)
+    int wcount[DW_WAVES];
+    uint32_t last;
+};
+
+// derivI with its pair-uniform values read from LDS (derivIUniform fills them: the same operations on the same operands, once per workgroup instead of per pixel)
+BF_DEV void derivIUniform(const m44& A, const m44& D, float m[4][3][3], float trI[16]) {
+    const m44 tr = mul44(A, D);
+#pragma unroll
+    for (int e = 0; e < 16; ++e) trI[e] = tr.e[e];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float vx = D.e[k], vy = D.e[4 + k], vz = D.e[8 + k];
+        const float sk[3][3] = {{0.0f, -vz, vy}, {vz, 0.0f, -vx}, {-vy, vx, 0.0f}};
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int cc = 0; cc < 3; ++cc)
+                m[k][r][cc] = (A.e[r * 4 + 0] * sk[0][cc] + A.e[r * 4 + 1] * sk[1][cc] + A.e[r * 4 + 2] * sk[2][cc]) * -1.0f;
+    }
+}
+BF_DEV void derivIShared(const m44& A, const float (*m)[3][3], const float* trI, f3 p, float jac[3][6]) {
+    const float pt[3] = {p.x - trI[3], p.y - trI[7], p.z - trI[11]};
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+        for (int cc = 0; cc < 3; ++cc) {
+            jac[r][cc] = (-trI[0 * 4 + r]) * A.e[0 * 4 + cc] + (-trI[1 * 4 + r]) * A.e[1 * 4 + cc] + (-trI[2 * 4 + r]) * A.e[2 * 4 + cc];
+            float acc = pt[0] * m[r][0][cc];
+            acc += pt[1] * m[r][1][cc];
+            acc += pt[2] * m[r][2][cc];
+            acc += (-trI[0 * 4 + r]) * m[3][0][cc];
+            acc += (-trI[1 * 4 + r]) * m[3][1][cc];
+            acc += (-trI[2 * 4 + r]) * m[3][2][cc];
+            jac[r][3 + cc] = acc;
+        }
+    }
+}
+
+// bilinear<K> in two steps, so that the taps of all four images of a pixel are in flight together: bilinear<K> loads a tap only behind the test of the tap
+// before it, 16 dependent round trips per pixel.  loadTaps reads the four taps whatever they hold (addresses outside the image fall back to texel 0);
+// combineTaps is bilinear<K>'s arithmetic on them, tap by tap in its order.
+template <int K> struct Taps { float v[4][K]; bool in[4]; };
+template <int K>
+BF_DEV void loadTaps(float x, float y, const float* __restrict__ in, uint32_t W, uint32_t H, Taps<K>& t) {
+    const int x0 = (int)floorf(x), y0 = (int)floorf(y);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int px = x0 + (q & 1), py = y0 + (q >> 1);
+        t.in[q] = (uint32_t)px < W && (uint32_t)py < H;
+        const float* v = in + (t.in[q] ? (size_t)K * ((size_t)py * W + px) : (size_t)0);
+        if (K == 4) { const float4 f = *reinterpret_cast<const float4*>(v); t.v[q][0] = f.x; t.v[q][1 % K] = f.y; t.v[q][2 % K] = f.z; t.v[q][3 % K] = f.w; }
+        else if (K == 2) { const float2 f = *reinterpret_cast<const float2*>(v); t.v[q][0] = f.x; t.v[q][1 % K] = f.y; }
+        else t.v[q][0] = v[0];
+    }
+}
+template <int K>
+BF_DEV bool combineTaps(float x, float y, const Taps<K>& t, float* out) {
+    const int x0 = (int)floorf(x), y0 = (int)floorf(y);
+    const float alpha = x - (float)x0, beta = y - (float)y0;
+    float s0[K], s1[K], w0 = 0.0f, w1 = 0.0f;
+#pragma unroll
+    for (int k = 0; k < K; ++k) { s0[k] = 0.0f; s1[k] = 0.0f; }
+#define BF_TAP(Q, WGT, S, WS) \
+    if (t.in[Q] && t.v[Q][0] != BF_MINF) { _Pragma("unroll") for (int k = 0; k < K; ++k) S[k] += (WGT) * t.v[Q][k]; WS += (WGT); }
+    BF_TAP(0, 1.0f - alpha, s0, w0)
+    BF_TAP(1, alpha, s0, w0)
+    BF_TAP(2, 1.0f - alpha, s1, w1)
+    BF_TAP(3, alpha, s1, w1)
+#undef BF_TAP
+    float ss[K], ww = 0.0f;
+#pragma unroll
+    for (int k = 0; k < K; ++k) ss[k] = 0.0f;
+    if (w0 > 0.0f) { _Pragma("unroll") for (int k = 0; k < K; ++k) ss[k] += (1.0f - beta) * (s0[k] / w0); ww += (1.0f - beta); }
+    if (w1 > 0.0f) { _Pragma("unroll") for (int k = 0; k < K; ++k) ss[k] += beta * (s1[k] / w1); ww += beta; }
+    if (ww > 0.0f) { _Pragma("unroll") for (int k = 0; k < K; ++k) out[k] = ss[k] / ww; return true; }
+#pragma unroll
+    for (int k = 0; k < K; ++k) out[k] = BF_MINF;
+    return false;
+}
+
+// the rows of pixel idx of pair (i, j): k_dense_build's search and Jacobians, statement by statement; the loads come first, in two groups (the source pixel,
+// then every tap of the target), and a pixel that fails a test computes on until the taps are issued and is dropped then
+BF_DEV void denseRows(const Cfg& c, const bf_cached_frame& tgt, const bf_cached_frame& src, const float (*mI)[3][3], const float* trI, const m44& Tj, const m44& TiI, const m44& TjI,
+                      const m44& tr, uint32_t i, uint32_t j, float pw, bool useDepth, bool useColor, uint32_t idx, uint32_t npix,
+                      float Xd[13], float Xc[13], float& wd, float& wc) {
+    wd = 0.0f; wc = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 13; ++k) { Xd[k] = 0.0f; Xc[k] = 0.0f; }
+    const uint32_t ic = min(idx, npix - 1u);
+    const float4 cp4 = reinterpret_cast<const float4*>(src.d_cameraposDownsampled)[ic];
+    const float4 nj = reinterpret_cast<const float4*>(src.d_normalsDownsampled)[ic];
+    const float srcI = src.d_intensityDownsampled[ic];
+    bool ok = idx < npix && (cp4.z > c.denseDepthMin && cp4.z < c.denseDepthMax) && nj.x != BF_MINF;
+    const f3 cs = mk3(cp4.x, cp4.y, cp4.z);
+    const float n4[4] = {tr.e[0] * nj.x + tr.e[1] * nj.y + tr.e[2] * nj.z + tr.e[3] * nj.w,
+                         tr.e[4] * nj.x + tr.e[5] * nj.y + tr.e[6] * nj.z + tr.e[7] * nj.w,
+                         tr.e[8] * nj.x + tr.e[9] * nj.y + tr.e[10] * nj.z + tr.e[11] * nj.w,
+                         tr.e[12] * nj.x + tr.e[13] * nj.y + tr.e[14] * nj.z + tr.e[15] * nj.w};
+    const f3 cst = xform(tr, cs);
+    float u, v;
+    cameraToDepth(c, cst, u, v);
+    const int tx = f2i(roundf(u)), ty = f2i(roundf(v));
+    ok = ok && (tx >= 0 && ty >= 0 && tx < (int)c.W && ty < (int)c.H);
+    if (!ok) { u = 0.0f; v = 0.0f; }                  // a dropped pixel's taps: texel (0, 0)
+    Taps<4> tc, tn; Taps<2> td; Taps<1> ti;
+    loadTaps<4>(u, v, tgt.d_cameraposDownsampled, c.W, c.H, tc);
+    loadTaps<4>(u, v, tgt.d_normalsDownsampled, c.W, c.H, tn);
+    if (useColor) {
+        loadTaps<2>(u, v, tgt.d_intensityDerivsDownsampled, c.W, c.H, td);
+        loadTaps<1>(u, v, tgt.d_intensityDownsampled, c.W, c.H, ti);
+    }
+    if (!ok) return;
+    float ci[4], ni[4];
+    combineTaps<4>(u, v, tc, ci);
+    if (!(ci[2] > c.denseDepthMin && ci[2] < c.denseDepthMax)) return;
+    combineTaps<4>(u, v, tn, ni);
+    if (!(ni[0] != BF_MINF)) return;
+    const f3 ct = mk3(ci[0], ci[1], ci[2]);
+    const f3 nt = mk3(ni[0], ni[1], ni[2]);
+    const float dist = len3(cst - ct);
+    const float dN = n4[0] * ni[0] + n4[1] * ni[1] + n4[2] * ni[2] + n4[3] * ni[3];
+    if (!(dN >= c.denseNormalThresh && dist <= c.denseDistThresh)) return;
+    float jI[3][6], jJ[3][6];
+    if (i > 0) derivIShared(TjI, mI, trI, cs, jI);
+    if (j > 0) derivJ(TiI, Tj, cs, jJ);
+    if (useDepth) {
+        const f3 diff = ct - cst;
+        Xd[12] = dot3(diff, nt);
+        wd = c.wDepth * pw * powf(fmaxf(0.0f, 1.0f - ct.z / 2.0f), 2.5f);
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+            if (i > 0) Xd[k] = -(jI[0][k] * nt.x + jI[1][k] * nt.y + jI[2][k] * nt.z);
+            if (j > 0) Xd[6 + k] = -(jJ[0][k] * nt.x + jJ[1][k] * nt.y + jJ[2][k] * nt.z);
+        }
+    }
+    if (useColor) {
+        float dI[2], iT;
+        combineTaps<2>(u, v, td, dI);
+        combineTaps<1>(u, v, ti, &iT);
+        const float res = iT - srcI;
+        if (dI[0] != BF_MINF && fabsf(res) < c.denseColorThresh && sqrtf(dI[0] * dI[0] + dI[1] * dI[1]) > c.denseColorGradientMin) {
+            const float z2 = cst.z * cst.z;
+            const float P00 = c.fx / cst.z, P02 = -c.fx * cst.x / z2, P11 = c.fy / cst.z, P12 = -c.fy * cst.y / z2;
+            Xc[12] = res;
+            wc = c.wColor * pw * fmaxf(0.0f, 1.0f - fabsf(res) / (1.15f * c.denseColorThresh));
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+                if (i > 0) Xc[k] = dI[0] * (P00 * jI[0][k] + 0.0f * jI[1][k] + P02 * jI[2][k]) + dI[1] * (0.0f * jI[0][k] + P11 * jI[1][k] + P12 * jI[2][k]);
+                if (j > 0) Xc[6 + k] = dI[0] * (P00 * jJ[0][k] + 0.0f * jJ[1][k] + P02 * jJ[2][k]) + dI[1] * (0.0f * jJ[0][k] + P11 * jJ[1][k] + P12 * jJ[2][k]);
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(DW_THREADS, 2) void k_dense_wide(Dev d, Cfg c) {
+    if (d.flags[FL_DONE]) return;
+    __shared__ DenseWideLds S;
+    const uint32_t nPairs = min((uint32_t)d.flags[FL_NUM_PAIRS], DW_MAX_PAIRS);
+    const uint32_t npix = c.W * c.H;
+    const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const uint32_t nTrips = (npix + 255u) / 256u;
+    const bool useDepth = c.wDepth > 0.0f, useColor = c.wColor > 0.0f;
+    for (uint32_t q = blockIdx.x; q < 4u * nPairs; q += gridDim.x) {      // chain q: pair q / 4, wave q % 4 of k_dense_build
+        const uint32_t p = q >> 2, w = q & 3u;
+        const uint2 pr = d.densePairs[p];
+        const uint32_t i = pr.x, j = pr.y;
+        const m44 Ti = d.T[i], Tj = d.T[j], TiI = d.Tinv[i], TjI = d.Tinv[j];
+        const m44 tr = mul44(TiI, Tj);
+        const bf_cached_frame tgt = d.cache[i], src = d.cache[j];
+        if (tid == 0u && i > 0u) derivIUniform(TjI, Ti, S.m, S.trI);      // read behind the count's barriers; the previous chain's readers are behind its last barrier
+        // 1. the weight (k_dense_weight's tests; the loads of DW_PIX pixels are issued together, every address clamped into the image)
+        int count = 0;
+        for (uint32_t base = 0; base < npix; base += DW_THREADS * DW_PIX) {
+            float dep[DW_PIX]; uchar4 nu[DW_PIX];
+#pragma unroll
+            for (uint32_t k = 0; k < DW_PIX; ++k) {
+                const uint32_t idx = min(base + k * DW_THREADS + tid, npix - 1u);
+                dep[k] = src.d_depthDownsampled[idx];
+                nu[k] = reinterpret_cast<const uchar4*>(src.d_normalsDownsampledUCHAR4)[idx];
+            }
+            f3 nj[DW_PIX], qq[DW_PIX]; bool ok[DW_PIX]; float dt[DW_PIX]; uchar4 nt[DW_PIX]; int tx[DW_PIX], ty[DW_PIX];
+#pragma unroll
+            for (uint32_t k = 0; k < DW_PIX; ++k) {
+                const uint32_t idx = base + k * DW_THREADS + tid, ic = min(idx, npix - 1u);
+                const uint32_t x = ic % c.W, y = ic / c.W;
+                const f3 cp = depthToCamera(c, (int)x, (int)y, dep[k]);
+                ok[k] = idx < npix && (cp.z > c.denseDepthMin && cp.z < c.denseDepthMax) && (nu[k].x | nu[k].y | nu[k].z | nu[k].w);
+                nj[k] = mk3((float)nu[k].x / 255.0f * 2.0f - 1.0f, (float)nu[k].y / 255.0f * 2.0f - 1.0f, (float)nu[k].z / 255.0f * 2.0f - 1.0f);
+                nj[k] = rot(tr, nj[k]);
+                qq[k] = xform(tr, cp);
+                float u, v;
+                cameraToDepth(c, qq[k], u, v);
+                tx[k] = f2i(roundf(u)); ty[k] = f2i(roundf(v));
+                ok[k] = ok[k] && (tx[k] >= 0 && ty[k] >= 0 && tx[k] < (int)c.W && ty[k] < (int)c.H);
+                const uint32_t ti = ok[k] ? (uint32_t)(ty[k] * (int)c.W + tx[k]) : 0u;
+                dt[k] = tgt.d_depthDownsampled[ti];
+                nt[k] = reinterpret_cast<const uchar4*>(tgt.d_normalsDownsampledUCHAR4)[ti];
+            }
+#pragma unroll
+            for (uint32_t k = 0; k < DW_PIX; ++k) {
+                const f3 ct = depthToCamera(c, tx[k], ty[k], dt[k]);
+                const f3 nT = mk3((float)nt[k].x / 255.0f * 2.0f - 1.0f, (float)nt[k].y / 255.0f * 2.0f - 1.0f, (float)nt[k].z / 255.0f * 2.0f - 1.0f);
+                if (ok[k] && (ct.z > c.denseDepthMin && ct.z < c.denseDepthMax) && (nt[k].x | nt[k].y | nt[k].z | nt[k].w) &&
+                    dot3(nj[k], nT) >= c.denseNormalThresh && len3(qq[k] - ct) <= c.denseDistThresh) count++;
+            }
+        }
+        count = wave_sum_i(count);
+        __syncthreads();                              // the previous chain's readers of wcount and last are through
+        if (lane == 0) S.wcount[wave] = count;
+        __syncthreads();
+        int total = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < DW_WAVES; ++k) total += S.wcount[k];
+        float pw = (float)total;
+        if (pw > 0) { if (pw < 800) pw = 0; else pw = 1.0f / fminf(logf(pw), 9.0f); }
+        if (w == 0u && tid == 0u) d.denseWeight[p] = pw;
+        float* out = d.denseBlocks + (size_t)p * DENSE_BLK;
+        if (pw == 0.0f) {                             // all four chains of the pair find the same weight: none of them takes a ticket
+            if (w == 0u && tid < DENSE_BLK) out[tid] = 0.0f;
+            continue;
+        }
+        // 2. rows of DW_WAVES trips at once, then the chain over them in order
+        f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+        for (uint32_t t0 = 0; t0 < nTrips; t0 += DW_WAVES) {
+            if (t0 + wave < nTrips) {
+                float Xd[13], Xc[13], wd, wc;
+                denseRows(c, tgt, src, S.m, S.trI, Tj, TiI, TjI, tr, i, j, pw, useDepth, useColor, 256u * (t0 + wave) + 64u * w + lane, npix, Xd, Xc, wd, wc);
+#pragma unroll
+                for (int k = 0; k < 13; ++k) { S.X[wave][0][lane][k] = Xd[k]; S.X[wave][1][lane][k] = Xc[k]; }
+                S.W[wave][0][lane] = wd; S.W[wave][1][lane] = wc;
+            }
+            __syncthreads();
+            if (wave < 2u) {
+                const uint32_t nt = min(DW_WAVES, nTrips - t0), col = lane & 15u;
+                for (uint32_t t = 0; t < nt; ++t) {
+#pragma unroll
+                    for (int pass = 0; pass < 2; ++pass) {
+                        if (pass == 0 && !useDepth) continue;
+                        if (pass == 1 && !useColor) continue;
+#pragma unroll
+                        for (uint32_t g = 0; g < 16; g += 2) {
+                            const uint32_t row = 4u * (g + wave) + (lane >> 4);
+                            const float x = S.X[t][pass][row][min(col, DW_COLS - 1u)];
+                            const float b = col < DW_COLS ? x : 0.0f;
+                            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(S.W[t][pass][row] * b, b, acc, 0, 0, 0);
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+        }
+        // 3. acc0 + acc1 -> the pair's part w; the last chain of the pair sums the parts
+        if (wave < 2u) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) S.acc[wave][r][lane] = acc[r];
+        }
+        __syncthreads();
+        float* part = d.densePart + (size_t)p * 1024u;
+        static_assert(DW_THREADS == 256, "one thread per element of the chain's 16 x 16 Gram");
+        {                                             // D layout: lane l, reg r -> row 4*(l>>4)+r, col l&15
+            const uint32_t r = wave;
+            part[w * 256u + (4u * (lane >> 4) + r) * 16u + (lane & 15u)] = S.acc[0][r][lane] + S.acc[1][r][lane];
+        }
+        // hand-off to the chain of the pair that arrives last (k_batch_place's): EVERY storing wave drains its stores (a barrier waits for no counter), then one
+        // lane releases at agent scope - the chains of a pair run on different XCDs as a rule -, waits, and takes the ticket; the last arriver acquires and waits
+        // before the barrier that lets the other waves read the parts
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (tid == 0u) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            const uint32_t ticket = __hip_atomic_fetch_add(&d.denseTicket[p], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            S.last = ticket == 3u ? 1u : 0u;
+            if (S.last) {
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                d.denseTicket[p] = 0u;                // for the next launch
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            }
+        }
+        __syncthreads();
+        if (!S.last) continue;                        // block-uniform
+        if (tid < DENSE_BLK) {
+            const uint32_t t = tid;
+            uint32_t row, col;
+            if (t < 36) { row = t / 6; col = t % 6; }                        // ii
+            else if (t < 72) { row = 6 + (t - 36) / 6; col = 6 + (t - 36) % 6; }   // jj
+            else if (t < 108) { row = (t - 72) / 6; col = 6 + (t - 72) % 6; }      // ij (rows i, cols j)
+            else if (t < 114) { row = t - 108; col = 12; }                    // J_i^T r
+            else { row = 6 + (t - 114); col = 12; }                          // J_j^T r
+            const uint32_t e = row * 16 + col;
+            out[t] = ((part[e] + part[256u + e]) + part[512u + e]) + part[768u + e];
+        }
     }
 }
 
@@ -1244,6 +1562,7 @@ struct bf_solver {
     std::vector<float> convergence;
     float hMaxRes = 0.0f; int hMaxIdx = 0; int hBarrierFail = 0;
     bool pcgWide = true;                 // (BF_PCG_WIDE=0: the 256-thread kernel for every problem, for the A/B)
+    bool denseWide = true;               // (BF_DENSE_WIDE=0: k_dense_weight + k_dense_build, one workgroup per pair, for the A/B)
     int pcgGroups = -1;                  // BF_PCG_GROUPS: -1 automatic, 0 single-workgroup kernel, n forced group count
     uint32_t maxCoopGroups = COOP_MAX_GROUPS;
     bool forceVecGlobal = false;
@@ -1269,6 +1588,7 @@ int bf_solver_create(uint32_t maxNumberOfImages, uint32_t maxNumResiduals, const
     BF_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pcg_small<3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)PCG_LDS_MAX));
     BF_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pcg_small<4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)PCG_LDS_MAX));
     if (const char* e = getenv("BF_PCG_WIDE")) s->pcgWide = atoi(e) != 0;
+    if (const char* e = getenv("BF_DENSE_WIDE")) s->denseWide = atoi(e) != 0;
     if (const char* e = getenv("BF_PCG_GROUPS")) s->pcgGroups = atoi(e);        // 0: single-workgroup kernel, n > 0: force n groups
     if (const char* e = getenv("BF_PCG_VEC_GLOBAL")) s->forceVecGlobal = atoi(e) != 0;      // tests: the large-N form (vectors in global memory) on a small problem
     {   // every group of the cooperative PCG must be resident at once (each may take a whole CU's LDS): never ask for more than
@@ -1294,10 +1614,13 @@ int bf_solver_create(uint32_t maxNumberOfImages, uint32_t maxNumResiduals, const
     BF_TRY(R.device(&d.slotP, (size_t)d.maxSlots * 4)); BF_TRY(R.device(&d.diagA, N * 36)); BF_TRY(R.device(&d.rhs, N * 6)); BF_TRY(R.device(&d.prec, N * 6));
     BF_TRY(R.device(&d.delta, N * 6)); BF_TRY(R.device(&d.r, N * 6)); BF_TRY(R.device(&d.p, N * 6)); BF_TRY(R.device(&d.Ap, N * 6));
     BF_TRY(R.device(&d.densePairs, (size_t)d.maxPairs)); BF_TRY(R.device(&d.denseWeight, (size_t)d.maxPairs));
+    const size_t widePairs = std::min<size_t>(d.maxPairs, DW_MAX_PAIRS);
+    BF_TRY(R.device(&d.densePart, widePairs * 1024)); BF_TRY(R.device(&d.denseTicket, widePairs));
     BF_TRY(R.device(&d.denseBlocks, (size_t)d.maxPairs * DENSE_BLK)); BF_TRY(R.device(&d.flags, FL_COUNT)); BF_TRY(R.device(&d.gridBar, 32)); BF_TRY(R.device(&d.energies, 40));
     BF_TRY(R.device(&d.maxRes, 1)); BF_TRY(R.device(&d.maxIdx, 1)); BF_TRY(R.device(&d.highCount, 1)); BF_TRY(R.device(&d.numEntriesPerRow, N));
     BF_TRY(R.device(&d.scanRow, 3 * (N + 1))); BF_TRY(R.device(&d.coopVec, s->coopVecFloats)); BF_TRY(R.device(&d.maxResPart, MAXRES_GROUPS)); BF_TRY(R.device(&d.maxIdxPart, MAXRES_GROUPS));
     (void)hipMemset(d.flags, 0, FL_COUNT * sizeof(int));
+    (void)hipMemset(d.denseTicket, 0, widePairs * sizeof(uint32_t));
     *out = guard.dismiss();
     return BF_OK;
 }
@@ -1367,8 +1690,13 @@ int bf_solver_solve(bf_solver* s, bf_entry_j* d_corr, uint32_t numCorr, const in
         }
         if (useDense) {
             const uint32_t g = std::min<uint32_t>(std::max<uint32_t>(N * (N - 1) / 2, 1u), 1024u);
-            hipLaunchKernelGGL(k_dense_weight, dim3(g), dim3(256), 0, st, d, c);
-            hipLaunchKernelGGL(k_dense_build, dim3(g), dim3(256), 0, st, d, c);
+            const uint32_t pairsAtMost = std::min<uint32_t>(usePairwise ? N * (N - 1) / 2 : N - 1, d.maxPairs);
+            if (s->denseWide && pairsAtMost <= DW_MAX_PAIRS)         // four chain workgroups per pair, weight included
+                hipLaunchKernelGGL(k_dense_wide, dim3(4 * g), dim3(DW_THREADS), 0, st, d, c);
+            else {
+                hipLaunchKernelGGL(k_dense_weight, dim3(g), dim3(256), 0, st, d, c);
+                hipLaunchKernelGGL(k_dense_build, dim3(g), dim3(256), 0, st, d, c);
+            }
         }
         hipLaunchKernelGGL(k_slots, dim3(std::min<uint32_t>(div_up(d.maxSlots, 4), 2048u)), dim3(256), 0, st, d, c, useDense);
         hipLaunchKernelGGL(k_rows, dim3(div_up(N, 4)), dim3(256), 0, st, d);
