@@ -21,6 +21,8 @@ import pytest
 from bundlefusion_amd import synth
 from bundlefusion_amd.capi import default_hash_params, camera_params, FREE_ENTRY, VOX_PER_BLOCK
 
+from tests.voxel_update_ref import inverse44_f32 as _inverse44_f32          # (the float32 inverse pose; it lives beside the float64 restatement of the update)
+
 pytestmark = pytest.mark.gpu
 
 BAND = 2e-4            # pixels, images up to 640 wide (measured need: 1.1e-4, gpurun r04c; until round 3: 5e-4)
@@ -78,24 +80,6 @@ def _boundary_dist(pos, ptr, poses, cam, voxel, n_voxels, chunk=16384):
         idx = (bptr[:, None] + l[None, :]).reshape(-1)
         out[idx] = dist.reshape(-1).float()
     return out.cpu().numpy()
-
-
-def _inverse44_f32(T):
-    """bf::inverse44 (csrc/bf_device.h) operation by operation in float32: the world -> camera transform both the product and the oracle project voxels with"""
-    m = np.asarray(T, np.float32).reshape(16)
-    f = np.float32
-    adj = np.zeros(16, np.float32)
-    for r in range(4):
-        for c in range(4):
-            rows = [i for i in range(4) if i != c]; cols = [j for j in range(4) if j != r]
-            s_ = f(-1.0) if ((r + c) & 1) else f(1.0)
-            A = lambda i, j: m[rows[i] * 4 + cols[j]]
-            adj[r * 4 + c] = f(f(f(f(f(f(s_ * A(0, 0)) * A(1, 1)) * A(2, 2)) - f(f(f(s_ * A(0, 0)) * A(1, 2)) * A(2, 1))) - f(f(f(s_ * A(1, 0)) * A(0, 1)) * A(2, 2))) +
-                                 f(f(f(s_ * A(1, 0)) * A(0, 2)) * A(2, 1)))
-            adj[r * 4 + c] = f(f(adj[r * 4 + c] + f(f(f(s_ * A(2, 0)) * A(0, 1)) * A(1, 2))) - f(f(f(s_ * A(2, 0)) * A(0, 2)) * A(1, 1)))
-    det = f(f(f(f(m[0] * adj[0]) + f(m[1] * adj[4])) + f(m[2] * adj[8])) + f(m[3] * adj[12]))
-    detr = f(f(1.0) / det)
-    return (adj * detr).astype(np.float32).reshape(4, 4)
 
 
 def _block_keys(bad, eh):
