@@ -1486,6 +1486,20 @@ class Pipeline:
         check(lib.bf_pipeline_save_mesh_simplified(self._h, str(filename).encode(), T, C.byref(p), C.byref(sp), C.byref(st), C.byref(sst), C.byref(nt)))
         return st.as_dict(), sst.as_dict(), nt.value
 
+    def measure_mesh(self, reference, max_distance, direction=0, sample_spacing=0.0, sample_mode=0, cell_size=None, transform=None, min_faces=0, largest=False):
+        """bf_pipeline_measure_mesh: the scan's mesh (extracted, welded with the transform, cleaned and - cell_size given - simplified on the device) measured
+        against reference = (positions [nv,3] float32, faces [nf,3] uint32) as host arrays; direction 0: the scan against the reference (accuracy), 1: the reference
+        against the scan (completeness).  Returns (clean stats dict, simplify stats dict or None, distance stats dict, triangles)."""
+        pos, fc = _host_mesh(reference)
+        p = MeshCleanParams(int(min_faces), int(bool(largest)), 0); sp = None if cell_size is None else MeshSimplifyParams(float(cell_size), 0)
+        dp = MeshDistanceParams(float(max_distance), float(sample_spacing), int(sample_mode))
+        st = MeshCleanStats(); sst = MeshSimplifyStats(); dst = MeshDistanceStats(); nt = C.c_uint32()
+        T = mat16(transform) if transform is not None else None
+        check(lib.bf_pipeline_measure_mesh(self._h, T, C.byref(p), C.byref(sp) if sp is not None else None, pos.ctypes.data_as(C.c_void_p), fc.ctypes.data_as(C.c_void_p),
+                                           C.c_uint32(len(pos)), C.c_uint32(len(fc)), C.byref(dp), C.c_int32(int(direction)), C.byref(st), C.byref(sst), C.byref(dst), C.byref(nt)))
+        d = dst.as_dict(); d["max_distance"] = float(dp.maxDistance)
+        return st.as_dict(), (sst.as_dict() if sp is not None else None), d, nt.value
+
     def mesh_recolour_defaults(self):
         """bf_pipeline_get_mesh_recolour_defaults: the MeshRecolourParams the pipeline uses where none are given"""
         rp = MeshRecolourParams()
@@ -1838,6 +1852,32 @@ class MarchingCubesHashSDF:
         check(lib.bf_marching_cubes_save_mesh_simplified(self._h, str(filename).encode(), T, C.byref(p), C.byref(sp), C.byref(st), C.byref(sst)))
         return st.as_dict(), sst.as_dict()
 
+    # ---- MI355X additions: the distance of a mesh to a reference surface in HBM (csrc/meshdistance.hip)
+    def distance(self, a, b, max_distance, sample_spacing=0.0, sample_mode=0, download=True):
+        """bf_marching_cubes_distance (+ download): (distance float64, nearest face uint32, weight float64, stats dict), or the stats dict alone without download.
+        a, b: (positions [nv,3] float32, faces [nf,3] uint32) as contiguous torch cuda tensors; a None: the result of the latest of the object's simplify, clean
+        and weld.  Mesh a is sampled (sample_mode 0: its vertices; 1: its surface every sample_spacing metres) and measured against the surface b."""
+        p = MeshDistanceParams(float(max_distance), float(sample_spacing), int(sample_mode)); st = MeshDistanceStats()
+        keep = []
+
+        def mesh(m):
+            pos, faces = m
+            assert pos.is_contiguous() and faces.is_contiguous() and pos.numel() % 3 == 0 and faces.numel() % 3 == 0
+            keep.append(m)
+            return IndexedMesh(pos.data_ptr() or None, None, faces.data_ptr() or None, pos.numel() // 3, faces.numel() // 3)
+        mb = mesh(b)
+        ma = mesh(a) if a is not None else None
+        check(lib.bf_marching_cubes_distance(self._h, C.byref(ma) if ma is not None else None, C.byref(mb), C.byref(p), C.byref(st)))
+        d = st.as_dict(); d["max_distance"] = float(p.maxDistance)
+        return self.download_distance(d["numSamples"]) + (d,) if download else d
+
+    def download_distance(self, num_samples):
+        """bf_marching_cubes_download_distance: (distance, nearest face, weight) of the first num_samples samples of the last measurement"""
+        n = int(num_samples)
+        hd = np.zeros(n, np.float64); hf = np.zeros(n, np.uint32); hw = np.zeros(n, np.float64)
+        check(lib.bf_marching_cubes_download_distance(self._h, hd.ctypes.data_as(C.c_void_p), hf.ctypes.data_as(C.c_void_p), hw.ctypes.data_as(C.c_void_p), C.c_uint32(n)))
+        return hd, hf, hw
+
     # ---- MI355X additions: the mesh's vertex colours taken from the key frames in HBM (csrc/meshrecolour.hip)
     def recolour(self, mesh, frames, width, height, intrinsics, params):
         """bf_marching_cubes_recolour + download: (colours [nv,3] float32, views [nv] uint32, stats dict).  mesh: (positions, colours, normals, faces) as contiguous
@@ -2068,6 +2108,71 @@ def mesh_simplify_host(positions, colors, faces, cell_size, normals=False):
                                     mp.ctypes.data_as(C.c_void_p), len(pos), len(fc), C.byref(st)))
     nv, nf = st.numVerticesOut, st.numFacesOut
     return op[:nv].copy(), oc[:nv].copy(), (on[:nv].copy() if normals else None), of[:nf].copy(), st.as_dict(), mp
+
+
+class MeshDistanceParams(C.Structure):
+    _fields_ = [("maxDistance", C.c_float), ("sampleSpacing", C.c_float), ("sampleMode", C.c_int32)]
+
+
+class MeshDistanceStats(C.Structure):
+    _fields_ = [("numSamples", C.c_uint64), ("numWithin", C.c_uint64), ("numBeyond", C.c_uint64), ("numDegenerateA", C.c_uint32), ("numDegenerateB", C.c_uint32),
+                ("maxWithin", C.c_double), ("sumW", C.c_int64), ("sumWD", C.c_int64), ("sumWD2", C.c_int64), ("sumWBeyond", C.c_int64),
+                ("scaleW", C.c_int32), ("scaleWD", C.c_int32), ("scaleWD2", C.c_int32), ("reserved", C.c_int32), ("histogram", C.c_int64 * 1024)]
+
+    def as_dict(self):
+        d = {n: getattr(self, n) for n, _ in self._fields_ if n not in ("reserved", "histogram")}
+        d["histogram"] = np.array(self.histogram, np.int64)
+        return d
+
+
+def mesh_distance_summary(stats, thresholds=()):
+    """the figures a caller takes from a bf_mesh_distance_stats dict: mean, rms, max, median and p90 (to the upper edge of their histogram bin of maxDistance /
+    1024), the share of the weight that lies beyond, and per threshold in metres the share of the weight within it (to a bin).  max_distance: stats' own key,
+    set by the callers below.  Plain binary64 over the exact integer sums."""
+    w = stats["sumW"] / 2.0 ** stats["scaleW"]; wb = stats["sumWBeyond"] / 2.0 ** stats["scaleW"]
+    D = stats["max_distance"]
+    hist = stats["histogram"].astype(np.float64) / 2.0 ** stats["scaleW"]
+    cum = np.cumsum(hist)
+
+    def pct(q):
+        return float("nan") if w <= 0 else (int(np.searchsorted(cum, q * w, "left")) + 1) * D / 1024.0
+    out = {"samples": stats["numSamples"], "mean": stats["sumWD"] / 2.0 ** stats["scaleWD"] / w if w > 0 else float("nan"),
+           "rms": float(np.sqrt(stats["sumWD2"] / 2.0 ** stats["scaleWD2"] / w)) if w > 0 else float("nan"), "median": pct(0.5), "p90": pct(0.9), "max": stats["maxWithin"],
+           "beyond_share": wb / (w + wb) if w + wb > 0 else 0.0}
+    for t in thresholds:
+        k = min(1024, int(np.floor(t * 1024.0 / D)))
+        out["within_%g" % t] = float(cum[k - 1] / (w + wb)) if k >= 1 and w + wb > 0 else 0.0
+    return out
+
+
+def _host_mesh(m):
+    pos = np.ascontiguousarray(m[0], np.float32).reshape(-1, 3); fc = np.ascontiguousarray(m[1], np.uint32).reshape(-1, 3)
+    return pos, fc
+
+
+def mesh_distance_host(a, b, max_distance, sample_spacing=0.0, sample_mode=0):
+    """bf_mesh_distance_host, the definition on one core: (distance float64, nearest face uint32, weight float64, stats dict) of mesh a = (positions, faces)
+    against the surface b = (positions, faces).  Host-only."""
+    pa, fa = _host_mesh(a); pb, fb = _host_mesh(b)
+    p = MeshDistanceParams(float(max_distance), float(sample_spacing), int(sample_mode)); st = MeshDistanceStats()
+    n = C.c_uint64()
+    check(lib.bf_mesh_distance_sample_count_host(pa.ctypes.data_as(C.c_void_p), fa.ctypes.data_as(C.c_void_p), C.c_uint32(len(pa)), C.c_uint32(len(fa)), C.byref(p), C.byref(n)))
+    n = n.value
+    hd = np.zeros(n, np.float64); hf = np.zeros(n, np.uint32); hw = np.zeros(n, np.float64)
+    check(lib.bf_mesh_distance_host(pa.ctypes.data_as(C.c_void_p), fa.ctypes.data_as(C.c_void_p), C.c_uint32(len(pa)), C.c_uint32(len(fa)), pb.ctypes.data_as(C.c_void_p),
+                                    fb.ctypes.data_as(C.c_void_p), C.c_uint32(len(pb)), C.c_uint32(len(fb)), C.byref(p), hd.ctypes.data_as(C.c_void_p), hf.ctypes.data_as(C.c_void_p),
+                                    hw.ctypes.data_as(C.c_void_p), C.c_uint32(n), C.byref(st)))
+    d = st.as_dict(); d["max_distance"] = float(p.maxDistance)
+    return hd, hf, hw, d
+
+
+def write_ply_indexed_error(filename, positions, faces, distance, max_distance):
+    """bf_write_ply_indexed_error: the mesh with its vertex-mode distance as a colour ramp (blue 0, green, red max_distance; beyond: magenta).  Host-only."""
+    pos, fc = _host_mesh((positions, faces))
+    d = np.ascontiguousarray(distance, np.float64)
+    assert len(d) == len(pos)
+    check(lib.bf_write_ply_indexed_error(str(filename).encode(), pos.ctypes.data_as(C.c_void_p), fc.ctypes.data_as(C.c_void_p), d.ctypes.data_as(C.c_void_p), C.c_float(max_distance),
+                                         C.c_uint32(len(pos)), C.c_uint32(len(fc))))
 
 
 def mesh_clean_host(positions, colors, faces, min_faces=0, largest=False, normals=False):

@@ -2587,6 +2587,8 @@ struct PlMeshJob {
     const bf_mesh_recolour_params* recolour; bf_mesh_recolour_stats* recolourStats; const bf_mesh_recolour_frame* frames; uint32_t numFrames; const float* intrinsics;
     // texture non-null (with clean): the textured save from the same frames; recolour and simplify are optional before it
     const bf_mesh_texture_params* texture; bf_mesh_texture_stats* textureStats;
+    // distance non-null (with clean): no file, the mesh is measured against the reference mesh (bf_pipeline_measure_mesh); simplify is optional before it
+    const bf_mesh_distance_params* distance; bf_mesh_distance_stats* distanceStats; const float* refPositions; const uint32_t* refFaces; uint32_t numRefVertices, numRefFaces; int32_t direction;
 };
 
 // on the volume thread (timings: on the calling thread), between two batches.  The view's exclusive section is a render's: the preparation stream has finished
@@ -2600,7 +2602,10 @@ int plMeshExec(void* ctx) {
     BF_TRY(bf_scene_begin_view(p->scene, I, &p->cam, &hd, &hp));
     int rc = bf_marching_cubes_extract_gpu(p->marchingCubes, &hd, &hp, nullptr, nullptr, 0);
     if (rc == BF_OK) rc = bf_marching_cubes_get_triangles_gpu(p->marchingCubes, nullptr, nullptr, &j.nt);
-    if (rc == BF_OK && j.texture)
+    if (rc == BF_OK && j.distance)
+        rc = bf_marching_cubes_measure_mesh(p->marchingCubes, j.transform, j.clean, j.simplify, j.refPositions, j.refFaces, j.numRefVertices, j.numRefFaces, j.distance, j.direction, j.stats,
+                                            j.simplifyStats, j.distanceStats);
+    else if (rc == BF_OK && j.texture)
         rc = bf_marching_cubes_save_mesh_textured(p->marchingCubes, j.filename, j.transform, j.clean, j.frames, j.numFrames, p->im->wInt, p->im->hInt, j.intrinsics, j.texture, j.recolour,
                                                   j.simplify, j.stats, j.recolourStats, j.simplifyStats, j.textureStats);
     else if (rc == BF_OK && j.recolour)
@@ -2628,7 +2633,7 @@ static int plSaveMesh(bf_pipeline* p, PlMeshJob& j) {
         BF_TRY(bf_marching_cubes_set_stream(p->marchingCubes, p->sVolume));
     }
     VolumeQueue::Cmd c;
-    c.op = j.texture ? VolumeQueue::Op::SaveMeshTextured : j.recolour ? VolumeQueue::Op::SaveMeshRecoloured : j.simplify ? VolumeQueue::Op::SaveMeshSimplified : VolumeQueue::Op::SaveMesh; c.render = plMeshExec; c.renderCtx = &j;
+    c.op = j.distance ? VolumeQueue::Op::MeasureMesh : j.texture ? VolumeQueue::Op::SaveMeshTextured : j.recolour ? VolumeQueue::Op::SaveMeshRecoloured : j.simplify ? VolumeQueue::Op::SaveMeshSimplified : VolumeQueue::Op::SaveMesh; c.render = plMeshExec; c.renderCtx = &j;
     return p->vol.postAndWait(c);
 }
 
@@ -2656,6 +2661,19 @@ int bf_pipeline_save_mesh_simplified(bf_pipeline* p, const char* filename, const
                                      bf_mesh_clean_stats* cleanStats, bf_mesh_simplify_stats* simplifyStats, uint32_t* numTriangles) {
     BF_REQUIRE(p && filename && cleanParams && simplifyParams, "null argument");
     PlMeshJob j = {p, filename, transform, 0, 0, 0, cleanParams, cleanStats, simplifyParams, simplifyStats, nullptr, nullptr, nullptr, 0, nullptr};
+    BF_TRY(plSaveMesh(p, j));
+    if (numTriangles) *numTriangles = j.nt;
+    return BF_OK;
+}
+
+// the scan's mesh measured against a reference mesh: the simplified save's command without the file (bf_marching_cubes_measure_mesh)
+int bf_pipeline_measure_mesh(bf_pipeline* p, const float* transform, const bf_mesh_clean_params* cleanParams, const bf_mesh_simplify_params* simplifyParams, const float* referencePositions,
+                             const uint32_t* referenceFaces, uint32_t numVertices, uint32_t numFaces, const bf_mesh_distance_params* distanceParams, int32_t direction,
+                             bf_mesh_clean_stats* cleanStats, bf_mesh_simplify_stats* simplifyStats, bf_mesh_distance_stats* distanceStats, uint32_t* numTriangles) {
+    BF_REQUIRE(p && cleanParams && distanceParams, "null argument");
+    PlMeshJob j = {p, "", transform, 0, 0, 0, cleanParams, cleanStats, simplifyParams, simplifyStats, nullptr, nullptr, nullptr, 0, nullptr};
+    j.distance = distanceParams; j.distanceStats = distanceStats; j.refPositions = referencePositions; j.refFaces = referenceFaces; j.numRefVertices = numVertices; j.numRefFaces = numFaces;
+    j.direction = direction;
     BF_TRY(plSaveMesh(p, j));
     if (numTriangles) *numTriangles = j.nt;
     return BF_OK;

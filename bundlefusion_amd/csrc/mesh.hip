@@ -35,6 +35,7 @@
 #include "bf_meshweld.h"
 #include "bf_meshclean.h"
 #include "bf_meshsimplify.h"
+#include "bf_meshdistance.h"
 #include "bf_meshrecolour.h"
 #include "bf_meshtexture.h"
 #include "bf_volume.h"
@@ -321,6 +322,10 @@ struct bf_marching_cubes {
     MeshSimplify simplify;              // the simplified mesh of the last bf_marching_cubes_simplify, in HBM (meshsimplify.hip)
     MeshRecolour recolour;              // the colours of the last bf_marching_cubes_recolour, in HBM (meshrecolour.hip)
     MeshTexture texture;                // the atlas, face frames and texture coordinates of the last bf_marching_cubes_texture, in HBM (meshtexture.hip)
+    MeshDistance distance;              // the per-sample result of the last bf_marching_cubes_distance, in HBM (meshdistance.hip)
+    float* d_refPositions = nullptr; uint32_t* d_refFaces = nullptr;          // the reference mesh bf_marching_cubes_measure_mesh uploads
+    uint32_t capRefVertices = 0, capRefFaces = 0;
+    int lastStage = 0;                  // bf_marching_cubes_distance's default mesh A: 0 none, 1 the last weld, 2 the last clean, 3 the last simplify (whichever ran latest)
     int lastMesh = 0;                   // bf_marching_cubes_recolour's and _texture's default input: 0 none, 1 the last clean, 2 the last simplify (whichever ran later)
     bf::Resources res;                  // owns every buffer above, the weld's, the clean's, the simplification's, the recolouring's and the texture's included
 };
@@ -504,6 +509,7 @@ int bf_marching_cubes_weld(bf_marching_cubes* m, const bf_mc_triangle* d_triangl
     m->recolour.numVertices = m->recolour.numFaces = 0;          // a recolour's result ends here: the arrays it points into may be regrown
     m->texture.numFaces = m->texture.atlasWidth = m->texture.atlasHeight = 0;          // a texture's too: its faces are another mesh's
     BF_TRY(meshweld_run(m->weld, m->res, m->stream, d_triangles, numTriangles, transform));
+    m->lastStage = 1;
     if (out) { out->d_positions = m->weld.d_positions; out->d_colors = m->weld.d_colors; out->d_faces = m->weld.d_faces; out->numVertices = m->weld.numVertices; out->numFaces = m->weld.numFaces; }
     return BF_OK;
 }
@@ -540,7 +546,7 @@ int bf_marching_cubes_clean(bf_marching_cubes* m, const bf_indexed_mesh* in, con
     m->recolour.numVertices = m->recolour.numFaces = 0;          // (as the weld)
     m->texture.numFaces = m->texture.atlasWidth = m->texture.atlasHeight = 0;
     BF_TRY(meshclean_run(m->clean, m->res, m->stream, in ? *in : last, *params, stats));
-    m->lastMesh = 1;
+    m->lastMesh = 1; m->lastStage = 2;
     const MeshClean& c = m->clean;
     if (out) { out->d_positions = c.d_positions; out->d_colors = c.d_colors; out->d_normals = c.hasNormals ? c.normals.d_normals : nullptr; out->d_faces = c.d_faces; out->numVertices = c.numVertices; out->numFaces = c.numFaces; }
     return BF_OK;
@@ -585,7 +591,7 @@ int bf_marching_cubes_simplify(bf_marching_cubes* m, const bf_indexed_mesh* in, 
     last.d_positions = m->clean.d_positions; last.d_colors = m->clean.d_colors; last.d_faces = m->clean.d_faces; last.numVertices = m->clean.numVertices; last.numFaces = m->clean.numFaces;
     m->texture.numFaces = m->texture.atlasWidth = m->texture.atlasHeight = 0;          // (as the weld)
     BF_TRY(meshsimplify_run(m->simplify, m->res, m->stream, in ? *in : last, *params, stats));
-    m->lastMesh = 2;
+    m->lastMesh = 2; m->lastStage = 3;
     const MeshSimplify& s = m->simplify;
     if (out) { out->d_positions = s.d_positions; out->d_colors = s.d_colors; out->d_normals = s.hasNormals ? s.normals.d_normals : nullptr; out->d_faces = s.d_faces; out->numVertices = s.numVertices; out->numFaces = s.numFaces; }
     return BF_OK;
@@ -626,6 +632,62 @@ int bf_marching_cubes_save_mesh_simplified(bf_marching_cubes* m, const char* fil
     std::vector<uint32_t> faces(3 * (size_t)sm.numFaces);
     BF_TRY(bf_marching_cubes_download_simplified(m, pos.data(), col.data(), nrm.data(), faces.data()));
     return bf_write_ply_indexed_normals(filename, pos.data(), sm.d_normals ? nrm.data() : nullptr, col.data(), faces.data(), sm.numVertices, sm.numFaces);
+}
+
+// Distance of a mesh to a surface, both in HBM (meshdistance.hip); a null: the last simplify's result, else the last clean's, else the last weld's.  On the
+// object's stream.
+int bf_marching_cubes_distance(bf_marching_cubes* m, const bf_indexed_mesh* a, const bf_indexed_mesh* b, const bf_mesh_distance_params* params, bf_mesh_distance_stats* stats) {
+    BF_REQUIRE(m && b && params, "null argument");
+    bf_indexed_mesh last;
+    if (!a) {
+        const MeshSimplify& s = m->simplify; const MeshClean& c = m->clean; const MeshWeld& w = m->weld;
+        BF_REQUIRE(m->lastStage, "no input mesh and no result of a simplify, a clean or a weld to take");
+        if (m->lastStage == 3) { last.d_positions = s.d_positions; last.d_colors = s.d_colors; last.d_faces = s.d_faces; last.numVertices = s.numVertices; last.numFaces = s.numFaces; }
+        else if (m->lastStage == 2) { last.d_positions = c.d_positions; last.d_colors = c.d_colors; last.d_faces = c.d_faces; last.numVertices = c.numVertices; last.numFaces = c.numFaces; }
+        else {
+            last.d_positions = w.d_positions; last.d_colors = w.d_colors; last.d_faces = w.d_faces; last.numVertices = w.numVertices; last.numFaces = w.numFaces;
+        }
+    }
+    return meshdistance_run(m->distance, m->res, m->stream, a ? *a : last, *b, *params, stats);
+}
+
+int bf_marching_cubes_download_distance(bf_marching_cubes* m, double* h_distance, uint32_t* h_face, double* h_weight, uint32_t capacity) {
+    BF_REQUIRE(m, "null argument");
+    const MeshDistance& d = m->distance;
+    const uint32_t n = std::min(capacity, d.numSamples);
+    if (h_distance && n) BF_HIP_TRY(hipMemcpyAsync(h_distance, d.d_distance, 8 * (size_t)n, hipMemcpyDeviceToHost, m->stream));
+    if (h_face && n) BF_HIP_TRY(hipMemcpyAsync(h_face, d.d_face, 4 * (size_t)n, hipMemcpyDeviceToHost, m->stream));
+    if (h_weight && n) BF_HIP_TRY(hipMemcpyAsync(h_weight, d.d_weight, 8 * (size_t)n, hipMemcpyDeviceToHost, m->stream));
+    BF_HIP_TRY(hipStreamSynchronize(m->stream));
+    return BF_OK;
+}
+
+// weld of the last extraction + clean (without normals) + the optional simplify + the upload of the reference mesh + the distance; m_meshData is not touched
+int bf_marching_cubes_measure_mesh(bf_marching_cubes* m, const float transform[16], const bf_mesh_clean_params* cleanParams, const bf_mesh_simplify_params* simplifyParams,
+                                   const float* h_refPositions, const uint32_t* h_refFaces, uint32_t numVertices, uint32_t numFaces, const bf_mesh_distance_params* distanceParams,
+                                   int32_t direction, bf_mesh_clean_stats* cleanStats, bf_mesh_simplify_stats* simplifyStats, bf_mesh_distance_stats* distanceStats) {
+    BF_REQUIRE(m && cleanParams && distanceParams, "null argument");
+    BF_REQUIRE(direction == 0 || direction == 1, "direction is not 0 (scan to reference) or 1 (reference to scan)");
+    BF_REQUIRE((numVertices == 0 || h_refPositions) && (numFaces == 0 || h_refFaces), "null reference array");
+    BF_REQUIRE(numFaces <= 300000000u && numVertices <= 900000000u, "too many faces or vertices for one measurement");
+    bf_mesh_clean_params cp = *cleanParams;
+    cp.computeNormals = 0;
+    BF_TRY(bf_marching_cubes_weld(m, nullptr, 0, transform, nullptr));
+    bf_clean_mesh cm;
+    BF_TRY(bf_marching_cubes_clean(m, nullptr, &cp, &cm, cleanStats));
+    if (simplifyParams) {
+        bf_mesh_simplify_params sp = *simplifyParams;
+        sp.computeNormals = 0;
+        BF_TRY(bf_marching_cubes_simplify(m, nullptr, &sp, &cm, simplifyStats));
+    }
+    if (numVertices > m->capRefVertices || !m->d_refPositions) { m->capRefVertices = 0; BF_TRY(m->res.regrow(&m->d_refPositions, std::max<size_t>(3 * (size_t)numVertices, 1))); m->capRefVertices = numVertices; }
+    if (numFaces > m->capRefFaces || !m->d_refFaces) { m->capRefFaces = 0; BF_TRY(m->res.regrow(&m->d_refFaces, std::max<size_t>(3 * (size_t)numFaces, 1))); m->capRefFaces = numFaces; }
+    if (numVertices) BF_HIP_TRY(hipMemcpyAsync(m->d_refPositions, h_refPositions, 12 * (size_t)numVertices, hipMemcpyHostToDevice, m->stream));
+    if (numFaces) BF_HIP_TRY(hipMemcpyAsync(m->d_refFaces, h_refFaces, 12 * (size_t)numFaces, hipMemcpyHostToDevice, m->stream));
+    bf_indexed_mesh scan, ref;
+    scan.d_positions = cm.d_positions; scan.d_colors = cm.d_colors; scan.d_faces = cm.d_faces; scan.numVertices = cm.numVertices; scan.numFaces = cm.numFaces;
+    ref.d_positions = m->d_refPositions; ref.d_colors = nullptr; ref.d_faces = m->d_refFaces; ref.numVertices = numVertices; ref.numFaces = numFaces;
+    return direction == 0 ? bf_marching_cubes_distance(m, &scan, &ref, distanceParams, distanceStats) : bf_marching_cubes_distance(m, &ref, &scan, distanceParams, distanceStats);
 }
 
 // the result of the last clean, or of the last simplify if that ran later

@@ -42,7 +42,7 @@ int VolumeQueue::dispatch(const Cmd& c, bool batch) {
         return bf_scene_garbage_collect(scene_);
     case Op::Flush:
         return submitPending();
-    case Op::Render: case Op::SaveMesh: case Op::SaveMeshSimplified: case Op::SaveMeshRecoloured: case Op::SaveMeshTextured: {
+    case Op::Render: case Op::SaveMesh: case Op::SaveMeshSimplified: case Op::SaveMeshRecoloured: case Op::SaveMeshTextured: case Op::MeasureMesh: {
         BF_TRY(submitPending());
         const int rc = c.render ? c.render(c.renderCtx) : BF_ERR_INVALID_ARG;
         if (c.reply) { c.reply->rc = rc; if (rc != BF_OK) c.reply->message = bf_last_error(); }

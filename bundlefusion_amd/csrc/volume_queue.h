@@ -17,7 +17,7 @@ namespace bf {
 // 12 % of the wall time), so they do not serialize with the ~60 launches of the detect and bundling streams on one CPU thread.
 class VolumeQueue {
 public:
-    enum class Op : int { Integrate = BF_SCENE_OP_INTEGRATE, Deintegrate = BF_SCENE_OP_DEINTEGRATE, Reintegrate = BF_SCENE_OP_REINTEGRATE, Collect, Flush, Render, SaveMesh, SaveMeshSimplified, SaveMeshRecoloured, SaveMeshTextured };
+    enum class Op : int { Integrate = BF_SCENE_OP_INTEGRATE, Deintegrate = BF_SCENE_OP_DEINTEGRATE, Reintegrate = BF_SCENE_OP_REINTEGRATE, Collect, Flush, Render, SaveMesh, SaveMeshSimplified, SaveMeshRecoloured, SaveMeshTextured, MeasureMesh };
     // what the poster of a Render command waits for: the command's own status and message (not the worker's sticky error, unless the flush before it failed)
     struct Reply { bool done = false; int rc = BF_OK; std::string message; };
     // The three operators carry the frame (data, optional interleaved texels), its pose T0 (a re-integration: from T0 to T1) and the event that completes the
@@ -27,7 +27,7 @@ public:
     // guarantees by keeping them on the poster's stack until the worker has set reply->done.  SaveMesh (the mesh of the volume between two frames' batches,
     // bf_pipeline_save_mesh and bf_pipeline_save_mesh_clean) is posted and answered the same way, with its job in render / renderCtx: the queue knows nothing
     // about marching cubes either; SaveMeshSimplified (bf_pipeline_save_mesh_simplified), SaveMeshRecoloured (bf_pipeline_save_mesh_recoloured) and SaveMeshTextured
-    // (bf_pipeline_save_mesh_textured) likewise.
+    // (bf_pipeline_save_mesh_textured) likewise, and MeasureMesh (bf_pipeline_measure_mesh), which writes no file.
     struct Cmd {
         Op op = Op::Flush; bf_depth_camera_data data = {nullptr, nullptr}; const void* texels = nullptr; float T0[16] = {}, T1[16] = {}; void* waitEvent = nullptr;
         int (*render)(void*) = nullptr; void* renderCtx = nullptr; Reply* reply = nullptr;

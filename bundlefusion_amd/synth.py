@@ -210,6 +210,19 @@ def scene_room(k, width=640, height=480, frames_per_loop=1800, bob=0.0):
     return scene_room_at(trajectory_pose(k, frames_per_loop, bob=bob), intrinsics(width, height), width, height)
 
 
+def room_mesh():
+    """The true surface of S2 as an indexed mesh: the room box, then the eight boxes of _clutter_boxes(), each as 8 corners (corner c takes hi on axis d where
+    bit d of c is set) and 12 faces - (positions [72,3] float32, faces [108,3] uint32).  Orientation carries no meaning: the distance to it is unsigned."""
+    quads = [(0, 2, 6, 4), (1, 5, 7, 3), (0, 4, 5, 1), (2, 3, 7, 6), (0, 1, 3, 2), (4, 6, 7, 5)]          # x lo, x hi, y lo, y hi, z lo, z hi
+    pos, faces = [], []
+    for lo, hi in [(ROOM_MIN, ROOM_MAX)] + _clutter_boxes():
+        base = len(pos)
+        pos += [[(hi if (c >> d) & 1 else lo)[d] for d in range(3)] for c in range(8)]
+        for a, b, c, d in quads:
+            faces += [[base + a, base + b, base + c], [base + a, base + c, base + d]]
+    return np.array(pos, np.float64).astype(np.float32), np.array(faces, np.uint32)
+
+
 # ---------------------------------------------------------------- parallel rendering of a stream
 def render_frames(indices, width=640, height=480, workers=None, frames_per_loop=1800, bob=0.0):
     """[scene_room(k) for k in indices], rendered by `workers` plain-python subprocesses that execute this file

@@ -899,6 +899,78 @@ BF_API int bf_mesh_texture_host(const float* h_positions, const float* h_colors,
  * is theirs followed by the byte 6 and the six floats u_a v_a u_b v_b u_c v_c (38 bytes).  reference: none, the definition is the library's own */
 BF_API int bf_write_ply_textured(const char* filename, const char* textureFileName, const float* h_positions, const float* h_normals, const float* h_colors, const uint32_t* h_faces,
                                  const float* h_faceUV, uint32_t numVertices, uint32_t numFaces);
+/* ---- MI355X additions: the distance of a mesh to a reference surface in HBM (csrc/meshdistance.hip; DESIGN.md "Mesh distance: the definition"; reference: none,
+ * the definition is the library's own) ----
+ * Mesh A (the samples) is measured against mesh B (the surface); both are indexed meshes, positions n x 3 binary32, faces m x 3 uint32, colours not read.  All
+ * arithmetic is binary64 from the binary32 inputs, one rounding per operation, no contraction, IEEE division and square root; dot(x, y) = (x0*y0 + x1*y1) + x2*y2.
+ * Degenerate: with u = b - a, v = c - a, n = (u1*v2 - u2*v1, u2*v0 - u0*v2, u0*v1 - u1*v0) and N2 = dot(n, n), a face is degenerate iff not (0 < N2 < inf) (so is
+ * every face with a corner that is not finite).  A degenerate face of B is never a candidate, one of A gives no samples; both are counted.
+ * Samples: sampleMode 0 - the vertices of A in vertex order, weight 1, those no face uses included.  sampleMode 1 - per non-degenerate face in face order, with
+ * L = sqrt(max(dot(b-a, b-a), dot(c-a, c-a), dot(c-b, c-b))) and n = max(1, ceil(L / (double)sampleSpacing)) (sampleSpacing == 0: n = 1), the n*n centroids of
+ * its congruent sub-triangles: sample k = 0 .. n*n - 1 lies in row j = n - r, r the least integer with r*r >= n*n - k, at t = k - (n*n - r*r) in the row, i = t / 2;
+ * t even (upright): u = (3i + 1) / (3n), v = (3j + 1) / (3n); t odd (inverted): u = (3i + 2) / (3n), v = (3j + 2) / (3n), the numerators and 3n exact in binary64;
+ * p = (a + u * (b - a)) + v * (c - a) per component, in binary64 (the sample is not rounded to binary32); weight (0.5 * sqrt(N2)) / (double)(n*n).  Sample ids: the
+ * prefix sum of the faces' n*n.
+ * Distance: d2(p, f) = dot(p - q, p - q), q the closest point of Ericson, Real-Time Collision Detection 5.1.5, with ab = b-a, ac = c-a, ap = p-a, bp = p-b,
+ * cp = p-c, d1 = dot(ab, ap), d2 = dot(ac, ap), d3 = dot(ab, bp), d4 = dot(ac, bp), d5 = dot(ab, cp), d6 = dot(ac, cp), vc = d1*d4 - d3*d2, vb = d5*d2 - d1*d6,
+ * va = d3*d6 - d5*d4, the first rule that holds: d1 <= 0 and d2 <= 0: q = a; d3 >= 0 and d4 <= d3: q = b; vc <= 0, d1 >= 0, d3 <= 0: q = a + (d1 / (d1 - d3)) * ab;
+ * d6 >= 0 and d5 <= d6: q = c; vb <= 0, d2 >= 0, d6 <= 0: q = a + (d2 / (d2 - d6)) * ac; va <= 0, d4 - d3 >= 0, d5 - d6 >= 0: q = b + ((d4 - d3) / ((d4 - d3) +
+ * (d5 - d6))) * (c - b); otherwise den = 1 / ((va + vb) + vc), q = (a + ab * (vb * den)) + ac * (vc * den).  A sample's result is the minimum of d2 over the
+ * non-degenerate faces of B, the lowest face index among equal d2.  With D = (double)maxDistance: minimum > D * D (or no face): beyond, distance +inf, face
+ * 0xFFFFFFFF; otherwise within, distance sqrt(minimum).
+ * Sums: q(x, k) = (int64)floor(x * 2^k + 0.5).  With L the least integer with numSamples <= 2^L, E = 0 (sampleMode 0) or 6 (sampleMode 1) and e the least integer
+ * in [-20, 6] with D <= 2^e: scaleW = 62 - L - E, scaleWD = scaleW - e, scaleWD2 = scaleW - 2e.  Over the within-samples sumW = sum q(w, scaleW), sumWD =
+ * sum q(w * d, scaleWD), sumWD2 = sum q((w * d) * d, scaleWD2), histogram[min(1023, floor(d * (1024.0 / D)))] += q(w, scaleW); over the beyond-samples
+ * sumWBeyond = sum q(w, scaleW).  maxWithin is the greatest within-distance (0 without one).  No sum passes 2^62 + numSamples; no result depends on the order in
+ * which threads run or on the search structure.
+ * Refused with BF_ERR_INVALID_ARG, nothing written and the last result staying: maxDistance not finite, <= 0 or > 64; sampleSpacing negative or not finite;
+ * sampleMode not 0 or 1; a face id >= numVertices in either mesh; a finite component with |x| >= 1024 at a corner of any face of either mesh; in
+ * sampleMode 0 a component of a vertex of A that is not finite or has |x| >= 1024; a face of A with n > 1024 or a sample weight >= 64 (lower sampleSpacing);
+ * more than 2^28 samples; more than 300 000 000 faces in either mesh.  (A corner that is not finite makes its face degenerate: skipped and counted, not refused.)
+ * An empty A gives zero samples; an empty or all-degenerate B puts every sample beyond.  BF_ERR_CAPACITY, the last result staying: the search grid over B (cell
+ * edge max(D, 2^-9) * (1 + 2^-10); a face is listed in every cell of its bounding box that its plane may cross, a sliver with sin^2 of its angle at a below 2^-20 in
+ * every cell of its box) would hold more than 2^27 (face, cell) pairs. */
+typedef struct bf_mesh_distance_params { float maxDistance; float sampleSpacing; int32_t sampleMode; } bf_mesh_distance_params;
+/* a sum S with scale k stands for S / 2^k: mean = (sumWD / 2^scaleWD) / (sumW / 2^scaleW), rms^2 = (sumWD2 / 2^scaleWD2) / (sumW / 2^scaleW) */
+typedef struct bf_mesh_distance_stats {
+    uint64_t numSamples, numWithin, numBeyond;
+    uint32_t numDegenerateA, numDegenerateB;
+    double maxWithin;
+    int64_t sumW, sumWD, sumWD2, sumWBeyond;
+    int32_t scaleW, scaleWD, scaleWD2, reserved;
+    int64_t histogram[1024];
+} bf_mesh_distance_stats;
+/* Measures mesh `a` against mesh `b` (device arrays of any origin, d_colors not read) on the object's stream and waits for it twice (the refusals and counts,
+ * then the sums).  a NULL: the result of the object's last simplify, else of its last clean, else of its last weld - the latest of the three stages that has run, so a
+ * mesh of an earlier extraction is never taken behind a newer weld (BF_ERR_INVALID_ARG if none has).  The
+ * per-sample result stays on the device with the object until its next measurement or destroy.  stats may be NULL.  reference: none, the definition is the
+ * library's own */
+BF_API int bf_marching_cubes_distance(bf_marching_cubes* m, const bf_indexed_mesh* a, const bf_indexed_mesh* b, const bf_mesh_distance_params* params, bf_mesh_distance_stats* stats);
+/* host copies of the last measurement's per-sample arrays, at most `capacity` samples of each (any of them may be NULL).  reference: none, the definition is
+ * the library's own */
+BF_API int bf_marching_cubes_download_distance(bf_marching_cubes* m, double* h_distance, uint32_t* h_face, double* h_weight, uint32_t capacity);
+/* weld of the last extraction (with the transform) + clean (its normals skipped) + (simplifyParams non-NULL) simplify + the upload of the reference mesh (host
+ * arrays, kept on the device with the object) + the measurement: direction 0 measures the scan against the reference (accuracy), direction 1 the reference against
+ * the scan (completeness).  The per-sample result is bf_marching_cubes_download_distance's; m_meshData is not touched.  Any stats may be NULL.  reference: none,
+ * the definition is the library's own */
+BF_API int bf_marching_cubes_measure_mesh(bf_marching_cubes* m, const float transform[16], const bf_mesh_clean_params* cleanParams, const bf_mesh_simplify_params* simplifyParams,
+                                          const float* h_refPositions, const uint32_t* h_refFaces, uint32_t numVertices, uint32_t numFaces, const bf_mesh_distance_params* distanceParams,
+                                          int32_t direction, bf_mesh_clean_stats* cleanStats, bf_mesh_simplify_stats* simplifyStats, bf_mesh_distance_stats* distanceStats);
+/* The number of samples the definition takes from mesh A (host arrays; with every refusal that concerns A alone).  Host only.  reference: none, the definition
+ * is the library's own */
+BF_API int bf_mesh_distance_sample_count_host(const float* h_positionsA, const uint32_t* h_facesA, uint32_t numVerticesA, uint32_t numFacesA, const bf_mesh_distance_params* params,
+                                              uint64_t* numSamples);
+/* The definition on one core (needs no device): host arrays in, host arrays out, the same closest-point function as the kernels, over a grid of its own whose
+ * cells follow the faces' size and are searched ring by ring.  The first min(capacity, numSamples) samples are written; any output may be NULL.  reference:
+ * none, the definition is the library's own */
+BF_API int bf_mesh_distance_host(const float* h_positionsA, const uint32_t* h_facesA, uint32_t numVerticesA, uint32_t numFacesA, const float* h_positionsB, const uint32_t* h_facesB,
+                                 uint32_t numVerticesB, uint32_t numFacesB, const bf_mesh_distance_params* params, double* h_distance, uint32_t* h_face, double* h_weight,
+                                 uint32_t capacity, bf_mesh_distance_stats* stats);
+/* bf_write_ply_indexed with the vertex-mode distance as the colours (host only).  t = (float)(d / (double)maxDistance); a vertex with d <= maxDistance gets
+ * (max(0, 2t - 1), 1 - |2t - 1|, max(0, 1 - 2t)) in binary32 - blue at 0 through green to red at maxDistance -, any other (beyond, NaN) gets (1, 0, 1).
+ * reference: none, the definition is the library's own */
+BF_API int bf_write_ply_indexed_error(const char* filename, const float* h_positions, const uint32_t* h_faces, const double* h_distance, float maxDistance, uint32_t numVertices,
+                                      uint32_t numFaces);
 /* the generated case tables (edge mask per case, up to 5 triangles of edge indices, -1 terminated), for inspection / tests */
 BF_API int bf_marching_cubes_tables(uint16_t edgeTable[256], int8_t triTable[256 * 16]);
 

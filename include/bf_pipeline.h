@@ -408,6 +408,16 @@ BF_API int bf_pipeline_save_mesh_clean(bf_pipeline* p, const char* filename, con
 BF_API int bf_pipeline_save_mesh_simplified(bf_pipeline* p, const char* filename, const float* transform, const bf_mesh_clean_params* cleanParams,
                                             const bf_mesh_simplify_params* simplifyParams, bf_mesh_clean_stats* cleanStats, bf_mesh_simplify_stats* simplifyStats,
                                             uint32_t* numTriangles);
+/* The scan's mesh measured against a reference surface from inside the frame loop (bf_marching_cubes_measure_mesh; bf_hip.h has the definition of the distance):
+ * extraction, weld with the transform, clean, (simplifyParams non-NULL) simplify, the upload of the reference mesh (host arrays: positions numVertices x 3 float,
+ * faces numFaces x 3 uint32) and the measurement - direction 0: the scan against the reference (accuracy), 1: the reference against the scan (completeness).  No
+ * file is written.  A typed command of the volume thread's queue like the simplified save's, between two frames' batches; the caller waits for its own command
+ * only.  cleanParams and distanceParams must not be NULL; simplifyParams, the stats and numTriangles may be.  The same refusal for a sharded volume; the
+ * reconstruction is left alone.  reference: none, the definition is the library's own */
+BF_API int bf_pipeline_measure_mesh(bf_pipeline* p, const float* transform, const bf_mesh_clean_params* cleanParams, const bf_mesh_simplify_params* simplifyParams,
+                                    const float* referencePositions, const uint32_t* referenceFaces, uint32_t numVertices, uint32_t numFaces,
+                                    const bf_mesh_distance_params* distanceParams, int32_t direction, bf_mesh_clean_stats* cleanStats, bf_mesh_simplify_stats* simplifyStats,
+                                    bf_mesh_distance_stats* distanceStats, uint32_t* numTriangles);
 /* The same command with bf_marching_cubes_recolour behind the clean (bf_marching_cubes_save_mesh_recoloured; bf_hip.h has the definition): the vertices' colours
  * are taken from the stored integration frames 0, frameStride, 2 * frameStride, ... that have a valid optimised pose (bf_pipeline_save_point_cloud's rule), under
  * the optimised trajectory: camera to mesh is transform * pose (bf_device.h's product; the pose alone without a transform), the intrinsics are those the

@@ -824,6 +824,25 @@ public:
                             bf_mesh_clean_stats* cleanStats = nullptr, bf_mesh_simplify_stats* simplifyStats = nullptr) {
         check(bf_marching_cubes_save_mesh_simplified(m_h, filename.c_str(), transform ? transform->m : nullptr, &cleanParams, &simplifyParams, cleanStats, simplifyStats));
     }
+    // The distance of mesh `a` (NULL: the latest of the object's simplify, clean and weld) to the surface `b`, both in device memory (bf_marching_cubes_distance;
+    // bf_hip.h has the definition): the summary; the per-sample distances, nearest faces and weights stay on the device until the next measurement
+    bf_mesh_distance_stats distance(const bf_indexed_mesh* a, const bf_indexed_mesh& b, const bf_mesh_distance_params& params) {
+        bf_mesh_distance_stats out;
+        check(bf_marching_cubes_distance(m_h, a, &b, &params, &out));
+        return out;
+    }
+    // host copies of the last measurement's per-sample arrays, at most `capacity` samples of each (any of them may be null)
+    void downloadDistance(double* distance, unsigned int* face, double* weight, unsigned int capacity) { check(bf_marching_cubes_download_distance(m_h, distance, face, weight, capacity)); }
+    // weld of the last extraction + clean + (simplifyParams) simplify + the measurement against a reference mesh in host memory; direction 0: the scan against the
+    // reference (accuracy), 1: the reference against the scan (completeness)
+    bf_mesh_distance_stats measureMesh(const bf_mesh_clean_params& cleanParams, const bf_mesh_simplify_params* simplifyParams, const float* referencePositions,
+                                       const unsigned int* referenceFaces, unsigned int numVertices, unsigned int numFaces, const bf_mesh_distance_params& distanceParams,
+                                       int direction = 0, const mat4f* transform = nullptr, bf_mesh_clean_stats* cleanStats = nullptr, bf_mesh_simplify_stats* simplifyStats = nullptr) {
+        bf_mesh_distance_stats out;
+        check(bf_marching_cubes_measure_mesh(m_h, transform ? transform->m : nullptr, &cleanParams, simplifyParams, referencePositions, referenceFaces, numVertices, numFaces, &distanceParams,
+                                             direction, cleanStats, simplifyStats, &out));
+        return out;
+    }
     // The last clean's (or, if later, the last simplify's) result with its vertex colours taken on the device from `frames` (bf_marching_cubes_recolour; a frame
     // is filled from its camera-to-mesh pose by bf_mesh_recolour_frame_from_pose): the input's arrays with the object's own colour array, valid until the next
     // extract, weld, clean, simplify, recolour or destruction.  The mesh needs normals (computeNormals of the clean).

@@ -9,7 +9,12 @@ bf_mesh_recolour_host on the host route; --mesh-recolour-best: the best view in 
 the recolouring's stats, its time and the mean absolute colour difference across the cleaned mesh's edges before and after, for both modes.  --mesh-texture
 (device route) writes the mesh with a texture atlas from the same frames (bf_pipeline_save_mesh_textured: the PLY and a PNG next to it; after the recolouring and
 the simplification if those are asked for) and prints the texture's stats, the times of its stages, the one-core
-route's time and whether its atlas is the device's, and the held-out colour measurement of profiles/mesh_texture.md."""
+route's time and whether its atlas is the device's, and the held-out colour measurement of profiles/mesh_texture.md.  --mesh-evaluate measures the mesh the
+other options describe (cleaned, simplified) against synth.room_mesh(), the true surface of the synthetic room, in both directions on the device
+(bf_pipeline_measure_mesh: scan -> reference is the accuracy, reference -> scan the completeness) and prints mean, RMS, median, 90th percentile, max, the share
+within one voxel and the share beyond --mesh-evaluate-max; --mesh-evaluate-against PLY measures against a mesh on disk instead; --mesh-evaluate-spacing sets the
+surface sampling (the reference is always sampled on its surface; the scan by its vertices unless --mesh-evaluate-surface); --mesh-error-ply PATH writes the
+measured mesh with its distance as a colour ramp; with --mesh-host the one-core route (bf_mesh_distance_host) runs the scan -> reference direction on the same arrays for comparison."""
 import ctypes as C
 import time
 
@@ -28,6 +33,12 @@ def add_arguments(ap):
     ap.add_argument("--mesh-recolour", action="store_true", help="take the (cleaned) mesh's vertex colours from the stored frames under the optimised trajectory")
     ap.add_argument("--mesh-recolour-stride", type=int, default=0, metavar="N", help="recolour from every Nth frame (default: s_submapSize, the key frames)")
     ap.add_argument("--mesh-texture", action="store_true", help="write the mesh with a texture atlas from the stored frames (a PNG next to the PLY); the stride is --mesh-recolour-stride")
+    ap.add_argument("--mesh-evaluate", action="store_true", help="measure the mesh against the true surface of the synthetic room (synth.room_mesh()), both directions")
+    ap.add_argument("--mesh-evaluate-against", default=None, metavar="PLY", help="measure the mesh against this PLY instead")
+    ap.add_argument("--mesh-evaluate-max", type=float, default=0.1, metavar="METRES", help="maxDistance of the measurement: samples farther than this count as beyond (default 0.1)")
+    ap.add_argument("--mesh-evaluate-spacing", type=float, default=0.01, metavar="METRES", help="sampleSpacing of the surface sampling (default 0.01)")
+    ap.add_argument("--mesh-evaluate-surface", action="store_true", help="sample the scan's surface too (area-weighted) instead of taking its vertices")
+    ap.add_argument("--mesh-error-ply", default=None, metavar="PATH", help="write the measured mesh with its vertices' distance to the reference as a colour ramp")
     ap.add_argument("--mesh-recolour-best", action="store_true", help="each vertex takes its best view (greatest weight) instead of the weighted blend of all views")
 
 
@@ -321,8 +332,102 @@ def _host(p, path, a):
     mc.close()
 
 
+def read_ply_mesh(path):
+    """(positions [nv,3] float32, faces [nf,3] uint32) of a binary little-endian PLY as this library writes them (float / uchar vertex properties, faces as a
+    uchar-counted int list, optionally followed by a uchar-counted float list)"""
+    raw = open(path, "rb").read()
+    head, body = raw.split(b"end_header\n", 1)
+    lines = head.decode("ascii").split("\n")
+    assert lines[0] == "ply" and "format binary_little_endian 1.0" in lines, "not a binary little-endian PLY"
+    nv = nf = 0; fields = []; section = None; face_lists = 0
+    for ln in lines:
+        t = ln.split()
+        if t[:1] == ["element"]:
+            section = t[1]
+            if section == "vertex": nv = int(t[2])
+            if section == "face": nf = int(t[2])
+        elif t[:1] == ["property"] and section == "vertex":
+            fields.append((t[2], {"float": "<f4", "uchar": "u1", "int": "<i4", "double": "<f8"}[t[1]]))
+        elif t[:2] == ["property", "list"] and section == "face":
+            face_lists += 1
+    vt = np.dtype(fields)
+    v = np.frombuffer(body, vt, nv)
+    ft = np.dtype([("n", "u1"), ("v", "<u4", 3)] + ([("m", "u1"), ("uv", "<f4", 6)] if face_lists == 2 else []))
+    f = np.frombuffer(body, ft, nf, nv * vt.itemsize)
+    assert (f["n"] == 3).all(), "a face that is not a triangle"
+    return np.stack([v["x"], v["y"], v["z"]], 1).astype(np.float32), np.ascontiguousarray(f["v"], np.uint32)
+
+
+def _distance_line(name, st, voxel):
+    s = bf.capi.mesh_distance_summary(st, (voxel,))
+    return ("%s: %d samples (%d faces of the samples' mesh and %d of the surface degenerate); mean %.5f m, rms %.5f m, median %.5f m, 90 %% %.5f m, max %.5f m; within one voxel (%g m) %.4f; "
+            "beyond %g m %.4f" % (name, s["samples"], st["numDegenerateA"], st["numDegenerateB"], s["mean"], s["rms"], s["median"], s["p90"], s["max"], voxel, s["within_%g" % voxel],
+                                  st["max_distance"], s["beyond_share"]))
+
+
+def _evaluate(p, a):
+    """the measurement from the frame loop in both directions, then stage by stage on an object of its own (the error PLY from there), then the one-core route"""
+    import torch
+    from bundlefusion_amd import synth
+    capi = bf.capi
+    ref = read_ply_mesh(a.mesh_evaluate_against) if a.mesh_evaluate_against else synth.room_mesh()
+    what = a.mesh_evaluate_against or "synth.room_mesh()"
+    # the reconstruction lives in its first camera's frame; the room's surface in the scene's: the first frame's true pose takes the scan there (a PLY on disk is
+    # taken to be in the scan's frame already)
+    first = getattr(a, "first", 0)
+    T = None if a.mesh_evaluate_against else synth.trajectory_pose(first, bob=getattr(a, "bob", 0.0))
+    D, spacing, voxel = a.mesh_evaluate_max, a.mesh_evaluate_spacing, float(p.gas.s_SDFVoxelSize)
+    cell = a.mesh_simplify_cell if a.mesh_simplify_cell > 0 else None
+    smode, sspacing = (1, spacing) if a.mesh_evaluate_surface else (0, 0.0)
+    t0 = time.perf_counter()
+    cst, sst, acc, nt = p.measure_mesh(ref, D, 0, sspacing, smode, cell, T, a.mesh_min_faces, a.mesh_largest)
+    t1 = time.perf_counter()
+    _, _, com, _ = p.measure_mesh(ref, D, 1, spacing, 1, cell, T, a.mesh_min_faces, a.mesh_largest)
+    t2 = time.perf_counter()
+    print("mesh evaluation against %s (%d vertices, %d faces), %d triangles; cleaned: %s;%s" % (what, len(ref[0]), len(ref[1]), nt, _stats_line(cst),
+                                                                                               " simplified at %g m: %s;" % (cell, _simplify_line(sst)) if sst else ""))
+    print("  " + _distance_line("accuracy (scan -> reference, %s)" % ("surface every %g m" % spacing if smode else "vertices"), acc, voxel) + "; bf_pipeline_measure_mesh %.3f s" % (t1 - t0))
+    print("  " + _distance_line("completeness (reference -> scan, surface every %g m)" % spacing, com, voxel) + "; bf_pipeline_measure_mesh %.3f s" % (t2 - t1))
+    # stage by stage
+    mc = capi.MarchingCubesHashSDF.from_global_app_state(p.gas)
+    t0 = time.perf_counter()
+    mc.extract_gpu(p.scene())
+    capi.check(capi.lib.bf_marching_cubes_weld(mc._h, None, 0, capi.mat16(T) if T is not None else None, None))
+    pos, col, _, faces, _ = mc.clean(None, a.mesh_min_faces, a.mesh_largest, False)
+    if cell:
+        pos, col, _, faces, _ = mc.simplify(None, cell, False)
+    t1 = time.perf_counter()
+    refd = (torch.from_numpy(ref[0]).cuda(), torch.from_numpy(ref[1].view(np.int32)).cuda())
+    scand = (torch.from_numpy(pos).cuda(), torch.from_numpy(faces.view(np.int32)).cuda())
+    times = []
+    for _ in range(2):
+        t2 = time.perf_counter()
+        st0 = mc.distance(None, refd, D, sspacing, smode, download=False)
+        times.append(time.perf_counter() - t2)
+    t3 = time.perf_counter()
+    st1 = mc.distance(refd, scand, D, spacing, 1, download=False)
+    t4 = time.perf_counter()
+    print("mesh evaluation (device route, stage by stage): extract + weld + clean%s + download %.4f s; scan -> reference %.4f s (first call, buffers allocated) and %.4f s; reference -> scan %.4f s"
+          % (" + simplify" if cell else "", t1 - t0, times[0], times[1], t4 - t3))
+    if a.mesh_error_ply:
+        d = mc.distance(None, refd, D, 0.0, 0)[0]
+        capi.write_ply_indexed_error(a.mesh_error_ply, pos, faces, d, D)
+        print("mesh error PLY %s: %d vertices coloured blue (0) through green to red (%g m), %d beyond in magenta" % (a.mesh_error_ply, len(d), D, int(np.isinf(d).sum())))
+    mc.close()
+    if a.mesh_host:
+        # one direction only: the one-core route walks the rings of its grid out to maxDistance for every sample that has nothing near it, which the millions
+        # of surface samples of the reference -> scan direction make minutes
+        t5 = time.perf_counter()
+        h0 = capi.mesh_distance_host((pos, faces), ref, D, sspacing, smode)
+        t6 = time.perf_counter()
+        same = np.array_equal(h0[3]["histogram"], st0["histogram"]) and {k: v for k, v in h0[3].items() if k != "histogram"} == {k: v for k, v in st0.items() if k != "histogram"}
+        print("mesh evaluation (host route) on one core (bf_mesh_distance_host): scan -> reference %.3f s; its summary %s the device's" % (t6 - t5, "is" if same else "IS NOT"))
+
+
 def write(p, a):
     """p: the Pipeline after process_end_of_sequence / synchronize; a: the parsed arguments"""
+    if a.mesh_evaluate or a.mesh_evaluate_against:
+        _evaluate(p, a)
     if a.mesh and a.mesh_texture:
         _textured(p, a)
         return

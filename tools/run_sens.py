@@ -15,6 +15,10 @@ s_submapSize: the key frames) under the optimised trajectory, before the simplif
 bf_mesh_recolour_host with --mesh-host); both print the recolouring's stats and its time.
 --mesh-texture (with --mesh): write the mesh with a texture atlas from the same frames, a PNG next to the PLY (bf_pipeline_save_mesh_textured; after the
 recolouring and the simplification if those are asked for); prints the texture's stats and times and compares with bf_mesh_texture_host on one core.
+--mesh-evaluate-against other.ply: measure the mesh (cleaned, simplified as the other options say) against a PLY on disk in both directions on the device
+(bf_pipeline_measure_mesh) and print mean, RMS, median, 90th percentile, max, the share within one voxel and the share beyond --mesh-evaluate-max (default
+0.1 m); --mesh-evaluate-spacing sets the surface sampling, --mesh-evaluate-surface samples the scan's surface too, --mesh-error-ply err.ply writes the mesh
+coloured by its distance; --mesh-evaluate measures against synth.room_mesh(), which is the truth for a recording of the synthetic room only.
 --point-cloud FILE [--point-cloud-stride N --point-cloud-cell M]: the stored frames on the stride (default s_submapSize: the key frames) under the optimised
 trajectory as a coloured, oriented point cloud, one point per cell of M metres (default 0.005), thinned on the device (bf_pipeline_save_point_cloud);
 --point-cloud-host FILE: the same file by the host route on one core.  Both print frame and point counts and the seconds spent.

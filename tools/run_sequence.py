@@ -5,6 +5,8 @@ usage: python tools/run_sequence.py [--frames N] [--voxel 0.01] [--host] [--timi
                                      [--mesh-simplify-cell METRES]    (simplify the cleaned mesh before it is written, one vertex per grid cell: tools/mesh_out.py)
                                      [--mesh-recolour [--mesh-recolour-stride N] [--mesh-recolour-best]]    (vertex colours from the stored key frames: tools/mesh_out.py)
                                      [--mesh-texture]    (a texture atlas from the stored key frames, a PNG next to the PLY: tools/mesh_out.py)
+                                     [--mesh-evaluate | --mesh-evaluate-against other.ply] [--mesh-evaluate-max METRES] [--mesh-evaluate-spacing METRES] [--mesh-evaluate-surface]
+                                     [--mesh-error-ply err.ply]    (the mesh's distance to the room's true surface, or to a PLY, both directions: tools/mesh_out.py)
                                     [--point-cloud cloud.ply [--point-cloud-stride N --point-cloud-cell M]] [--point-cloud-host cloud_host.ply]
 """
 import argparse
